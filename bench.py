@@ -11,7 +11,10 @@ cross-modal FPN, dynamic mask head -- BASELINE.json config 2 -- followed (N > 1)
 units sharded over ranks (weak scaling, no data-path collective besides the gather).  Inputs and weights are
 synthetic and already resident in HBM when the timed region starts.
 
-Prints ONE JSON line (rank 0).  Extra objects / fields:
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the steps and prints the headline fields (`value`,
+`ms_per_step`, ...).  --dump-outputs DIR writes the arrays the last timed step returned as DIR/<name>.npy (float32; fixed,
+seeded samples of the largest ones past 64 MB in all); inputs and weights are seeded, so two builds compare output for output.
+--full adds the passes below (each of them runs after the timed region):
   roofline          : the kernel that carries the most algorithmic FLOPs of a step -- its FLOPs / its summed launch
                       durations, measured live with events on the launch stream in a second, instrumented (eager) pass
                       (the headline `value` comes from the un-instrumented pass).  `traffic` is NOT measured by this
@@ -27,6 +30,9 @@ Prints ONE JSON line (rank 0).  Extra objects / fields:
                       of the 3 x fp16 split (N=1 only, short pass).
   value_text_cached : clips/s with the per-expression text cache on (RoBERTa evaluated once per distinct caption
                       instead of every clip like the reference; N=1 only, short pass).
+  parity            : the masks of one step against the CPU oracle's on the same clip and weights (with cpu_baseline).
+  value_group8      : N > 1 only: clips/s with 8 clips per forward as one launch program, gather included.
+  group_first_clip_vs_b1_max_rel_err : N > 1 with --group G only: the group's first clip against its own B=1 forward.
 """
 import argparse
 import json
@@ -75,6 +81,53 @@ def _latency_summary(cfg_name):
     return None
 
 
+DUMP_BUDGET = 64 << 20  # bytes written by --dump-outputs, all files together
+
+
+def _dump_outputs(out_dir, outs):
+    """Writes every tensor of the last step's output dicts (`aux_outputs` and the like flattened into the name) as
+    out_dir/<name>.npy in float32 (float64 for integer tensors).  Past DUMP_BUDGET, the largest arrays are replaced, largest
+    first, by 2^20 of their flattened elements at fixed seeded positions (out_dir/<name>_sample.npy), so a dump of the same
+    arguments always holds the same elements."""
+    import numpy as np
+    import torch
+    arrays = []
+
+    def walk(prefix, v):
+        if torch.is_tensor(v):
+            arrays.append((prefix, v))
+        elif isinstance(v, dict):
+            for k in sorted(v):
+                walk(f"{prefix}_{k}" if prefix else str(k), v[k])
+        elif isinstance(v, (list, tuple)):
+            for i, x in enumerate(v):
+                walk(f"{prefix}_{i}", x)
+
+    for j, o in enumerate(outs):
+        walk("" if len(outs) == 1 else f"clip{j}", o)
+    host = []
+    for name, t in arrays:
+        t = t.detach().cpu()
+        host.append((name, t.double() if not (t.is_floating_point() or t.is_complex()) else t.float()))
+    total = sum(t.numel() * t.element_size() for _, t in host)
+    sample = set()
+    for name, t in sorted(host, key=lambda nt: -nt[1].numel() * nt[1].element_size()):
+        if total <= DUMP_BUDGET:
+            break
+        sample.add(name)
+        total -= t.numel() * t.element_size()
+        total += (1 << 20) * t.element_size()
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in host:
+        a = t.numpy()
+        if name in sample:
+            g = torch.Generator().manual_seed(0)
+            idx = torch.randperm(a.size, generator=g)[:1 << 20].sort().values.numpy()
+            np.save(os.path.join(out_dir, name + "_sample.npy"), a.reshape(-1)[idx])
+        else:
+            np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def _ensure_built(local_rank, world):
     """Fresh checkout: the shared object is git-ignored.  Runs BEFORE any GPU / RCCL call (the compiler children must
     not be spawned from a process that has initialised the GPU); local rank 0 builds (the linker output is renamed
@@ -102,6 +155,10 @@ def main():
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--tokens", type=int, default=32)
     ap.add_argument("--backbone", default="swin_t_p4w7")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the roofline, variant, CPU-baseline / parity and N > 1 group passes")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32, at most 64 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-variants", action="store_true", help="skip the value_f32_exact / value_text_cached passes")
@@ -196,6 +253,7 @@ def main():
     targets = [{"size": torch.tensor([H, W])}]
     gather_buf, pending = None, None
     last_local = [None]  # this rank's masks of the last gathered step (the forced world-1 run checks the collective's result)
+    last_outs = [None]  # the per-clip output dicts of the last step (--dump-outputs)
     streams = [torch.cuda.Stream(device=dev) for _ in range(max(C, 4))]
     use_host_ids = False  # the text-cache pass keys the cache on host ids
 
@@ -234,6 +292,7 @@ def main():
                 gather_buf = pending.wait()
             pending = gather_clip_masks_async(local if args.backend == "nccl" else local.cpu(), world * C * Gp, force=force_dist)
             last_local[0] = local
+        last_outs[0] = outs
         return outs[0]
 
     def fence():
@@ -256,6 +315,8 @@ def main():
         return time.perf_counter() - t0
 
     elapsed = timed(args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:  # before any later pass reuses the replayed graph's output buffers
+        _dump_outputs(args.dump_outputs, last_outs[0])
     collective = None
     if dist_on and not args.no_gather:
         # the last step's gathered masks must hold this rank's block at this rank's place (checked on every rank)
@@ -280,7 +341,7 @@ def main():
         return float(t.item())
 
     dist_variants = {}
-    if dist_on and Gp > 1 and rank == 0:
+    if args.full and dist_on and Gp > 1 and rank == 0:
         # BASELINE config 4's per-rank shape is a clip GROUP (64 clips over 8 GPUs = 8 per rank): the first clip of rank 0's group
         # must be what its own B = 1 forward gives (forward_group's contract; another kernel route at the group's row count is
         # allowed: 2e-5 of the tensor's range)
@@ -293,7 +354,7 @@ def main():
         dist_variants["group_first_clip_vs_b1_max_rel_err"] = rel
         if max(rel.values()) > 2e-5:
             raise SystemExit(f"bench.py: the group's first clip differs from its B = 1 forward: {rel}")
-    if dist_on and world > 1 and Gp == 1 and C == 1 and model.use_graph and args.gemm_mode != "f32" and not args.no_variants:
+    if args.full and dist_on and world > 1 and Gp == 1 and C == 1 and model.use_graph and args.gemm_mode != "f32" and not args.no_variants:
         # N > 1 lines also carry the rate at config 4's per-rank shape (8 clips per rank as ONE launch program), gather included;
         # every rank runs it (the step holds the collective)
         Gp = 8
@@ -307,7 +368,7 @@ def main():
     C_saved, C = C, 1  # the instrumented pass, the variants and the parity check run one clip at a time
     Gp_saved, Gp = Gp, 1
     solo = rank == 0 and world == 1 and not force_dist
-    if rank == 0 and not args.no_roofline:
+    if args.full and rank == 0 and not args.no_roofline:
         n_inst = min(args.steps, 40)
         graph_mode, model.use_graph = model.use_graph, False  # per-launch events need eager launches
         step(0, gather=False)  # rank-0-only passes must not enter the collective
@@ -393,7 +454,7 @@ def main():
 
     variants = {}
     exact_masks, product_err = None, {}
-    if solo and not args.no_variants:
+    if args.full and solo and not args.no_variants:
         n_var = max(10, min(args.steps, 60))
         if model.use_graph and C_saved == 1:
             for cc in (2, 4):
@@ -430,7 +491,7 @@ def main():
             ops.set_gemm_mode(args.gemm_mode)
 
     cpu_baseline, parity = None, None
-    if solo and not args.no_cpu_baseline:
+    if args.full and solo and not args.no_cpu_baseline:
         from oracle import tce_oracle as O
         cores = min(32, os.cpu_count() or 1)  # oneDNN/MKL scale poorly past ~32 threads on this graph
         torch.set_num_threads(cores)

@@ -503,8 +503,8 @@ def test_two_rank_gloo_rehearsal_on_one_device(group):
                    TCE_BENCH_ONE_DEVICE="1")
         procs.append(subprocess.Popen([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo",
                                        "--steps", "4", "--warmup", "2", "--frames", "2", "--height", "96", "--width", "128",
-                                       "--tokens", "8", "--no-cpu-baseline", "--no-roofline", "--group", str(group)] +
-                                      # group 1 runs WITH the N > 1 variants (the driver's scaling run does): every rank then also times
+                                       "--tokens", "8", "--full", "--no-cpu-baseline", "--no-roofline", "--group", str(group)] +
+                                      # group 1 runs WITH the N > 1 variants (a --full scaling run does): every rank then also times
                                       # 8 clips per forward, gather included, and the line carries value_group8
                                       (["--no-variants"] if group > 1 else []),
                                       env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
@@ -535,7 +535,7 @@ def test_config4_per_rank_shape_through_the_two_rank_flow():
         env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE="2", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
                    TCE_BENCH_ONE_DEVICE="1")
         procs.append(subprocess.Popen([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo",
-                                       "--steps", "3", "--warmup", "2", "--group", "8", "--no-cpu-baseline", "--no-roofline",
+                                       "--steps", "3", "--warmup", "2", "--group", "8", "--full", "--no-cpu-baseline", "--no-roofline",
                                        "--no-variants"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
     outs = [p.communicate(timeout=900) for p in procs]
     assert all(p.returncode == 0 for p in procs), [o[1][-2000:] for o in outs]
@@ -639,6 +639,30 @@ def test_rccl_world1_bench_path_executes_the_collective():
     assert c["backend"] == "nccl" and c["world"] == 1 and c["forced_world1"] and c["own_block_matches"]
     assert c["gathered_shape"] == [1, 2, 96, 128] and c["bytes_per_rank_per_step"] == 2 * 96 * 128
     assert "RCCL all_gather(uint8 masks)" in line["config"]["parallelism"] and line["value"] > 0
+
+
+def test_bench_plain_line_and_dump_outputs(tmp_path):
+    """A plain bench.py run times exactly --steps steps and prints the headline fields only (the extra passes are --full's);
+    --dump-outputs writes what the last timed step returned, float32, in the shapes a caller receives.  Fresh child process."""
+    import json, os, subprocess, sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    d = tmp_path / "out"
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
+                        "--frames", "2", "--height", "96", "--width", "128", "--tokens", "8", "--dump-outputs", str(d)],
+                       capture_output=True, text=True, timeout=900)
+    assert p.returncode == 0, p.stderr[-3000:]
+    line = json.loads([l for l in p.stdout.strip().splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0 and line["unit"] == "clips/s"
+    assert line["higher_is_better"] is True and line["dtype"].startswith("f32")
+    assert abs(line["ms_per_step"] * 3 - line["timed_region_s"] * 1e3) <= 1.0   # timed_region_s is rounded to the millisecond
+    assert line["roofline"] is None and line["cpu_baseline"] is None and line["parity"] is None
+    assert not [k for k in line if k.startswith("value_")]
+    masks, logits = np.load(d / "pred_masks.npy"), np.load(d / "pred_logits.npy")
+    assert masks.dtype == np.float32 and masks.shape[:2] == (1, 2) and masks.shape[-2:] == (24, 32)
+    assert logits.shape[:3] == masks.shape[:3] and np.isfinite(masks).all() and np.abs(masks).max() > 0
+    assert "memory.npy" in os.listdir(d)
+    assert sum(os.path.getsize(d / f) for f in os.listdir(d)) <= 64 << 20
 
 
 _RCCL_DIST_SCRIPT = r"""

@@ -201,3 +201,28 @@ def test_ffn_split_plan_is_the_calibrated_one(built_lib):
             assert (ws, cnt) == (0, 0), (M, ws, cnt)
     assert l.tce_ffn_split_ws_floats(18000, 192, 768, 2) == 0 and l.tce_ffn_split_ws_floats(18000, 256, 2048, 2) == 0
     assert l.tce_ffn_split_ws_floats(0, 256, 2048, 1) == 0
+
+
+def test_bench_dump_outputs_names_dtypes_and_budget(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every tensor of the last step's output dicts becomes <name>.npy in float32 (integers in float64),
+    nested results flattened into the name; past the byte budget the largest arrays become fixed seeded samples."""
+    import numpy as np
+    import bench
+    g = torch.Generator().manual_seed(3)
+    out = {"pred_masks": torch.randn(1, 2, 3, 40, 50, generator=g), "pred_boxes": torch.rand(1, 2, 3, 4, generator=g).double(),
+           "aux_outputs": [{"pred_logits": torch.randn(1, 2, 3, 1, generator=g)}], "idx": torch.arange(5), "ablated": ["x"]}
+    bench._dump_outputs(str(tmp_path / "all"), [out])
+    got = {f: np.load(tmp_path / "all" / f) for f in sorted(os.listdir(tmp_path / "all"))}
+    assert sorted(got) == ["aux_outputs_0_pred_logits.npy", "idx.npy", "pred_boxes.npy", "pred_masks.npy"]
+    assert got["pred_masks.npy"].dtype == np.float32 and np.array_equal(got["pred_masks.npy"], out["pred_masks"].numpy())
+    assert got["pred_boxes.npy"].dtype == np.float32 and got["idx.npy"].dtype == np.float64
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 16 << 20)
+    big = {"memory": torch.randn(3 << 20, generator=g), "pred_masks": out["pred_masks"]}
+    for d in ("s1", "s2"):
+        bench._dump_outputs(str(tmp_path / d), [big, big])
+    files = sorted(os.listdir(tmp_path / "s1"))
+    assert files == ["clip0_memory_sample.npy", "clip0_pred_masks.npy", "clip1_memory_sample.npy", "clip1_pred_masks.npy"]
+    s = np.load(tmp_path / "s1" / "clip0_memory_sample.npy")
+    assert s.shape == (1 << 20,) and np.isin(s, big["memory"].numpy()).all()
+    for f in files:  # the same arguments give the same elements
+        assert np.array_equal(np.load(tmp_path / "s1" / f), np.load(tmp_path / "s2" / f))
