@@ -324,6 +324,18 @@ int tce_mha_small64_splits_f32(const float* qkv_planes, int32_t splits, const fl
  * sequence only (several captions of one clip group). */
 int tce_mha_small64_seqs_f32(const float* qkv_planes, int32_t splits, const float* bias, float* out, int32_t nseq, int32_t L,
                              int32_t nheads, float scale, tceStream stream);
+/* Ragged clip groups: nseq captions right-padded to L tokens, lens[nseq] (int32, device) their token counts.  As
+ * tce_mha_small64_seqs_f32 (splits = 1 and bias = NULL: one packed qkv [nseq * L, 3E]), but sequence z's keys are its rows
+ * < lens[z] (HF's attention_mask); every query row, pad rows included, is computed over them. */
+int tce_mha_small64_lens_f32(const float* qkv_planes, int32_t splits, const float* bias, float* out, int32_t nseq, int32_t L,
+                             int32_t nheads, float scale, const int32_t* lens, tceStream stream);
+/* Caption lengths of right-padded token ids [nseq, Lmax] (int64, device), one launch:
+ *   lens[b]  = index of the first pad_id of caption b, Lmax if none, at least 1           (int32 [nseq])
+ *   kmask[b][j] = (j >= lens[b])                                                           (uint8 [nseq, Lmax], tce_mha_f32's kmask)
+ *   pos[b * Lmax + j][D] = PositionEmbeddingSine1D(D, normalize=True) under that mask (position_encoding.py:28-50), pads included:
+ *              x = min(j + 1, lens[b]) / (lens[b] + 1e-6) * 2 pi;  pos[2i] = sin(x / 10000^(2i/D)), pos[2i+1] = cos(x / 10000^(2i/D)) */
+int tce_caption_lens_f32(const int64_t* ids, int32_t nseq, int32_t Lmax, int32_t pad_id, int32_t D, int32_t* lens, uint8_t* kmask,
+                         float* pos, tceStream stream);
 
 /* Fused FFN / MLP, the hidden tensor kept on chip (csrc/chain.hip):
  *     out[M,C] = LN_out?( x + W2 act( W1 LN_in?(x) + b1 ) + b2 )        act 1 ReLU | 2 GELU(erf)
@@ -454,6 +466,12 @@ int tce_xattn_ffn_fused_f32(const tceXattnArgs* args, const tceXattnFfnArgs* ffn
  * tce_ffn_packed_bytes(256, 8*group) bytes each, bit-identical to the two-launch form. */
 int tce_xattn_pack_f32(const float* k, const float* v, const float* wqT_ext, const float* wo, void* packed, int32_t L, int32_t group,
                        int32_t batch, tceStream stream);
+/* Ragged clip groups: the same two forms with lens[batch] (int32, device): batch entry b's keys are its rows < lens[b] of L (the
+ * rest get zero W1 / W2 columns and b1 = -1e30, as slots >= L).  Entry b's result equals the plain form with L = lens[b] on its keys. */
+int tce_xattn_prepare_lens_f32(const float* k, const float* v, const float* wqT_ext, const float* wo, float* W1, float* b1, float* W2,
+                               int32_t L, int32_t group, int32_t batch, const int32_t* lens, tceStream stream);
+int tce_xattn_pack_lens_f32(const float* k, const float* v, const float* wqT_ext, const float* wo, void* packed, int32_t L,
+                            int32_t group, int32_t batch, const int32_t* lens, tceStream stream);
 
 /* Swin attention half-block as ONE launch (csrc/swinattn.hip):
  *     out = x + proj( window_attention( LayerNorm_norm1(x) ) )                                   C in {96, 128, 192, 256}

@@ -114,6 +114,8 @@ SIGNATURES = {
     "tce_mha_small64_f32": (i32, [c_f, c_f, i32, i32, f32, c_f]),
     "tce_mha_small64_seqs_f32": (i32, [c_f, i32, c_f, c_f, i32, i32, i32, f32, c_f]),
     "tce_embed_ln_seqs_f32": (i32, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, i32, i32, i32, f32, i32, c_f]),
+    "tce_mha_small64_lens_f32": (i32, [c_f, i32, c_f, c_f, i32, i32, i32, f32, c_f, c_f]),
+    "tce_caption_lens_f32": (i32, [c_f, i32, i32, i32, i32, c_f, c_f, c_f, c_f]),
     "tce_tanh_f32": (i32, [c_f, c_f, i64, c_f]),
     "tce_ffn_packed_bytes": (i64, [i32, i32]),
     "tce_ffn_pack_f32": (i32, [c_f, c_f, c_f, c_f, i32, i32, c_f]),
@@ -127,6 +129,8 @@ SIGNATURES = {
     "tce_xattn_ffn_fused_f32": (i32, [C.POINTER(XattnArgs), C.POINTER(XattnFfnArgs), c_f]),
     "tce_ffn_pack_chain_f32": (i32, [c_f, c_f, c_f, c_f, i32, i32, c_f]),
     "tce_xattn_pack_f32": (i32, [c_f, c_f, c_f, c_f, c_f, i32, i32, i32, c_f]),
+    "tce_xattn_prepare_lens_f32": (i32, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, i32, i32, i32, c_f, c_f]),
+    "tce_xattn_pack_lens_f32": (i32, [c_f, c_f, c_f, c_f, c_f, i32, i32, i32, c_f, c_f]),
     "tce_rowlin_packed_bytes": (i64, [i32, i32]),
     "tce_rowlin_pack_f32": (i32, [c_f, i64, c_f, i32, i32, c_f]),
     "tce_rowlin_f32": (i32, [C.POINTER(RowLinArgs), c_f]),

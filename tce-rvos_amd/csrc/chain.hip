@@ -1109,10 +1109,13 @@ void ffn_launch(const FfnArgs& a, int act, hipStream_t s, int batch = 1) {
 __global__ void __launch_bounds__(256) xattn_prepare_kernel(const float* __restrict__ k, const float* __restrict__ v,
                                                             const float* __restrict__ wqT, const float* __restrict__ wo,
                                                             float* __restrict__ W1, float* __restrict__ b1,
-                                                            float* __restrict__ W2, const int L, const int G) {
+                                                            float* __restrict__ W2, const int L, const int G,
+                                                            const int* __restrict__ lens) {
   // G = key slots per head (32 or 8), hidden = 8 * G; blockIdx.y = batch entry (its own keys / values and outputs)
+  // lens != NULL (ragged clip groups): entry b's keys are slots < lens[b] of its L rows; the rest are padded like slots >= L
   constexpr int C = 256, HD = 32;
   const int Hd = 8 * G;
+  const int Lb = lens ? min(lens[blockIdx.y], L) : L;
   k += (long long)blockIdx.y * L * C;
   v += (long long)blockIdx.y * L * C;
   W1 += (long long)blockIdx.y * Hd * C;
@@ -1122,7 +1125,7 @@ __global__ void __launch_bounds__(256) xattn_prepare_kernel(const float* __restr
   if (idx < Hd * C) {  // W1[h*G + j][i] = sum_c k[j][h*32 + c] * wqT[i][h*32 + c]
     const int r = idx / C, i = idx - r * C, h = r / G, j = r - h * G;
     float a = 0.f;
-    if (j < L) {
+    if (j < Lb) {
       const f32x4* kp = reinterpret_cast<const f32x4*>(k + j * C + h * HD);
       const f32x4* wp = reinterpret_cast<const f32x4*>(wqT + (long long)i * C + h * HD);
 #pragma unroll
@@ -1135,7 +1138,7 @@ __global__ void __launch_bounds__(256) xattn_prepare_kernel(const float* __restr
   } else if (idx < 2 * Hd * C) {  // W2[n][h*G + j] = sum_c wo[n][h*32 + c] * v[j][h*32 + c]
     const int e = idx - Hd * C, n = e / Hd, r = e - n * Hd, h = r / G, j = r - h * G;
     float a = 0.f;
-    if (j < L) {
+    if (j < Lb) {
       const f32x4* vp = reinterpret_cast<const f32x4*>(v + j * C + h * HD);
       const f32x4* wp = reinterpret_cast<const f32x4*>(wo + (long long)n * C + h * HD);
 #pragma unroll
@@ -1148,7 +1151,7 @@ __global__ void __launch_bounds__(256) xattn_prepare_kernel(const float* __restr
   } else if (idx < 2 * Hd * C + Hd) {  // b1[h*G + j] = sum_c k[j][h*32 + c] * wqT[256][h*32 + c]; padded keys: -inf
     const int r = idx - 2 * Hd * C, h = r / G, j = r - h * G;
     float a = -1.0e30f;
-    if (j < L) {
+    if (j < Lb) {
       a = 0.f;
       for (int c = 0; c < HD; ++c) a = fmaf(k[j * C + h * HD + c], wqT[(long long)C * C + h * HD + c], a);
     }
@@ -1165,13 +1168,15 @@ __global__ void __launch_bounds__(256) xattn_pack_fused_kernel(const float* __re
                                                                const float* __restrict__ wqT, const float* __restrict__ wo,
                                                                unsigned char* __restrict__ out, const int L, const int G,
                                                                const int P, const int SL, const long long threads,
-                                                               const long long units, const int single) {
+                                                               const long long units, const int single,
+                                                               const int* __restrict__ lens) {
   // a thread owns one SLOT of a stage: slot 0 = the bias piece, slot sl >= 1 = the (hi, lo) piece pair 2 sl - 1, 2 sl -- the
   // eight folded values are computed once and split into both planes (a thread per piece computed every value twice)
   constexpr int C = 256, HD = 32, KS = C / 16, NT = C / 32;
   const long long tix = (long long)blockIdx.x * 256 + threadIdx.x;
   if (tix >= threads) return;
   const int Hd = 8 * G, NC = Hd / 32;
+  const int Lb = lens ? min(lens[blockIdx.y], L) : L;  // keys of this entry (ragged clip groups: slots >= lens[b] are padded)
   k += (long long)blockIdx.y * L * C;
   v += (long long)blockIdx.y * L * C;
   out += (long long)blockIdx.y * units * 16;
@@ -1200,7 +1205,7 @@ __global__ void __launch_bounds__(256) xattn_pack_fused_kernel(const float* __re
         const int idx = 4 * lane + c, h2 = idx >> 4, i = idx & 15;
         const int row = 32 * it + (i & 3) + 8 * (i >> 2) + 4 * h2, h = row / G, j = row - h * G;
         float a = -1.0e30f;
-        if (j < L) {
+        if (j < Lb) {
           a = 0.f;
           for (int c2 = 0; c2 < HD; ++c2) a = fmaf(k[j * C + h * HD + c2], wqT[(long long)C * C + h * HD + c2], a);
         }
@@ -1221,14 +1226,14 @@ __global__ void __launch_bounds__(256) xattn_pack_fused_kernel(const float* __re
       const int row = 32 * it + r, h = row / G, j = row - h * G;
 #pragma unroll
       for (int e = 0; e < 8; ++e)
-        val[e] = (it < NC && j < L) ? dot32(k + j * C + h * HD, wqT + (long long)(16 * s + 8 * hf + e) * C + h * HD) : 0.f;
+        val[e] = (it < NC && j < Lb) ? dot32(k + j * C + h * HD, wqT + (long long)(16 * s + 8 * hf + e) * C + h * HD) : 0.f;
     } else {  // W2[32 t + r][col] = sum_c wo[n][h*32 + c] * v[key][h*32 + c], col in the accumulator's k order
       const int idx = (p_hi - 1 - 2 * KS) >> 1, t = idx >> 1, s2 = idx & 1, chunk = it - 1;
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         const int col = 32 * chunk + 16 * s2 + 8 * (e >> 2) + 4 * hf + (e & 3);
         const int h = col / G, j = col - h * G;
-        val[e] = (chunk >= 0 && chunk < NC && j < L) ? dot32(wo + (long long)(32 * t + r) * C + h * HD, v + j * C + h * HD) : 0.f;
+        val[e] = (chunk >= 0 && chunk < NC && j < Lb) ? dot32(wo + (long long)(32 * t + r) * C + h * HD, v + j * C + h * HD) : 0.f;
       }
     }
     const HL f = split8(val, single);
@@ -1760,7 +1765,7 @@ extern "C" int tce_xattn_prepare_f32(const float* k, const float* v, const float
                 "tce_xattn_prepare_f32: pointers must be 16-byte aligned");
   const int Hd = 8 * group;
   hipLaunchKernelGGL(xattn_prepare_kernel, dim3(tce_cdiv(2 * Hd * 256 + Hd, 256), batch), dim3(256), 0, (hipStream_t)stream,
-                     k, v, wqT_ext, wo, W1, b1, W2, L, group);
+                     k, v, wqT_ext, wo, W1, b1, W2, L, group, (const int*)nullptr);
   TCE_CHECK_LAUNCH("tce_xattn_prepare_f32");
   return TCE_OK;
 }
@@ -1776,8 +1781,39 @@ extern "C" int tce_xattn_pack_f32(const float* k, const float* v, const float* w
   const int P = ffn_pieces(256), SL = 1 + P / 2;           // slot 0 = piece 0, slot sl = pieces 2 sl - 1, 2 sl
   const long long threads = (long long)(Hd / 32 + 2) * SL * 64;
   hipLaunchKernelGGL(xattn_pack_fused_kernel, dim3(tce_cdiv(threads, 256), batch), dim3(256), 0, (hipStream_t)stream, k, v, wqT_ext,
-                     wo, (unsigned char*)packed, L, group, P, SL, threads, units, tce_gemm_single_pass());
+                     wo, (unsigned char*)packed, L, group, P, SL, threads, units, tce_gemm_single_pass(), (const int*)nullptr);
   TCE_CHECK_LAUNCH("tce_xattn_pack_f32");
+  return TCE_OK;
+}
+
+extern "C" int tce_xattn_prepare_lens_f32(const float* k, const float* v, const float* wqT_ext, const float* wo, float* W1, float* b1,
+                                          float* W2, int32_t L, int32_t group, int32_t batch, const int32_t* lens, tceStream stream) {
+  TCE_CHECK_ARG(k && v && wqT_ext && wo && W1 && b1 && W2 && lens, "tce_xattn_prepare_lens_f32: null pointer");
+  TCE_CHECK_ARG((group == 32 || group == 8) && L >= 1 && L <= group && batch >= 1,
+                "tce_xattn_prepare_lens_f32: group must be 32 or 8 and 1 <= L <= group (L=%d group=%d)", L, group);
+  TCE_CHECK_ARG(tce_aligned16(k) && tce_aligned16(v) && tce_aligned16(wqT_ext) && tce_aligned16(wo),
+                "tce_xattn_prepare_lens_f32: pointers must be 16-byte aligned");
+  const int Hd = 8 * group;
+  hipLaunchKernelGGL(xattn_prepare_kernel, dim3(tce_cdiv(2 * Hd * 256 + Hd, 256), batch), dim3(256), 0, (hipStream_t)stream,
+                     k, v, wqT_ext, wo, W1, b1, W2, L, group, (const int*)lens);
+  TCE_CHECK_LAUNCH("tce_xattn_prepare_lens_f32");
+  return TCE_OK;
+}
+
+extern "C" int tce_xattn_pack_lens_f32(const float* k, const float* v, const float* wqT_ext, const float* wo, void* packed, int32_t L,
+                                       int32_t group, int32_t batch, const int32_t* lens, tceStream stream) {
+  TCE_CHECK_ARG(k && v && wqT_ext && wo && packed && lens, "tce_xattn_pack_lens_f32: null pointer");
+  TCE_CHECK_ARG((group == 32 || group == 8) && L > 0 && L <= group && batch > 0,
+                "tce_xattn_pack_lens_f32: group must be 32 or 8, 0 < L <= group");
+  TCE_CHECK_ARG(tce_aligned16(k) && tce_aligned16(v) && tce_aligned16(wqT_ext) && tce_aligned16(wo) && tce_aligned16(packed),
+                "tce_xattn_pack_lens_f32: pointers must be 16-byte aligned");
+  const int Hd = 8 * group;
+  const long long units = ffn_units(256, Hd);
+  const int P = ffn_pieces(256), SL = 1 + P / 2;
+  const long long threads = (long long)(Hd / 32 + 2) * SL * 64;
+  hipLaunchKernelGGL(xattn_pack_fused_kernel, dim3(tce_cdiv(threads, 256), batch), dim3(256), 0, (hipStream_t)stream, k, v, wqT_ext,
+                     wo, (unsigned char*)packed, L, group, P, SL, threads, units, tce_gemm_single_pass(), (const int*)lens);
+  TCE_CHECK_LAUNCH("tce_xattn_pack_lens_f32");
   return TCE_OK;
 }
 

@@ -58,15 +58,19 @@ __global__ void __launch_bounds__(256) embed_ln_kernel(const int64_t* __restrict
 // of the whole sentence (L <= 128 tokens) live in LDS; lane = query row.
 // splits > 1 / bias: qkv is given as `splits` partial planes [L, 3E] (split-K partial sums, plane stride L*3E) + a bias [3E]:
 // the reduction of the projection rides in this kernel's loads (no reduce launch between projection and attention).
+// lens != NULL (right-padded captions of a ragged clip group): sequence z's keys stop at lens[z] (HF's attention_mask); every
+// query row is still computed, pad rows included, each over the same keys in the same order as the un-padded sequence.
 template <int HDIM, int LMAX>
 __global__ void __launch_bounds__(256) mha_small_kernel(const float* __restrict__ qkv, float* __restrict__ out, int L,
-                                                        int nheads, float scale, int splits, const float* __restrict__ bias) {
+                                                        int nheads, float scale, int splits, const float* __restrict__ bias,
+                                                        const int* __restrict__ lens) {
   // gridDim.z sequences of L tokens stacked as rows: sequence z owns rows z*L .. z*L + L - 1 of every plane and of `out`
   __shared__ __attribute__((aligned(16))) float sK[LMAX * HDIM];
   __shared__ __attribute__((aligned(16))) float sV[LMAX * HDIM];
   const int h = blockIdx.x;
   const int E = nheads * HDIM;
   const int tid = threadIdx.x;
+  const int Lk = lens ? min(max(lens[blockIdx.z], 1), L) : L;  // keys of this sequence
   const long long plane = (long long)L * gridDim.z * 3 * E;
   qkv += (long long)blockIdx.z * L * 3 * E;
   out += (long long)blockIdx.z * L * E;
@@ -77,7 +81,7 @@ __global__ void __launch_bounds__(256) mha_small_kernel(const float* __restrict_
     return v;
   };
   // 256 threads stage K / V (with partial planes that is three times the loads); the upper 128 leave after the barrier
-  for (int i = tid; i < L * (HDIM / 4); i += 256) {
+  for (int i = tid; i < Lk * (HDIM / 4); i += 256) {
     const int j = i / (HDIM / 4), d4 = i % (HDIM / 4);
     const float* p = qkv + (long long)j * 3 * E + h * HDIM + d4 * 4;
     *reinterpret_cast<f32x4*>(&sK[j * HDIM + d4 * 4]) = ld4(p + E, E + h * HDIM + d4 * 4);
@@ -104,7 +108,7 @@ __global__ void __launch_bounds__(256) mha_small_kernel(const float* __restrict_
   float o[QD];
 #pragma unroll
   for (int d = 0; d < QD; ++d) o[d] = 0.f;
-  for (int j = 0; j < L; ++j) {  // online softmax, one key at a time (L is tiny)
+  for (int j = 0; j < Lk; ++j) {  // online softmax, one key at a time (L is tiny)
     const f32x4* kp = reinterpret_cast<const f32x4*>(&sK[j * HDIM + part * QD]);
     float a = 0.f;
 #pragma unroll
@@ -136,6 +140,32 @@ __global__ void __launch_bounds__(256) mha_small_kernel(const float* __restrict_
   for (int d4 = 0; d4 < QD / 4; ++d4) {
     f32x4 v = {o[d4 * 4] * inv, o[d4 * 4 + 1] * inv, o[d4 * 4 + 2] * inv, o[d4 * 4 + 3] * inv};
     *reinterpret_cast<f32x4*>(po + d4 * 4) = v;
+  }
+}
+
+// Caption lengths of right-padded ids [G, Lmax] (one workgroup per caption): lens[b] = index of the first pad id, Lmax if
+// none, at least 1; kmask[b][j] = (j >= lens[b]); pos[b * Lmax + j][:] = PositionEmbeddingSine1D(normalize=True) with that
+// mask (position_encoding.py:28-50): x = cumsum(not_mask) = min(j + 1, lens), x / (lens + 1e-6) * 2 pi, sin / cos interleaved.
+__global__ void __launch_bounds__(256) caption_lens_kernel(const int64_t* __restrict__ ids, int Lmax, int pad_id, int D,
+                                                           int* __restrict__ lens, unsigned char* __restrict__ kmask,
+                                                           float* __restrict__ pos) {
+  __shared__ int first;
+  const int b = blockIdx.x, tid = threadIdx.x;
+  if (tid == 0) first = Lmax;
+  __syncthreads();
+  for (int j = tid; j < Lmax; j += 256)
+    if (ids[(long long)b * Lmax + j] == pad_id) atomicMin(&first, j);
+  __syncthreads();
+  const int n = max(first, 1);
+  if (tid == 0) lens[b] = n;
+  for (int j = tid; j < Lmax; j += 256) kmask[(long long)b * Lmax + j] = j >= n;
+  const float last = (float)n + 1e-6f;
+  for (int e = tid; e < Lmax * D; e += 256) {
+    const int j = e / D, c = e - j * D;
+    const float x = (float)min(j + 1, n) / last * 6.28318530717958647692f;
+    const float dim_t = powf(10000.0f, (float)(2 * (c >> 1)) / (float)D);
+    const float a = x / dim_t;
+    pos[(long long)b * Lmax * D + e] = (c & 1) ? cosf(a) : sinf(a);
   }
 }
 
@@ -175,7 +205,7 @@ extern "C" int tce_mha_small64_f32(const float* qkv, float* out, int32_t L, int3
   TCE_CHECK_ARG(L > 0 && L <= 128, "tce_mha_small64_f32: sequence length %d outside 1..128", L);
   TCE_CHECK_ARG(tce_aligned16(qkv) && tce_aligned16(out), "tce_mha_small64_f32: pointers must be 16-byte aligned");
   hipLaunchKernelGGL((mha_small_kernel<64, 128>), dim3(nheads, tce_cdiv(L, 32)), dim3(256), 0, (hipStream_t)stream, qkv, out, L,
-                     nheads, scale, 1, (const float*)nullptr);
+                     nheads, scale, 1, (const float*)nullptr, (const int*)nullptr);
   TCE_CHECK_LAUNCH("tce_mha_small64_f32");
   return TCE_OK;
 }
@@ -187,7 +217,7 @@ extern "C" int tce_mha_small64_splits_f32(const float* qkv_planes, int32_t split
   TCE_CHECK_ARG(tce_aligned16(qkv_planes) && tce_aligned16(out) && (!bias || tce_aligned16(bias)),
                 "tce_mha_small64_splits_f32: pointers must be 16-byte aligned");
   hipLaunchKernelGGL((mha_small_kernel<64, 128>), dim3(nheads, tce_cdiv(L, 32)), dim3(256), 0, (hipStream_t)stream, qkv_planes, out,
-                     L, nheads, scale, splits, bias);
+                     L, nheads, scale, splits, bias, (const int*)nullptr);
   TCE_CHECK_LAUNCH("tce_mha_small64_splits_f32");
   return TCE_OK;
 }
@@ -199,8 +229,30 @@ extern "C" int tce_mha_small64_seqs_f32(const float* qkv_planes, int32_t splits,
   TCE_CHECK_ARG(tce_aligned16(qkv_planes) && tce_aligned16(out) && (!bias || tce_aligned16(bias)),
                 "tce_mha_small64_seqs_f32: pointers must be 16-byte aligned");
   hipLaunchKernelGGL((mha_small_kernel<64, 128>), dim3(nheads, tce_cdiv(L, 32), nseq), dim3(256), 0, (hipStream_t)stream, qkv_planes,
-                     out, L, nheads, scale, splits, bias);
+                     out, L, nheads, scale, splits, bias, (const int*)nullptr);
   TCE_CHECK_LAUNCH("tce_mha_small64_seqs_f32");
+  return TCE_OK;
+}
+
+extern "C" int tce_mha_small64_lens_f32(const float* qkv_planes, int32_t splits, const float* bias, float* out, int32_t nseq,
+                                        int32_t L, int32_t nheads, float scale, const int32_t* lens, tceStream stream) {
+  TCE_CHECK_ARG(qkv_planes && out && lens && nheads > 0 && splits >= 1 && splits <= 64 && nseq > 0 && nseq <= 64,
+                "tce_mha_small64_lens_f32: bad arguments");
+  TCE_CHECK_ARG(L > 0 && L <= 128, "tce_mha_small64_lens_f32: sequence length %d outside 1..128", L);
+  TCE_CHECK_ARG(tce_aligned16(qkv_planes) && tce_aligned16(out) && (!bias || tce_aligned16(bias)),
+                "tce_mha_small64_lens_f32: pointers must be 16-byte aligned");
+  hipLaunchKernelGGL((mha_small_kernel<64, 128>), dim3(nheads, tce_cdiv(L, 32), nseq), dim3(256), 0, (hipStream_t)stream, qkv_planes,
+                     out, L, nheads, scale, splits, bias, (const int*)lens);
+  TCE_CHECK_LAUNCH("tce_mha_small64_lens_f32");
+  return TCE_OK;
+}
+
+extern "C" int tce_caption_lens_f32(const int64_t* ids, int32_t nseq, int32_t Lmax, int32_t pad_id, int32_t D, int32_t* lens,
+                                    uint8_t* kmask, float* pos, tceStream stream) {
+  TCE_CHECK_ARG(ids && lens && kmask && pos && nseq > 0 && Lmax > 0 && D > 0 && D % 2 == 0, "tce_caption_lens_f32: bad arguments");
+  hipLaunchKernelGGL(caption_lens_kernel, dim3(nseq), dim3(256), 0, (hipStream_t)stream, ids, Lmax, pad_id, D, (int*)lens,
+                     (unsigned char*)kmask, pos);
+  TCE_CHECK_LAUNCH("tce_caption_lens_f32");
   return TCE_OK;
 }
 

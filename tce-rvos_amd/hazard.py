@@ -382,6 +382,16 @@ MODELS = {
     "tce_xattn_pack_f32": lambda a: (
         [dense(_p(a[0]), a[7] * a[5] * 256 * F), dense(_p(a[1]), a[7] * a[5] * 256 * F), dense(_p(a[2]), 257 * 256 * F), dense(_p(a[3]), 256 * 256 * F)],
         [dense(_p(a[4]), a[7] * _lib.lib_raw().tce_ffn_packed_bytes(256, 8 * a[6]))]),
+    # k, v, wqT, wo, W1, b1, W2, L, group, batch, lens
+    "tce_xattn_prepare_lens_f32": lambda a: (
+        [dense(_p(a[0]), a[9] * a[7] * 256 * F), dense(_p(a[1]), a[9] * a[7] * 256 * F), dense(_p(a[2]), 257 * 256 * F),
+         dense(_p(a[3]), 256 * 256 * F), dense(_p(a[10]), a[9] * 4)],
+        [dense(_p(a[4]), a[9] * 8 * a[8] * 256 * F), dense(_p(a[5]), a[9] * 8 * a[8] * F), dense(_p(a[6]), a[9] * 8 * a[8] * 256 * F)]),
+    # k, v, wqT, wo, packed, L, group, batch, lens
+    "tce_xattn_pack_lens_f32": lambda a: (
+        [dense(_p(a[0]), a[7] * a[5] * 256 * F), dense(_p(a[1]), a[7] * a[5] * 256 * F), dense(_p(a[2]), 257 * 256 * F), dense(_p(a[3]), 256 * 256 * F),
+         dense(_p(a[8]), a[7] * 4)],
+        [dense(_p(a[4]), a[7] * _lib.lib_raw().tce_ffn_packed_bytes(256, 8 * a[6]))]),
     "tce_rowlin_pack_f32": lambda a: ([strided(_p(a[0]), a[4] * F, (a[3], a[1] * F))],
                                       [dense(_p(a[2]), _lib.lib_raw().tce_rowlin_packed_bytes(a[3], a[4]))]),
     "tce_rowlin_f32": lambda a: _rowlin(_st(a[0])),
@@ -408,6 +418,13 @@ MODELS = {
     # planes, splits, bias, out, nseq, L, nheads
     "tce_mha_small64_seqs_f32": lambda a: ([dense(_p(a[0]), a[1] * a[4] * a[5] * 3 * a[6] * 64 * F), dense(_p(a[2]), 3 * a[6] * 64 * F)],
                                            [dense(_p(a[3]), a[4] * a[5] * a[6] * 64 * F)]),
+    # planes, splits, bias, out, nseq, L, nheads, scale, lens
+    "tce_mha_small64_lens_f32": lambda a: ([dense(_p(a[0]), a[1] * a[4] * a[5] * 3 * a[6] * 64 * F), dense(_p(a[2]), 3 * a[6] * 64 * F),
+                                            dense(_p(a[8]), a[4] * 4)],
+                                           [dense(_p(a[3]), a[4] * a[5] * a[6] * 64 * F)]),
+    # ids, nseq, Lmax, pad_id, D, lens, kmask, pos
+    "tce_caption_lens_f32": lambda a: ([dense(_p(a[0]), a[1] * a[2] * 8)],
+                                       [dense(_p(a[5]), a[1] * 4), dense(_p(a[6]), a[1] * a[2]), dense(_p(a[7]), a[1] * a[2] * a[4] * F)]),
     # ids, word, pos, type0, gamma, beta, out, nseq, seq_len, C
     "tce_embed_ln_seqs_f32": lambda a: ([dense(_p(a[0]), a[7] * a[8] * 8), dense(_p(a[4]), a[9] * F), dense(_p(a[5]), a[9] * F)],
                                         [dense(_p(a[6]), a[7] * a[8] * a[9] * F)]),

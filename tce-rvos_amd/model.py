@@ -673,8 +673,25 @@ class ReferFormer(nn.Module):
         ops.range_snapshot_async(frames.device)
         return self._tag_diagnostics(out)
 
+    def _pad_id(self):
+        return int(getattr(getattr(self.text_encoder, "config", None), "pad_token_id", 1) or 1)
+
+    def _group_text(self, ids, ragged):
+        """The text callable of a clip group's launch program.  Ragged: the captions' lengths, key padding mask and position table
+        come from the ids on the device in the same program (ops.caption_lens), so a captured graph follows the lengths that its
+        static id buffer holds at each replay -- nothing about them is baked in at capture time."""
+        if not ragged:
+            return lambda alloc: self._text_plan().forward(ids, alloc)
+        pad_id = self._pad_id()
+
+        def text(alloc):
+            rag = ops.caption_lens(ids, pad_id, alloc, self.cfg.hidden_dim)
+            hid, pooled = self._text_plan().forward(ids, alloc, lens=rag[0])
+            return hid, pooled, rag
+        return text
+
     @torch.no_grad()
-    def forward_group(self, clips, captions, targets, slot=0):
+    def forward_group(self, clips, captions, targets, slot=0, ragged=False):
         """G independent clips in ONE launch program (an extension; `forward` is the reference's boundary).
 
         clips: list of G tensors [T,3,H,W] of the SAME shape on the GPU; captions: LongTensor [G, L] of token ids, or a list of G
@@ -688,10 +705,26 @@ class ReferFormer(nn.Module):
         length are INVALID input (rejected on the first sighting of a group shape).  Video-Swin's 3-D windows span a clip's frames: its window kernel is launched
         per clip, everything else is shared.  When `clips` holds the SAME tensor G times (G expressions of one video, the inner loop
         of inference_ytvos.py) the backbone runs once for the group.  Limits: one clip shape and one caption length per group, un-padded clips, G <= 64 (the
-        text layers leave the weight-stream kernels for the tiled GEMMs above 128 caption tokens in all)."""
+        text layers leave the weight-stream kernels for the tiled GEMMs above 128 caption tokens in all).
+
+        ragged=True (opt-in): the captions may have different token lengths.  Strings are tokenised as `forward` tokenises them
+        and right-padded with the pad id to the longest; a LongTensor [G, Lmax] is taken as right-padded with pad_token_id
+        (caption g's length = index of its first pad id, Lmax if none, at least 1; derived on the device, no read-back).  Host ids
+        with an interior pad or an empty caption raise ValueError.  Each clip's result is its B = 1 forward on the un-padded
+        caption: the text self-attention and every text cross-attention take the pads as masked keys, the 1-D position map is
+        normalised by each caption's length (position_encoding.py:28-50).  One captured graph serves every length mix of a
+        (G, Lmax, clip shape)."""
         G = len(clips)
+        if ragged:
+            pad_id = self._pad_id()
+            if isinstance(captions, (list, tuple)):
+                captions, _ = pad_captions([self._tokenise([c], clips[0].device)[0] for c in captions], pad_id)
+            elif torch.is_tensor(captions) and not captions.is_cuda:
+                caption_lengths(captions, pad_id)  # validation only: the device derives the lengths itself
         if G == 1:
             cap = captions[:1] if torch.is_tensor(captions) else [captions[0]]
+            if ragged and torch.is_tensor(cap):  # one caption: no padding needed (its length on the host: one read-back)
+                cap = cap[:, :caption_lengths(cap.cpu(), self._pad_id())[0]]
             return [self.forward([clips[0]], cap, targets[:1], slot=slot)]
         shp = tuple(clips[0].shape)
         if any(tuple(c.shape) != shp or not c.is_cuda for c in clips) or len(shp) != 4:
@@ -719,16 +752,18 @@ class ReferFormer(nn.Module):
         # one clip, G captions (the expressions of a video: the SAME tensor G times): the backbone runs once
         shared = all(c is clips[0] for c in clips[1:])
         srcs = [clips[0]] if shared else list(clips)
-        key = ("group", G, shared, shp, tuple(ids.shape), img_h, img_w, self.training, int(slot), self._stamp)
+        if ragged:
+            ids = ids.to(torch.int64).contiguous()
+        # ragged: the flag, never the lengths (they live in the static id buffer)
+        key = ("group", G, shared, shp, tuple(ids.shape), img_h, img_w, self.training, int(slot), self._stamp) + (("ragged",) if ragged else ())
 
         def frames_now():
             return srcs[0].to(torch.float32).contiguous() if shared else torch.cat([c.to(torch.float32) for c in srcs], 0)
 
         def eager():
-            return self._run(frames_now(), lambda alloc: self._text_plan().forward(ids, alloc), img_h, img_w, None, slot, groups=G,
-                             shared=shared)
+            return self._run(frames_now(), self._group_text(ids, ragged), img_h, img_w, None, slot, groups=G, shared=shared)
 
-        if key not in self._group_checked:
+        if not ragged and key not in self._group_checked:
             self._group_checked.add(key)
             # a [G, L] id tensor built by PADDING G captions to one length would silently differ from each clip's B = 1 forward
             # (the text kernels take every position as a token; the reference masks pads through attention_mask /
@@ -743,10 +778,7 @@ class ReferFormer(nn.Module):
             ent = self._graphs.get(key)
             if ent is None:
                 st = (frames_now().clone() if shared else frames_now(), ids.clone())
-
-                def text_fn(alloc):
-                    return self._text_plan().forward(st[1], alloc)
-
+                text_fn = self._group_text(st[1], ragged)
                 like = types.SimpleNamespace(shape=(G * Tc,) + shp[1:], device=dev)  # arenas are sized for the whole group
                 ent = self._capture(key, st, lambda res: self._run(st[0], text_fn, img_h, img_w, res, groups=G, shared=shared), like, slot)
             if ent is None:
@@ -915,11 +947,12 @@ class ReferFormer(nn.Module):
                 st[3])
 
     @torch.no_grad()
-    def hazard_check(self, frames, ids, img_hw=None, valid=None, slot=0, dry=False, groups=1, shared=False):
+    def hazard_check(self, frames, ids, img_hw=None, valid=None, slot=0, dry=False, groups=1, shared=False, ragged=False):
         """Records ONE pass of the clip's launch program on the capture topology (the same arenas, side streams, forks and
         joins a captured graph is built from) and checks it for races: any two launches not ordered by a fork / join edge
         must touch disjoint memory (tce_rvos_amd/hazard.py).  frames [T,3,H,W] and token ids [1,L] on the GPU.
-        dry=True: the recorded pass launches nothing (negative controls).  Returns a hazard.Report (`.clean`, `str()`);
+        dry=True: the recorded pass launches nothing (negative controls).  ragged=True: the ragged clip-group program
+        (forward_group(..., ragged=True); ids [groups, Lmax] right-padded).  Returns a hazard.Report (`.clean`, `str()`);
         results of the pass are discarded."""
         from . import hazard
         frames = frames.to(torch.float32).contiguous()
@@ -928,7 +961,7 @@ class ReferFormer(nn.Module):
         self._ensure_packed()
         res = self._branch_resources(types.SimpleNamespace(shape=(T * (groups if shared else 1), 3, H0, W0), device=frames.device), slot)
         st = (frames.clone(), ids.to(frames.device).clone())
-        run = lambda: self._run(st[0], lambda alloc: self._text_plan().forward(st[1], alloc), img_h, img_w, res, valid=valid, shared=shared,  # noqa: E731
+        run = lambda: self._run(st[0], self._group_text(st[1], ragged), img_h, img_w, res, valid=valid, shared=shared,  # noqa: E731
                                 groups=groups)
         main = torch.cuda.Stream(device=frames.device)  # like a capture: never the legacy default stream (it syncs with all)
         main.wait_stream(torch.cuda.current_stream())
@@ -1052,6 +1085,37 @@ class ReferFormer(nn.Module):
                 return self._tag_diagnostics(self._run(frames, (text_hidden, text_pooled), img_h, img_w, None, slot, valid=valid_hw,
                                                        select=select))
         return self._tag_diagnostics(self._replay(key, ent, (frames, text_hidden, text_pooled)))
+
+
+def caption_lengths(ids, pad_id):
+    """Token counts of right-padded host ids [G, Lmax] (ragged clip groups): caption g's length is the index of its first pad id,
+    Lmax if it has none.  ValueError for a caption with no token or a pad id followed by a non-pad id."""
+    if not torch.is_tensor(ids) or ids.dim() != 2:
+        raise ValueError("ragged captions: token ids [G, Lmax]")
+    lens = []
+    for g, row in enumerate(ids.tolist()):
+        n = row.index(pad_id) if pad_id in row else len(row)
+        if n == 0:
+            raise ValueError(f"ragged captions: caption {g} has no token")
+        if any(t != pad_id for t in row[n:]):
+            raise ValueError(f"ragged captions: caption {g} has a pad id inside it (position {n}): pads go at the right end only")
+        lens.append(n)
+    return lens
+
+
+def pad_captions(rows, pad_id):
+    """Host id rows [1, L_g] of G captions -> (ids [G, Lmax] right-padded with pad_id, lengths).  Validated as caption_lengths."""
+    rows = [r.reshape(-1).to(torch.int64).cpu() for r in rows]
+    if not rows:
+        raise ValueError("ragged captions: no caption")
+    Lmax = max(int(r.numel()) for r in rows)
+    ids = torch.full((len(rows), Lmax), int(pad_id), dtype=torch.int64)
+    for g, r in enumerate(rows):
+        ids[g, :r.numel()] = r
+    lens = caption_lengths(ids, pad_id)
+    if lens != [int(r.numel()) for r in rows]:
+        raise ValueError("ragged captions: a caption contains the pad id")
+    return ids, lens
 
 
 def _flat_outputs(out):

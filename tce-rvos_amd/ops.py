@@ -516,6 +516,19 @@ def mha_core(q, k, v, batch, nheads, Lq, Lk, ldq, ldk, ldv, sQ, sK, sV, out, ldo
     return out
 
 
+def caption_lens(ids, pad_id, alloc, D=256):
+    """Ragged clip groups: right-padded token ids int64 [G, Lmax] on the device -> (lens int32 [G], kmask uint8 [G, Lmax] (non-zero
+    = pad), per-caption 1-D sine position table [G * Lmax, D]) in one launch (tce_caption_lens_f32).  Derived on the device from
+    the ids, so a captured graph follows whatever lengths its static id buffer holds at replay."""
+    if ids.dtype != torch.int64 or ids.dim() != 2 or not ids.is_contiguous():
+        raise ValueError("caption_lens: contiguous int64 ids [G, Lmax]")
+    G, Lmax = int(ids.shape[0]), int(ids.shape[1])
+    lens, kmask, pos = alloc(G, dtype=torch.int32), alloc(G, Lmax, dtype=torch.uint8), alloc(G * Lmax, D)
+    check(lib().tce_caption_lens_f32(ids.data_ptr(), G, Lmax, int(pad_id), D, lens.data_ptr(), kmask.data_ptr(), pos.data_ptr(),
+                                     _stream()), "tce_caption_lens_f32")
+    return lens, kmask, pos
+
+
 def ms_deform_attn_forward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, im2col_step=64):
     """Drop-in for MultiScaleDeformableAttention_update.ms_deform_attn_forward (ms_deform_attn_func.py:26-27)."""
     for t, n in ((value, "value"), (sampling_loc, "sampling_loc"), (attn_weight, "attn_weight")):
@@ -1170,20 +1183,30 @@ def xattn_static(wq, bq, scale=32 ** -0.5):
     return (torch.cat([wq.t(), bq[None]], 0) * scale).contiguous()
 
 
-def xattn_pack(k, v, wqT_ext, wo, L, alloc, group=32, batch=1):
+def xattn_pack(k, v, wqT_ext, wo, L, alloc, group=32, batch=1, lens=None):
     """Per clip: folds the projected keys / values ([batch][L,256]) of the 8 heads into W1, b1, W2 and packs the weight
-    stream(s).  Returns a uint8 tensor [batch, bytes_per_stream]."""
+    stream(s).  Returns a uint8 tensor [batch, bytes_per_stream].  lens: int32 [batch] on the device (ragged clip groups):
+    entry b's keys are its rows < lens[b] (tce_xattn_pack_lens_f32 / tce_xattn_prepare_lens_f32)."""
     _chk(k, "k")
     _chk(v, "v")
     Hd = 8 * group
     if XATTN_PACK_FUSED:  # fold + pack in one launch (bit-identical stream)
         pk = alloc(batch, lib().tce_ffn_packed_bytes(256, Hd), dtype=torch.uint8)
+        if lens is not None:
+            check(lib().tce_xattn_pack_lens_f32(k.data_ptr(), v.data_ptr(), wqT_ext.data_ptr(), wo.data_ptr(), pk.data_ptr(), L, group,
+                                                batch, lens.data_ptr(), _stream()), "tce_xattn_pack_lens_f32")
+            return pk
         check(lib().tce_xattn_pack_f32(k.data_ptr(), v.data_ptr(), wqT_ext.data_ptr(), wo.data_ptr(), pk.data_ptr(), L, group, batch,
                                        _stream()), "tce_xattn_pack_f32")
         return pk
     W1, b1, W2 = alloc(batch, Hd, 256), alloc(batch, Hd), alloc(batch, 256, Hd)
-    check(lib().tce_xattn_prepare_f32(k.data_ptr(), v.data_ptr(), wqT_ext.data_ptr(), wo.data_ptr(), W1.data_ptr(), b1.data_ptr(),
-                                      W2.data_ptr(), L, group, batch, _stream()), "tce_xattn_prepare_f32")
+    if lens is not None:
+        check(lib().tce_xattn_prepare_lens_f32(k.data_ptr(), v.data_ptr(), wqT_ext.data_ptr(), wo.data_ptr(), W1.data_ptr(),
+                                               b1.data_ptr(), W2.data_ptr(), L, group, batch, lens.data_ptr(), _stream()),
+              "tce_xattn_prepare_lens_f32")
+    else:
+        check(lib().tce_xattn_prepare_f32(k.data_ptr(), v.data_ptr(), wqT_ext.data_ptr(), wo.data_ptr(), W1.data_ptr(), b1.data_ptr(),
+                                          W2.data_ptr(), L, group, batch, _stream()), "tce_xattn_prepare_f32")
     nbytes = lib().tce_ffn_packed_bytes(256, Hd)
     pk = alloc(batch, nbytes, dtype=torch.uint8)
     check(lib().tce_ffn_pack_batched_f32(W1.data_ptr(), b1.data_ptr(), W2.data_ptr(), pk.data_ptr(), 256, Hd, batch, _stream()),

@@ -193,17 +193,22 @@ def _run_clip(model, frames, text, img_h, img_w, ar, side_arena=None, side_strea
         clip_start = torch.cuda.Event()
         clip_start.record()
     text_fork = _Fork(side_stream, after=clip_start)
-    L = fk = fv = fpk = sent = None
+    L = fk = fv = fpk = fkm = sent = None
     vl_sites = {}
     text_in = text
 
     def text_stage():
-        nonlocal L, fk, fv, fpk, sent
+        nonlocal L, fk, fv, fpk, fkm, sent
+        rag = None
         with text_fork, model.arith("text"):
             if "text" in ABLATE and callable(text_in):  # diagnostic: the RoBERTa layers skipped (garbage features)
                 text_hidden, text_pooled = tA(32, cfg.text_hidden), tA(cfg.text_hidden)
             else:
-                text_hidden, text_pooled = text_in(tA) if callable(text_in) else text_in
+                got = text_in(tA) if callable(text_in) else text_in
+                text_hidden, text_pooled = got[0], got[1]
+                # ragged clip group: (lens [G], kmask [G, L], position table [G*L, 256]) of captions right-padded to L
+                # (ops.caption_lens, derived on the device from the ids); pad rows are computed but never read as keys
+                rag = got[2] if len(got) > 2 else None
             GL = text_hidden.shape[0]  # G captions of L tokens, caption-major
             if GL % G:
                 raise ValueError("clip group: the text features must hold `groups` captions of equal length")
@@ -219,28 +224,33 @@ def _run_clip(model, frames, text, img_h, img_w, ar, side_arena=None, side_strea
                 text = ops.layernorm(tmp, w["resizer.layer_norm.weight"], w["resizer.layer_norm.bias"], 1e-12, out=tA(GL, D))
                 tmp = _lin(tA, text_pooled, G, TH, w["resizer.fc.weight"], w["resizer.fc.bias"], D)
                 sent = ops.layernorm(tmp, w["resizer.layer_norm.weight"], w["resizer.layer_norm.bias"], 1e-12, out=tA(G, D))
-            text_pos = model._text_pos(L, dev)
+            if rag is None:
+                lens = tkm = None
+                text_pos, pos_rows, pos_stride = model._text_pos(L, dev), L, 0  # one position map shared by the captions
+            else:
+                lens, tkm, text_pos = rag
+                pos_rows, pos_stride = GL, L * D  # each caption's own map (normalised by its length)
             xattn_ok = L <= 32 and ops.get_gemm_mode() != "f32"
 
             def text_site(pre, rows, group):
-                """(k, v, folded stream or None) of the cross-attention module `pre` whose largest launch has `rows` rows.
-                The folded stream is packed in the arithmetic of the site group that consumes it."""
-                k = tA(GL, D)  # [G][L, D]: every caption's keys (the position map is shared by the captions)
+                """(k, v, folded stream or None, key padding mask or None) of the cross-attention module `pre` whose largest launch
+                has `rows` rows.  The folded stream is packed in the arithmetic of the site group that consumes it."""
+                k = tA(GL, D)  # [G][L, D]: every caption's keys
                 if few(GL, "text"):  # key (text + position) and value projections of the site in one launch
                     v = tA(GL, D)
                     FR(text, GL, D, [(w[pre + "k.w"], w[pre + "k.b"], k, D, D, True, 0), (w[pre + "v.w"], w[pre + "v.b"], v, D, D, False, 0)],
-                       a2=text_pos, lda2=D, a2_rows=L)
+                       a2=text_pos, lda2=D, a2_rows=pos_rows)
                 else:
                     gemm_ex(text, w[pre + "k.w"], k, L, D, D, D, D, D, bias=w[pre + "k.b"], a2=text_pos, lda2=D, batch=G, sA=L * D,
-                            sA2=0, sC=L * D)
+                            sA2=pos_stride, sC=L * D)
                     v = _lin(tA, text, GL, D, w[pre + "v.w"], w[pre + "v.b"], D)
                 pk = None
                 if xattn_ok and rows >= ops.XATTN_MIN_ROWS:
                     with model.arith(group):  # one folded weight stream per caption
-                        pk = ops.xattn_pack(k, v, w[pre + "q.wT:x"], w[pre + "out_proj.weight"], L, tA, batch=G)
-                return k, v, pk
+                        pk = ops.xattn_pack(k, v, w[pre + "q.wT:x"], w[pre + "out_proj.weight"], L, tA, batch=G, lens=lens)
+                return k, v, pk, tkm
 
-            fk, fv, fpk = text_site("fusion_module.multihead_attn.", Tc * lvl_sizes[0][0] * lvl_sizes[0][1], "input_proj")
+            fk, fv, fpk, fkm = text_site("fusion_module.multihead_attn.", Tc * lvl_sizes[0][0] * lvl_sizes[0][1], "input_proj")
             if cfg.vlblock:
                 for stage in (4, 3, 2, 1):
                     h_, w_ = sizes[stage - 1]
@@ -337,7 +347,7 @@ def _run_clip(model, frames, text, img_h, img_w, ar, side_arena=None, side_strea
         else:
             q = _lin(A, s, T * hw, D, w["fusion_module.multihead_attn.q.w"], w["fusion_module.multihead_attn.q.b"], D)
             att = A(T * hw, D)
-            ops.mha_core(q, fk, fv, G, NH, Tc * hw, L, D, D, D, Tc * hw * D, L * D, L * D, att, D, Tc * hw * D)
+            ops.mha_core(q, fk, fv, G, NH, Tc * hw, L, D, D, D, Tc * hw * D, L * D, L * D, att, D, Tc * hw * D, kmask=fkm)
             # src_l = s * out_proj(att), written straight into the level slice of [T, S, 256]
             gemm_ex(att, w["fusion_module.multihead_attn.out_proj.weight"], src[starts[l]:], hw, D, D, D, D, D,
                     bias=w["fusion_module.multihead_attn.out_proj.bias"], res=s, ldres=D, res_mode=RES_MUL, batch=T,
@@ -1071,7 +1081,7 @@ def _lateral(model, sc, feats, memory, vl_sites, T, L, ffn, ln_, stage, arx, G=1
     pre = bp + "multihead_attn."
     with model.arith("pixel.xattn"):
         m1 = arx.mark()
-        tk, tv, pk = vl_sites[stage]
+        tk, tv, pk, tkm = vl_sites[stage]
         Mc = (T // G) * hw  # rows of one clip
         chained = None
         if pk is not None:
@@ -1086,7 +1096,7 @@ def _lateral(model, sc, feats, memory, vl_sites, T, L, ffn, ln_, stage, arx, G=1
             gemm_ex(tgt, w[pre + "q.w"], q, hw, D, D, D, D, D, bias=w[pre + "q.b"], a2=pos, lda2=D, batch=T, sA=hw * D,
                     sA2=0, sC=hw * D)
             att = A(T * hw, D)
-            ops.mha_core(q, tk, tv, G, NH, Mc, L, D, D, D, Mc * D, L * D, L * D, att, D, Mc * D)
+            ops.mha_core(q, tk, tv, G, NH, Mc, L, D, D, D, Mc * D, L * D, L * D, att, D, Mc * D, kmask=tkm)  # tkm: ragged groups
             _proj_res_ln(att, w[pre + "out_proj.weight"], w[pre + "out_proj.bias"], tgt, T * hw, w[bp + "norm2.weight"],
                          w[bp + "norm2.bias"])
         arx.release(m1)

@@ -37,9 +37,10 @@ class TextPlan:
                               sd[p + "attention.self.value.bias"]], 0).contiguous()
             self.layers.append((wqkv, bqkv, p))
 
-    def forward(self, ids, A):
+    def forward(self, ids, A, lens=None):
         """ids int64 [G, L] on the GPU (G captions of equal length: one per clip of a clip group; G = 1 for a single clip);
-        A = arena allocator.  Returns (last_hidden_state [G*L, C] caption-major, pooler_output [C] for G = 1, [G, C] otherwise);
+        A = arena allocator.  lens: int32 [G] on the GPU (ragged clip groups: the captions are right-padded to L and caption g's
+        keys are its first lens[g] tokens, HF's attention_mask; every row, pad rows included, is computed -- ops.caption_lens).  Returns (last_hidden_state [G*L, C] caption-major, pooler_output [C] for G = 1, [G, C] otherwise);
         the two live in ONE [G*L + G, C] buffer, so the resizer takes them as one tensor (pipeline.text_stage).
         (The few-row kernel of csrc/fewrow.hip was tried for the dense layers and is slower at K = 768 / 3072 than the
         split-K GEMM: 12.7 vs 9.8 us, profiles/r03_fewrow.txt.)"""
@@ -71,8 +72,7 @@ class TextPlan:
             ws_b = A(max(t_out * L * C, t_f2 * L * C))             # out-proj planes / fc2 planes
             for wqkv, bqkv, p in self.layers:
                 ops.thin_partials(x, wqkv, ws_a, L, 3 * C, C)
-                check(lib().tce_mha_small64_seqs_f32(ws_a.data_ptr(), t_qkv, bqkv.data_ptr(), att.data_ptr(), G, Ls, self.heads, 0.125, s),
-                      "tce_mha_small64_seqs_f32")
+                self._attend(ws_a, t_qkv, bqkv, att, G, Ls, lens, s)
                 ops.thin_partials(att, sd[p + "attention.output.dense.weight"], ws_b, L, C, C)
                 ops.splitk_reduce(ws_b, t_out, L, C, x, bias=sd[p + "attention.output.dense.bias"], res=x, ldres=C, res_mode=RES_ADD,
                                   ln=(sd[p + "attention.output.LayerNorm.weight"], sd[p + "attention.output.LayerNorm.bias"]), eps=self.eps)
@@ -86,7 +86,9 @@ class TextPlan:
         ws = A(max(sk_qkv * L * 3 * C, sk_out * L * C, sk_f1 * L * self.ff, sk_f2 * L * C))
         for wqkv, bqkv, p in self.layers:
             gemm_ex(x, wqkv, qkv, L, 3 * C, C, C, C, 3 * C, bias=bqkv, splitk=sk_qkv, ws=ws)
-            if G == 1:
+            if lens is not None:
+                self._attend(qkv, 1, None, att, G, Ls, lens, s)
+            elif G == 1:
                 check(lib().tce_mha_small64_f32(qkv.data_ptr(), att.data_ptr(), L, self.heads, 0.125, s), "tce_mha_small64_f32")
             else:
                 check(lib().tce_mha_small64_seqs_f32(qkv.data_ptr(), 1, None, att.data_ptr(), G, Ls, self.heads, 0.125, s),
@@ -101,6 +103,16 @@ class TextPlan:
                     bias=sd[p + "output.dense.bias"], res=x, ldres=C, res_mode=RES_ADD, splitk=sk_f2, ws=ws, ln_eps=self.eps,
                     ln=(sd[p + "output.LayerNorm.weight"], sd[p + "output.LayerNorm.bias"]))
         return self._pooler(x, xbuf, G, Ls, s)
+
+    def _attend(self, planes, splits, bias, att, G, Ls, lens, s):
+        """self-attention inside each caption over `splits` partial qkv planes (+ bias): keys up to lens[g] when given"""
+        bp = bias.data_ptr() if bias is not None else None
+        if lens is not None:
+            check(lib().tce_mha_small64_lens_f32(planes.data_ptr(), splits, bp, att.data_ptr(), G, Ls, self.heads, 0.125, lens.data_ptr(), s),
+                  "tce_mha_small64_lens_f32")
+        else:
+            check(lib().tce_mha_small64_seqs_f32(planes.data_ptr(), splits, bp, att.data_ptr(), G, Ls, self.heads, 0.125, s),
+                  "tce_mha_small64_seqs_f32")
 
     def _pooler(self, x, xbuf, G, Ls, s):
         """pooler_output = tanh(dense(first token of each caption)) -> rows G*Ls .. of xbuf"""

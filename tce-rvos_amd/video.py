@@ -66,30 +66,46 @@ def _collect(out, origin_hw, threshold, acc):
     acc["pred_boxes"].append(out["pred_boxes"][0][ar, idx])
 
 
+def plan_expression_groups(lengths, max_group: int = 4, mixed_lengths: bool = False):
+    """The forwards of run_video_expressions: lists of expression indices, one list per forward_group call (per chunk).
+    mixed_lengths=False: expressions of one token length are grouped, `max_group` at a time (buckets in order of first sighting).
+    mixed_lengths=True: in input order, `max_group` at a time, whatever their lengths (forward_group(..., ragged=True))."""
+    mg = max(1, int(max_group))
+    if mixed_lengths:
+        idx = list(range(len(lengths)))
+        return [idx[g0:g0 + mg] for g0 in range(0, len(idx), mg)]
+    buckets = {}
+    for i, n in enumerate(lengths):
+        buckets.setdefault(int(n), []).append(i)
+    return [members[g0:g0 + mg] for members in buckets.values() for g0 in range(0, len(members), mg)]
+
+
 @torch.no_grad()
 def run_video_expressions(model, frames: torch.Tensor, captions, origin_hw, clip_size: Optional[int] = 32,
-                          threshold: float = 0.5, max_group: int = 4):
+                          threshold: float = 0.5, max_group: int = 4, mixed_lengths: bool = False):
     """Every expression of ONE video.  frames as in run_video; captions: list of str (or of LongTensor [1,L]).  Returns a list with
-    one run_video-style dict per caption, in order.  Captions of equal token length are grouped (at most `max_group` per forward)."""
+    one run_video-style dict per caption, in order.  Captions of equal token length are grouped (at most `max_group` per forward);
+    mixed_lengths=True groups them in input order whatever their lengths, right-padded to the group's longest
+    (forward_group(..., ragged=True): fewer forwards per chunk, the pad rows cost some text work)."""
     if frames.dim() != 4 or frames.shape[1] != 3 or frames.shape[0] == 0:
         raise ValueError("run_video_expressions: frames must be a non-empty [N,3,H,W]")
     n = frames.shape[0]
     H, W = int(frames.shape[-2]), int(frames.shape[-1])
     target = [{"size": torch.tensor([H, W])}]
     ids = [c if torch.is_tensor(c) else model._tokenise([c], frames.device)[0] for c in captions]
-    buckets = {}
-    for i, t in enumerate(ids):
-        buckets.setdefault(int(t.shape[1]), []).append(i)
     step = n if not clip_size else int(clip_size)
     accs = [{"masks": [], "best_query": [], "pred_logits": [], "pred_boxes": []} for _ in captions]
-    for members in buckets.values():
-        for g0 in range(0, len(members), max(1, int(max_group))):
-            grp = members[g0:g0 + max(1, int(max_group))]
+    for grp in plan_expression_groups([int(t.shape[1]) for t in ids], max_group, mixed_lengths):
+        if mixed_lengths:  # right-padded on the host (validated there), lengths derived again on the device
+            from .model import pad_captions
+            tok = pad_captions([ids[i] for i in grp], model._pad_id())[0].to(frames.device)
+        else:
             tok = torch.cat([ids[i].to(frames.device) for i in grp], 0)
-            for lo in range(0, n, step):
-                clip = frames[lo:lo + step]
-                outs = model.forward_group([clip] * len(grp), tok, target)  # one tensor, len(grp) captions: shared backbone
-                for i, out in zip(grp, outs):
-                    _collect(out, origin_hw, threshold, accs[i])
+        for lo in range(0, n, step):
+            clip = frames[lo:lo + step]
+            # one tensor, len(grp) captions: shared backbone
+            outs = model.forward_group([clip] * len(grp), tok, target, **({"ragged": True} if mixed_lengths else {}))
+            for i, out in zip(grp, outs):
+                _collect(out, origin_hw, threshold, accs[i])
     ops.check_range(frames.device)
     return [{k: torch.cat(v, 0) for k, v in a.items()} for a in accs]
