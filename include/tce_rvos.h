@@ -408,6 +408,16 @@ int64_t tce_conv3x3_packed_bytes(int32_t Cin, int32_t N);
 int tce_conv3x3_pack_f32(const float* w, void* packed, int32_t Cin, int32_t N, tceStream stream);
 int tce_conv3x3_f32(const float* x, int64_t ldx, const void* packed, const float* bias, float* out, int64_t ldo, int32_t T,
                     int32_t H, int32_t W, int32_t Cin, int32_t N, tceStream stream);
+/* The same convolution with a launch that fills less than one round of workgroups split over the K walk: `pieces` workgroups per
+ * 128-pixel block, each a contiguous run of the 144 k-steps (piece s starts at k-step tce_conv3x3_split_kstep(pieces, s)), fp32
+ * partial sums into ws, then one reduce pass adds them in piece order and the bias (deterministic).  ws: 16-byte aligned, at least
+ * tce_conv3x3_split_ws_floats(M = T*H*W) floats, private to this launch while it runs; unused when that size is 0 (nothing is split:
+ * the launches are those of tce_conv3x3_f32). */
+int64_t tce_conv3x3_split_ws_floats(int32_t M, int32_t Cin, int32_t N);
+int32_t tce_conv3x3_split_pieces(int32_t M, int32_t Cin, int32_t N);
+int32_t tce_conv3x3_split_kstep(int32_t pieces, int32_t s);
+int tce_conv3x3_split_f32(const float* x, int64_t ldx, const void* packed, const float* bias, float* out, int64_t ldo, int32_t T,
+                          int32_t H, int32_t W, int32_t Cin, int32_t N, float* ws, int64_t ws_floats, tceStream stream);
 
 /* Cross-attention of a token tensor against a SHORT key sequence as ONE token-stationary launch (csrc/chain.hip):
  *     out = LN?( res (+|*) ( MHA(q = x + a2, k, v) W_o^T + b_o ) )          8 heads x 32 channels, `group` key slots

@@ -31,6 +31,9 @@ int tce_debug_msda_set_fewq(int32_t on);
 /* tuning aid: 0 (default) = tce_conv3x3_f32 picks 128- or 256-pixel workgroups by the rounds of 256 workgroups each form needs;
  * 4 / 8 = always the 4-wave (128-pixel) / 8-wave (256-pixel) form (A/B timing and parity) */
 int tce_debug_conv3x3_set_waves(int32_t waves);
+/* tuning aid: 0 (default) = tce_conv3x3_split_f32 picks the piece count by its cost model; 1..12 = that many pieces for every split
+ * launch (1 = no split; A/B timing) -- tce_conv3x3_split_ws_floats follows it */
+int tce_debug_conv3x3_set_pieces(int32_t pieces);
 #ifdef __cplusplus
 }
 #endif

@@ -137,6 +137,10 @@ SIGNATURES = {
     "tce_conv3x3_packed_bytes": (i64, [i32, i32]),
     "tce_conv3x3_pack_f32": (i32, [c_f, c_f, i32, i32, c_f]),
     "tce_conv3x3_f32": (i32, [c_f, i64, c_f, c_f, c_f, i64, i32, i32, i32, i32, i32, c_f]),
+    "tce_conv3x3_split_ws_floats": (i64, [i32, i32, i32]),
+    "tce_conv3x3_split_pieces": (i32, [i32, i32, i32]),
+    "tce_conv3x3_split_kstep": (i32, [i32, i32]),
+    "tce_conv3x3_split_f32": (i32, [c_f, i64, c_f, c_f, c_f, i64, i32, i32, i32, i32, i32, c_f, i64, c_f]),
     "tce_fewrow_linear_f32": (i32, [C.POINTER(FewRowArgs), c_f]),
     "tce_thin_linear_splits": (i32, [i32, i32, i32]),
     "tce_thin_partials_f32": (i32, [c_f, i64, i32, c_f, i32, c_f, i64, c_f, i32, i32, i32, c_f]),
@@ -164,6 +168,7 @@ DEBUG_SIGNATURES = {
     "tce_debug_mha_set_split": (i32, [i32]),
     "tce_debug_msda_set_fewq": (i32, [i32]),
     "tce_debug_conv3x3_set_waves": (i32, [i32]),
+    "tce_debug_conv3x3_set_pieces": (i32, [i32]),
 }
 
 _LIB = None

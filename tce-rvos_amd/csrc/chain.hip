@@ -1031,13 +1031,32 @@ inline long long ffn_units(int C, int Hd) { return (long long)(Hd / 32 + 2) * ff
 // (2 -> 3) 138 -> 121 us, 40800 rows (2 -> 3) 288 -> 251 us and config 3's clip 9.82 -> 9.60 ms, but 24100 rows (3 -> 4) only
 // 169 -> 163 us and config 2's clip 6.08 -> 6.23 ms with it (the 67 CUs the un-split launch leaves idle are where the clip's
 // parallel branches run).  Hence the margin: the 2 -> 3 and 1 -> 2 plans pass it, 3 -> 4 does not.
+// Compute units of the current device, read once per device; 256 (MI355X) when there is no device (CPU-side planning).
+inline int tce_cu_count() {
+  static int cache[64] = {0};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) {
+    (void)hipGetLastError();
+    return 256;
+  }
+  if (!cache[dev]) {
+    int n = 0;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) {
+      (void)hipGetLastError();
+      n = 256;
+    }
+    cache[dev] = n;
+  }
+  return cache[dev];
+}
+
 struct FfnSplitPlan {
   int p = 0, k[2] = {0, 0}, nblk = 0;
   long long ws_floats = 0;
 };
 inline FfnSplitPlan ffn_split_plan(int M, int C, int Hd, int batch) {
   FfnSplitPlan best;
-  const int B = tce_cdiv(M, 32 * ffn_waves(C)), NC = Hd / 32, CUS = 256;
+  const int B = tce_cdiv(M, 32 * ffn_waves(C)), NC = Hd / 32, CUS = tce_cu_count();
   if (C != 256 || NC < 24 || batch < 1) return best;
   const int OVP = 3, OVF = 4;  // per piece: x load + split + partial store; per finished block: partial read + epilogue
   auto rounds = [&](long long wgs) { return (double)((wgs + CUS - 1) / CUS); };
@@ -1083,10 +1102,10 @@ void ffn_launch(const FfnArgs& a, int act, hipStream_t s, int batch = 1) {
     // 256 half workgroups runs one wave per SIMD and costs half a round.  Ties go to the half form (tools/ffn_bench.py: 72000 x 96
     // 92.7 -> 67.4 us, where it saves half a round; 122880 x 96 93.9 -> 88.8, 256800 x 128 279 -> 265, 36000 x 96 42.1 -> 42.3 us
     // at equal round counts)
-    const long long b8 = (long long)tce_cdiv(a.M, 256) * batch, b4 = (long long)tce_cdiv(a.M, 128) * batch;
-    const double c8 = (double)((b8 + 255) / 256);
-    const long long rem = b4 % 512;
-    const double c4 = (double)(b4 / 512) + (rem == 0 ? 0.0 : rem <= 256 ? 0.5 : 1.0);
+    const long long b8 = (long long)tce_cdiv(a.M, 256) * batch, b4 = (long long)tce_cdiv(a.M, 128) * batch, cus = tce_cu_count();
+    const double c8 = (double)((b8 + cus - 1) / cus);
+    const long long rem = b4 % (2 * cus);
+    const double c4 = (double)(b4 / (2 * cus)) + (rem == 0 ? 0.0 : rem <= cus ? 0.5 : 1.0);
     if (act == 2 && g_ffn_half >= 0 && (g_ffn_half > 0 || c4 <= c8)) {
       const dim3 grid(tce_cdiv(a.M, 128), batch), block(256);
       if (a.single) hipLaunchKernelGGL((ffn_fused_kernel<C, 4, 2, true>), grid, block, 0, s, a);
@@ -1280,7 +1299,17 @@ struct ConvArgs {
   int* range_flag;
   int single;
   int m_off;  // first pixel of this launch (a launch may cover a row range [m_off, ...) of the map: the mixed form below)
+  // split form only: workgroup = (piece, block) piece-major over nb blocks; piece s walks iterations conv3x3_piece_iter(pieces, s) ..
+  // conv3x3_piece_iter(pieces, s+1) and stores its fp32 partial sums (no bias) to ws + s * (M - m_off) * 256, rows m - m_off
+  int nb, pieces;
+  float* ws;
 };
+
+// The K walk is 3 * CIN/64 iterations of 12 k-steps (vertical tap, group of 4 channel chunks); a split piece is a contiguous run of whole
+// iterations (the unrolled body and its compile-time ring positions stay as they are).  Piece s of p starts at iteration s * ITERS / p:
+// the p pieces cover every iteration exactly once (tce_conv3x3_split_kstep exports it for the CPU test).
+constexpr int CONV_ITERS = 12;  // CIN = 256
+__host__ __device__ constexpr int conv3x3_piece_iter(const int pieces, const int s) { return s * CONV_ITERS / pieces; }
 
 // Ablation builds (tools/conv3_ablate.py, -DCONV_ABL=n; results are then wrong): bit 0: one workgroup per CU; bit 1: no
 // barrier inside the loop; bit 2: no MFMA (fragments kept live); bit 3: no weight DMA inside the loop; bit 4: no operand
@@ -1305,7 +1334,8 @@ __device__ __forceinline__ void static_for(F&& f) {
 // WAVES = 8 (round 5, A/B): 256 pixels per workgroup, two waves per SIMD sharing ONE weight ring -- half the weight bytes per pixel
 // through L2 -> CU, which is what bounds the kernel; each wave then moves 2 of a stage's 16 pieces and keeps shorter register rings
 // (XS 4, NW 3) to stay inside 256 registers.
-template <int CIN, bool SINGLE, int WAVES = 4>
+// SPLIT: one piece of the K walk per workgroup (see ConvArgs); partial sums out, conv3x3_reduce_kernel adds them and the bias.
+template <int CIN, bool SINGLE, int WAVES = 4, bool SPLIT = false>
 __global__ void __launch_bounds__(64 * WAVES, WAVES / 4) conv3x3_kernel(const ConvArgs p) {
   constexpr int NTL = 8;
   constexpr int PW = 16 / WAVES;          // weight pieces a wave moves per stage
@@ -1321,12 +1351,17 @@ __global__ void __launch_bounds__(64 * WAVES, WAVES / 4) conv3x3_kernel(const Co
   static_assert(CIN % 64 == 0, "channel chunks come in groups of four");
   static_assert(BODY % R == 0 && BODY % XS == 0 && BODY % NW == 0 && LX >= LW, "ring positions are compile-time");
   static_assert(WAVES * WT_BYTES <= R * STAGE, "the epilogue's staging tiles alias the ring");
+  static_assert(!SPLIT || (ITERS == CONV_ITERS && WAVES == 4 && !SINGLE), "split pieces: CIN = 256, 128-pixel workgroups, split fp16");
   __shared__ __attribute__((aligned(16))) unsigned char smem[R * STAGE];
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int hf = lane >> 5;
-  const int m0 = p.m_off + blockIdx.x * (32 * WAVES) + wave * 32;
+  const int blk = SPLIT ? (int)blockIdx.x % p.nb : (int)blockIdx.x;
+  const int piece = SPLIT ? (int)blockIdx.x / p.nb : 0;
+  const int i0 = SPLIT ? conv3x3_piece_iter(p.pieces, piece) : 0;  // iterations [i0, i1) of the K walk
+  const int i1 = SPLIT ? conv3x3_piece_iter(p.pieces, piece + 1) : ITERS;
+  const int m0 = p.m_off + blk * (32 * WAVES) + wave * 32;
 
   // this lane's pixel; per (vertical tap, chunk group) the addresses of its three horizontal neighbours' channels, or
   // of the zero block behind the weights for taps outside the image
@@ -1336,7 +1371,7 @@ __global__ void __launch_bounds__(64 * WAVES, WAVES / 4) conv3x3_kernel(const Co
   const float* const xme = p.x + (long long)min(m, p.M - 1) * p.ldx + 8 * hf;
   auto iter_ptrs = [&](const int it, const float* (&q)[3]) {
     const int dy = it / (CIN / 64) - 1, cq = it % (CIN / 64);
-    const bool row_ok = it < ITERS && m < p.M && (unsigned)(py + dy) < (unsigned)p.H;
+    const bool row_ok = it < i1 && m < p.M && (unsigned)(py + dy) < (unsigned)p.H;
 #pragma unroll
     for (int d = 0; d < 3; ++d) {
       const bool ok = row_ok && (unsigned)(px + d - 1) < (unsigned)p.W;
@@ -1346,7 +1381,7 @@ __global__ void __launch_bounds__(64 * WAVES, WAVES / 4) conv3x3_kernel(const Co
 
   // weights: this wave moves pieces PW*wave .. PW*wave+PW-1 of every stage (one float4 per lane and piece) through
   // registers into the ring
-  const float* wp = reinterpret_cast<const float*>(p.wpk + (long long)(PW * wave) * PIECE + lane * 16);
+  const float* wp = reinterpret_cast<const float*>(p.wpk + ((long long)i0 * BODY * STAGE) + (long long)(PW * wave) * PIECE + lane * 16);
   unsigned char* const wdst = smem + (PW * wave) * PIECE + lane * 16;
   f32x4 wr[NW][PW];
   auto wload = [&](f32x4 (&dst)[PW]) {
@@ -1368,8 +1403,8 @@ __global__ void __launch_bounds__(64 * WAVES, WAVES / 4) conv3x3_kernel(const Co
   f32x4 xr[XS][2];
   const float* cur[3];
   const float* nxt[3];
-  iter_ptrs(0, cur);
-  iter_ptrs(1, nxt);
+  iter_ptrs(i0, cur);
+  iter_ptrs(i0 + 1, nxt);
   // operand of body step JJ (>= BODY: of the next iteration) -> ring slot
   auto xload = [&](auto jjc, f32x4 (&dst)[2]) {
     constexpr int JJ = decltype(jjc)::value;
@@ -1426,7 +1461,7 @@ __global__ void __launch_bounds__(64 * WAVES, WAVES / 4) conv3x3_kernel(const Co
     fl[1] = *reinterpret_cast<const h16x8*>(st + 3 * PIECE);
   }
 
-  for (int it = 0; it < ITERS; ++it) {
+  for (int it = i0; it < i1; ++it) {
     static_for<0, BODY>([&](auto jc) {
       constexpr int j = decltype(jc)::value;
       constexpr int nslot = (j + 1) % XS;  // operand of the next step: split under this step's first four tiles
@@ -1498,6 +1533,12 @@ __global__ void __launch_bounds__(64 * WAVES, WAVES / 4) conv3x3_kernel(const Co
 
   float* const wt = reinterpret_cast<float*>(smem + wave * WT_BYTES);
   tce_amax_t amax = 0;
+  if constexpr (SPLIT) {  // partial sums; the range guard runs on the reduced output
+    float* const part = p.ws + (long long)piece * (p.M - p.m_off) * 256;
+#pragma unroll
+    for (int t = 0; t < NTL; ++t) tile_store(acc[t], part, 256, m0 - p.m_off, p.M - p.m_off, 32 * t, wt, lane, amax);
+    return;
+  }
   const ResTile none = {};
 #pragma unroll
   for (int t = 0; t < NTL; ++t) {
@@ -1505,6 +1546,25 @@ __global__ void __launch_bounds__(64 * WAVES, WAVES / 4) conv3x3_kernel(const Co
     tile_store(acc[t], p.out, p.ldo, m0, p.M, 32 * t, wt, lane, amax);
   }
   tce_range_report(p.range_flag, amax);
+}
+
+// out[m_off + r][c] = bias[c] + part_0[r][c] + part_1[r][c] + ... in piece order (deterministic whatever order the pieces ran in);
+// r < rows = M - m_off, one float4 per thread and step
+__global__ void __launch_bounds__(256) conv3x3_reduce_kernel(const float* __restrict__ ws, const int pieces, const int rows,
+                                                             const float* __restrict__ bias, float* __restrict__ out,
+                                                             const long long ldo, const int m_off, int* range_flag) {
+  const long long n4 = (long long)rows * 64, stride = (long long)gridDim.x * 256;
+  tce_amax_t amax = 0;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
+    const f32x4* src = reinterpret_cast<const f32x4*>(ws) + i;
+    f32x4 v = src[0];
+    for (int s = 1; s < pieces; ++s) v += src[(long long)s * n4];
+    const int c4 = (int)(i & 63);
+    if (bias) v += reinterpret_cast<const f32x4*>(bias)[c4];
+    amax = tce_amax4(amax, v);
+    *reinterpret_cast<f32x4*>(out + (m_off + (i >> 6)) * ldo + 4 * c4) = v;
+  }
+  tce_range_report(range_flag, amax);
 }
 
 // w [256, 9*CIN] (k = tap*CIN + c) -> 9*CIN/16 + 4 stages of 16 pieces in the kernel's K order: stage s = 12*it + j is
@@ -1961,44 +2021,134 @@ extern "C" int tce_debug_conv3x3_set_waves(int32_t waves) {
   return TCE_OK;
 }
 
-extern "C" int tce_conv3x3_f32(const float* x, int64_t ldx, const void* packed, const float* bias, float* out, int64_t ldo,
-                               int32_t T, int32_t H, int32_t W, int32_t Cin, int32_t N, tceStream stream) {
-  TCE_CHECK_ARG(conv3x3_shape_ok(Cin, N), "tce_conv3x3_f32: unsupported shape Cin=%d N=%d (256 -> 256)", Cin, N);
+// Launch plan of the 3x3 convolution (pure: tce_conv3x3_split_ws_floats / _pieces export it).  Forms, in units of a narrow round x 4:
+// 256-pixel (8-wave) workgroups halve the weight bytes per pixel; a round of them takes 1.75 x a round of 128-pixel workgroups
+// (measured, tools/conv3_bench.py: 128400 px 508 -> 444 us, 72000 px 333 -> 337, 18000 px 100 -> 142): taken when the rounds of
+// 256 workgroups that way cost less -- config 5 and clip groups, not the single config-2 clip.  Mixed form (round 5): full rounds of
+// 256-pixel workgroups, then the REMAINDER as 128-pixel workgroups (they run one wave per SIMD: a round of them costs 1 against 1.75).
+// 72000 px: 256 wide workgroups + 51 narrow ones = 1.75 + 1 rounds against 3 narrow rounds (or 2 x 1.75 wide ones).
+// Split (round 6, tce_conv3x3_split_f32 only): a narrow launch that fills less than one round -- the mixed form's remainder, or a
+// single sub-round launch such as 18000 px -- walks the same 144 k-steps per workgroup whatever its size, so it is issued as `pieces`
+// workgroups per block, each a contiguous run of the K walk (conv3x3_piece_iter), and a reduce pass adds the fp32 partials and the bias.
+struct Conv3Plan {
+  int wide = 4;          // form of the un-split part: 8 = 256-pixel workgroups, 4 = 128-pixel ones
+  int full8 = 0;         // mixed form: workgroups of the wide launch over pixels [0, 65536 * full8 / 256)
+  int m_narrow = 0;      // first pixel of the narrow launch (mixed form), else 0
+  int nb = 0;            // 128-pixel blocks of the narrow launch
+  int pieces = 1;        // > 1: the narrow launch is split
+  long long ws_floats = 0;
+};
+inline Conv3Plan conv3x3_plan(const int M, const int cus, const int single, const int force_waves, const int split, const int force_pieces) {
+  Conv3Plan pl;
+  const int r4 = tce_cdiv(tce_cdiv(M, 128), cus), r8 = tce_cdiv(tce_cdiv(M, 256), cus);
+  const int full8 = tce_cdiv(M, 256) / cus;  // complete rounds of wide workgroups
+  const int rem_px = M - full8 * 256 * cus;
+  const int mixed4 = 7 * full8 + 4 * tce_cdiv(tce_cdiv(rem_px, 128), cus);
+  if (!force_waves && !single && full8 >= 1 && rem_px > 0 && mixed4 < 4 * r4 && mixed4 < 7 * r8) {
+    pl.full8 = full8 * cus;
+    pl.m_narrow = full8 * 256 * cus;
+  } else {
+    pl.wide = force_waves ? force_waves : (4 * r4 > 7 * r8 ? 8 : 4);
+    if (single) pl.wide = 4;
+    if (pl.wide == 8) return pl;
+  }
+  pl.nb = tce_cdiv(M - pl.m_narrow, 128);
+  if (!split || single || pl.nb >= cus) return pl;
+  // cost in iterations of one workgroup's walk (12 for an un-split block): rounds x (longest piece + OVH), plus the reduce pass --
+  // its fp32 traffic ((pieces + 1) x 1 KiB per pixel) at RED_BPI bytes per iteration-time, and LAUNCH for the extra launch.
+  // Pieces are capped at two rounds of workgroups (this bounds the workspace: tce_conv3x3_split_ws_floats).
+  const double OVH = 0.5, LAUNCH = 0.3, RED_BPI = 8.0 * (3u << 20);  // ~3.3 TB/s over one iteration (~7.5 us)
+  const long long px = M - pl.m_narrow;
+  auto cost = [&](int p) {
+    const double walk = (double)tce_cdiv((long long)pl.nb * p, cus) * (tce_cdiv(CONV_ITERS, p) + OVH);
+    return p == 1 ? walk : walk + LAUNCH + (double)(p + 1) * px * 1024.0 / RED_BPI;
+  };
+  int best = 1;
+  for (int p = 2; p <= 6; ++p)
+    if ((long long)pl.nb * p <= 2ll * cus && cost(p) < cost(best)) best = p;
+  if (force_pieces > 0) best = force_pieces;
+  if (best > 1) {
+    pl.pieces = best;
+    pl.ws_floats = (long long)best * px * 256;
+  }
+  return pl;
+}
+
+static int g_conv3_pieces = 0;
+extern "C" int tce_debug_conv3x3_set_pieces(int32_t pieces) {
+  TCE_CHECK_ARG(pieces >= 0 && pieces <= CONV_ITERS, "tce_debug_conv3x3_set_pieces: 0 (automatic) .. 12");
+  g_conv3_pieces = pieces;
+  return TCE_OK;
+}
+
+static int conv3_force_waves() {
+  static const int env_force = []() { const char* e = getenv("TCE_CONV3_WAVES"); return e ? atoi(e) : 0; }();
+  return g_conv3_waves ? g_conv3_waves : env_force;
+}
+
+static Conv3Plan conv3x3_plan_for(const int M, const bool split) {
+  return conv3x3_plan(M, tce_cu_count(), tce_gemm_single_pass(), conv3_force_waves(), split, g_conv3_pieces);
+}
+
+// Workspace of tce_conv3x3_split_f32 (floats; 0 = that call splits nothing and needs none) and its piece count.
+extern "C" int64_t tce_conv3x3_split_ws_floats(int32_t M, int32_t Cin, int32_t N) {
+  return conv3x3_shape_ok(Cin, N) && M > 0 ? conv3x3_plan_for(M, true).ws_floats : 0;
+}
+extern "C" int32_t tce_conv3x3_split_pieces(int32_t M, int32_t Cin, int32_t N) {
+  return conv3x3_shape_ok(Cin, N) && M > 0 ? conv3x3_plan_for(M, true).pieces : 0;
+}
+// First k-step of piece s of `pieces` (s = pieces: the end of the walk, 9 * 256 / 16 = 144).
+extern "C" int32_t tce_conv3x3_split_kstep(int32_t pieces, int32_t s) {
+  return pieces >= 1 && pieces <= CONV_ITERS && s >= 0 && s <= pieces ? 12 * conv3x3_piece_iter(pieces, s) : -1;
+}
+
+static int conv3x3_launch(const float* x, int64_t ldx, const void* packed, const float* bias, float* out, int64_t ldo, int32_t T,
+                          int32_t H, int32_t W, int32_t Cin, int32_t N, float* ws, int64_t ws_floats, const bool split, tceStream stream,
+                          const char* name) {
+  TCE_CHECK_ARG(conv3x3_shape_ok(Cin, N), "%s: unsupported shape Cin=%d N=%d (256 -> 256)", name, Cin, N);
   TCE_CHECK_ARG(x && packed && out && T > 0 && H > 0 && W > 0 && (long long)T * H * W < (1ll << 31),
-                "tce_conv3x3_f32: null pointer or bad sizes");
-  TCE_CHECK_ARG(ldx >= Cin && ldx % 4 == 0 && ldo >= N && ldo % 4 == 0, "tce_conv3x3_f32: bad row pitch");
+                "%s: null pointer or bad sizes", name);
+  TCE_CHECK_ARG(ldx >= Cin && ldx % 4 == 0 && ldo >= N && ldo % 4 == 0, "%s: bad row pitch", name);
   TCE_CHECK_ARG(tce_aligned16(x) && tce_aligned16(out) && tce_aligned16(packed) && (!bias || tce_aligned16(bias)),
-                "tce_conv3x3_f32: pointers must be 16-byte aligned");
+                "%s: pointers must be 16-byte aligned", name);
   ConvArgs a;
   a.x = x; a.wpk = (const unsigned char*)packed; a.bias = bias; a.out = out;
   a.ldx = ldx; a.ldo = ldo; a.H = H; a.W = W; a.M = T * H * W;
   a.range_flag = tce_range_flag(); a.single = tce_gemm_single_pass();
-  // 256-pixel (8-wave) workgroups halve the weight bytes per pixel; a round of them takes 1.75 x a round of 128-pixel workgroups
-  // (measured, tools/conv3_bench.py: 128400 px 508 -> 444 us, 72000 px 333 -> 337, 18000 px 100 -> 142): taken when the rounds of
-  // 256 workgroups that way cost less -- config 5 and clip groups, not the single config-2 clip.  TCE_CONV3_WAVES=4|8 / tce_debug_conv3x3_set_waves force one.
-  static const int env_force = []() { const char* e = getenv("TCE_CONV3_WAVES"); return e ? atoi(e) : 0; }();
-  const int force = g_conv3_waves ? g_conv3_waves : env_force;
-  const int r4 = tce_cdiv(tce_cdiv(a.M, 128), 256), r8 = tce_cdiv(tce_cdiv(a.M, 256), 256);
-  a.m_off = 0;
-  // Mixed form (round 5): full rounds of 256-pixel workgroups, then the REMAINDER as 128-pixel workgroups (they run one wave per
-  // SIMD: a round of them costs 1 against 1.75).  72000 px: 256 wide workgroups + 51 narrow ones = 1.75 + 1 rounds against 3 narrow
-  // rounds (or 2 x 1.75 wide ones).  In units of a narrow round x 4:
-  const int full8 = tce_cdiv(a.M, 256) / 256;                       // complete rounds of wide workgroups
-  const int rem_px = a.M - full8 * 256 * 256;
-  const int mixed4 = 7 * full8 + 4 * tce_cdiv(tce_cdiv(rem_px, 128), 256);
-  if (!force && !a.single && full8 >= 1 && rem_px > 0 && mixed4 < 4 * r4 && mixed4 < 7 * r8) {
-    hipLaunchKernelGGL((conv3x3_kernel<256, false, 8>), dim3(full8 * 256), dim3(512), 0, (hipStream_t)stream, a);
-    a.m_off = full8 * 256 * 256;
-    hipLaunchKernelGGL((conv3x3_kernel<256, false>), dim3(tce_cdiv(rem_px, 128)), dim3(256), 0, (hipStream_t)stream, a);
-    TCE_CHECK_LAUNCH("tce_conv3x3_f32(mixed)");
-    return TCE_OK;
+  a.m_off = 0; a.nb = 0; a.pieces = 1; a.ws = nullptr;
+  hipStream_t s = (hipStream_t)stream;
+  const Conv3Plan pl = conv3x3_plan_for(a.M, split);
+  if (pl.pieces > 1)
+    TCE_CHECK_ARG(ws && tce_aligned16(ws) && ws_floats >= pl.ws_floats,
+                  "%s: workspace of %lld floats needed (tce_conv3x3_split_ws_floats), %lld given", name, pl.ws_floats, (long long)ws_floats);
+  if (pl.full8) hipLaunchKernelGGL((conv3x3_kernel<256, false, 8>), dim3(pl.full8), dim3(512), 0, s, a);
+  a.m_off = pl.m_narrow;
+  if (pl.wide == 8) hipLaunchKernelGGL((conv3x3_kernel<256, false, 8>), dim3(tce_cdiv(a.M, 256)), dim3(512), 0, s, a);
+  else if (a.single) hipLaunchKernelGGL((conv3x3_kernel<256, true>), dim3(pl.nb), dim3(256), 0, s, a);
+  else if (pl.pieces == 1) hipLaunchKernelGGL((conv3x3_kernel<256, false>), dim3(pl.nb), dim3(256), 0, s, a);
+  else {
+    a.nb = pl.nb; a.pieces = pl.pieces; a.ws = ws;
+    hipLaunchKernelGGL((conv3x3_kernel<256, false, 4, true>), dim3(pl.nb * pl.pieces), dim3(256), 0, s, a);
+    const int rows = a.M - a.m_off;
+    hipLaunchKernelGGL(conv3x3_reduce_kernel, dim3(std::min(tce_cdiv((long long)rows * 64, 256), 8 * tce_cu_count())), dim3(256), 0, s,
+                       (const float*)ws, pl.pieces, rows, bias, out, ldo, a.m_off, a.range_flag);
   }
-  const int wide = force ? force : (4 * r4 > 7 * r8 ? 8 : 4);
-  if (wide == 8 && !a.single) hipLaunchKernelGGL((conv3x3_kernel<256, false, 8>), dim3(tce_cdiv(a.M, 256)), dim3(512), 0, (hipStream_t)stream, a);
-  else if (a.single) hipLaunchKernelGGL((conv3x3_kernel<256, true>), dim3(tce_cdiv(a.M, 128)), dim3(256), 0, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL((conv3x3_kernel<256, false>), dim3(tce_cdiv(a.M, 128)), dim3(256), 0, (hipStream_t)stream, a);
-  TCE_CHECK_LAUNCH("tce_conv3x3_f32");
+  TCE_CHECK_LAUNCH(name);
   return TCE_OK;
+}
+
+// TCE_CONV3_WAVES=4|8 / tce_debug_conv3x3_set_waves force one form.
+extern "C" int tce_conv3x3_f32(const float* x, int64_t ldx, const void* packed, const float* bias, float* out, int64_t ldo,
+                               int32_t T, int32_t H, int32_t W, int32_t Cin, int32_t N, tceStream stream) {
+  return conv3x3_launch(x, ldx, packed, bias, out, ldo, T, H, W, Cin, N, nullptr, 0, false, stream, "tce_conv3x3_f32");
+}
+
+// As tce_conv3x3_f32, with a sub-round narrow launch split over the K walk: ws = tce_conv3x3_split_ws_floats(M) floats (16-byte
+// aligned; unused when that is 0), not shared with a launch that may run concurrently.  Bit-identical run to run.
+extern "C" int tce_conv3x3_split_f32(const float* x, int64_t ldx, const void* packed, const float* bias, float* out, int64_t ldo,
+                                     int32_t T, int32_t H, int32_t W, int32_t Cin, int32_t N, float* ws, int64_t ws_floats,
+                                     tceStream stream) {
+  return conv3x3_launch(x, ldx, packed, bias, out, ldo, T, H, W, Cin, N, ws, ws_floats, true, stream, "tce_conv3x3_split_f32");
 }
 
 // split-fp16 / fp16 modes of tce_patch_embed_f32 (norm.hip dispatches here); false = shape not covered

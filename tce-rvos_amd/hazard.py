@@ -401,6 +401,13 @@ MODELS = {
         [strided(_p(a[0]), a[9] * F, (a[6] * a[7] * a[8], a[1] * F)), dense(_p(a[2]), _lib.lib_raw().tce_conv3x3_packed_bytes(a[9], a[10])),
          dense(_p(a[3]), a[10] * F)],
         [strided(_p(a[4]), a[10] * F, (a[6] * a[7] * a[8], a[5] * F))]),
+    # x, ldx, packed, bias, out, ldo, T, H, W, Cin, N, ws, ws_floats: the pieces write the planned workspace, the reduce pass
+    # reads it back (a write covers both) and writes out
+    "tce_conv3x3_split_f32": lambda a: (
+        [strided(_p(a[0]), a[9] * F, (a[6] * a[7] * a[8], a[1] * F)), dense(_p(a[2]), _lib.lib_raw().tce_conv3x3_packed_bytes(a[9], a[10])),
+         dense(_p(a[3]), a[10] * F)],
+        [strided(_p(a[4]), a[10] * F, (a[6] * a[7] * a[8], a[5] * F)),
+         dense(_p(a[11]), _lib.lib_raw().tce_conv3x3_split_ws_floats(a[6] * a[7] * a[8], a[9], a[10]) * F)]),
     "tce_fewrow_linear_f32": lambda a: _fewrow(_st(a[0])),
     # x, ldx, xsplits, bias_x, act_x, W, ldw, ws, M, N, K
     "tce_thin_partials_f32": lambda a: (
@@ -440,7 +447,8 @@ MODELS = {
 # Entry points that launch nothing (queries, process switches, graph helpers, tuning aids): passed through.
 NOT_LAUNCHES = {"tce_abi_version", "tce_last_error", "tce_gemm_select_tile", "tce_gemm_select_tile_ex", "tce_set_gemm_mode", "tce_set_gemm_mode_thread",
                 "tce_get_gemm_mode", "tce_set_range_flag", "tce_groupnorm_nsplit", "tce_mha_ws_bytes", "tce_ffn_packed_bytes", "tce_ffn_split_ws_floats", "tce_ffn_split_counters",
-                "tce_rowlin_packed_bytes", "tce_conv3x3_packed_bytes", "tce_swin_attn_packed_bytes", "tce_thin_linear_splits", "tce_graph_begin", "tce_graph_end", "tce_graph_launch",
+                "tce_rowlin_packed_bytes", "tce_conv3x3_packed_bytes", "tce_conv3x3_split_ws_floats",
+                "tce_conv3x3_split_pieces", "tce_conv3x3_split_kstep", "tce_swin_attn_packed_bytes", "tce_thin_linear_splits", "tce_graph_begin", "tce_graph_end", "tce_graph_launch",
                 "tce_graph_destroy", "tce_graph_group"} | set(_lib.DEBUG_SIGNATURES)
 
 

@@ -591,9 +591,14 @@ class ReferFormer(nn.Module):
             self._shape_cache[key] = tp
         return tp
 
+    @staticmethod
+    def _conv3_ws_bytes(T, H0, W0, strides):
+        """The largest workspace of a split 3x3 convolution (ops.conv3x3_split_ws_floats) at the pixel decoder's maps of these strides."""
+        return 4 * max(ops.conv3x3_split_ws_floats(T * (-(-H0 // s)) * (-(-W0 // s))) for s in strides)
+
     def _arena_bytes(self, T, H0, W0):
         tok0 = T * ((H0 + 3) // 4) * ((W0 + 3) // 4)
-        return self.arena_bytes or int(tok0 * 4 * (2048 * 2.2 + 256 * 24) + (256 << 20))
+        return self.arena_bytes or int(tok0 * 4 * (2048 * 2.2 + 256 * 24) + (256 << 20) + self._conv3_ws_bytes(T, H0, W0, (4, 8)))
 
     def _get_arena(self, T, H0, W0, device, slot=0):
         """The eager path's arena of `slot` (captured graphs own a private one each: their addresses are baked in).
@@ -941,7 +946,7 @@ class ReferFormer(nn.Module):
                 # (projection, GroupNorm output, q, attention output + workspaces: 5 maps of [tokens/4, 256]) -- the form
                 # exact-fp32 mode and captions longer than 32 tokens take
                 ops.Arena(like.device, max(int(tok0 / 64 * 4 * (2048 + 256 * 12)) + int(tok0 / 16 * 4 * 256 * 8),
-                                           int(tok0 / 4 * 4 * 256 * 5)) + (64 << 20)),
+                                           int(tok0 / 4 * 4 * 256 * 5)) + (64 << 20) + self._conv3_ws_bytes(T, H0, W0, (16, 32))),
                 st[2],
                 ops.Arena(like.device, int(tok0 / 16 * 4 * (2048 * 1.1 + 256 * 12)) + (64 << 20)),
                 st[3])

@@ -1123,6 +1123,14 @@ def rowlin(x, pk, out, M, N, K, ldx, ldo, bias=None, a2=None, lda2=0, a2_rows=0,
 # 3x3 / stride 1 / pad 1 convolution 256 -> 256 as a pixel-stationary launch (csrc/chain.hip: tce_conv3x3_f32)
 # ---------------------------------------------------------------------------------------------------------------
 CONV3_MIN_PIXELS = int(os.environ.get("TCE_CONV3_MIN_PIXELS", 12000))
+# A launch that fills less than one round of workgroups is split over the K walk (tce_conv3x3_split_f32) when the call site gives an
+# allocator for its workspace (the pipeline's arenas); TCE_CONV3_SPLIT=0 keeps tce_conv3x3_f32 everywhere (A/B switch).
+CONV3_SPLIT = os.environ.get("TCE_CONV3_SPLIT", "1") != "0"
+
+
+def conv3x3_split_ws_floats(M, Cin=256, N=256):
+    """Workspace (floats) tce_conv3x3_split_f32 needs at M pixels; 0 = nothing is split there."""
+    return int(lib().tce_conv3x3_split_ws_floats(M, Cin, N)) if CONV3_SPLIT else 0
 
 
 def conv3x3_pack(w_cl, Cin):
@@ -1155,9 +1163,17 @@ def conv3x3(x, pk, T, H, W, Cin, N, bias=None, out=None, alloc=None):
     if out is None:
         out = alloc(M, N) if alloc else torch.empty(M, N, dtype=torch.float32, device=x.device)
 
+    nws = conv3x3_split_ws_floats(M, Cin, N) if alloc else 0
+    ws = alloc(nws) if nws else None
+
     def go():
-        check(lib().tce_conv3x3_f32(x.data_ptr(), x.stride(0), pk.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                    out.data_ptr(), out.stride(0), T, H, W, Cin, N, _stream()), "tce_conv3x3_f32")
+        bp = bias.data_ptr() if bias is not None else None
+        if ws is not None:
+            check(lib().tce_conv3x3_split_f32(x.data_ptr(), x.stride(0), pk.data_ptr(), bp, out.data_ptr(), out.stride(0), T, H, W,
+                                              Cin, N, ws.data_ptr(), nws, _stream()), "tce_conv3x3_split_f32")
+        else:
+            check(lib().tce_conv3x3_f32(x.data_ptr(), x.stride(0), pk.data_ptr(), bp, out.data_ptr(), out.stride(0), T, H, W, Cin,
+                                        N, _stream()), "tce_conv3x3_f32")
     if GEMM_PROFILE is None:
         go()
         return out
