@@ -525,9 +525,16 @@ __global__ void __launch_bounds__(64 * WAVES, (WAVES == 4 && C <= 128) ? 2 : WAV
 #pragma unroll
         for (int q = (8 * j) / (2 * NT); q < (8 * (j + 1)) / (2 * NT); ++q) {
           float v0 = hacc[2 * q], v1 = hacc[2 * q + 1];
-          if (A_ == 1) {  // plain v_max: fmaxf() would first quiet a possible sNaN with a second v_max per value
-            asm("v_max_f32_e32 %0, 0, %1" : "=v"(v0) : "v"(v0));
-            asm("v_max_f32_e32 %0, 0, %1" : "=v"(v1) : "v"(v1));
+          if (A_ == 1) {
+            // ReLU as a signed-integer max on the bit patterns: one v_max_i32 per value (negative floats, -0 and negative NaNs are
+            // negative integers -> +0; positive values and positive NaNs pass unchanged, no canonicalising second instruction).
+            // It must be an instruction the compiler sees: hacc is the D of the first product's last MFMA, the scheduler may
+            // place this read right behind it, and only the compiler's hazard recogniser pads the MFMA-write -> VALU-read wait
+            // states.  (A v_max_f32 inside an asm string gets no padding: in the single-pass mode at C <= 128 it was issued
+            // directly after that MFMA and lost the last k16 slice; in the split mode one MFMA and an LDS wait happened to sit
+            // between.)
+            v0 = __builtin_bit_cast(float, max(__builtin_bit_cast(int, v0), 0));
+            v1 = __builtin_bit_cast(float, max(__builtin_bit_cast(int, v1), 0));
           }
           if (A_ == 2) {
             v0 = tce_gelu(v0);
