@@ -102,6 +102,20 @@ def _p(v):
     return int(v) if v else 0
 
 
+# Gather tables whose extent no argument of the entry point carries (the vocabulary of tce_embed_ln_f32): whoever records a
+# pass hands the tensors to `recording(tables=...)` (model.hazard_check: the text encoder's embeddings).  The declarations live
+# for that recording only -- nothing is keyed by an address beyond the life of its tensor -- and a launch on an undeclared
+# table cannot be modelled and is an error.
+TABLES = {}
+
+
+def _table(ptr, what):
+    n = TABLES.get(_p(ptr))
+    if n is None:
+        raise RuntimeError(f"hazard checker: the extent of {what} at {_p(ptr):#x} is unknown (hazard.recording(tables=...))")
+    return dense(_p(ptr), n)
+
+
 def _gemm(g, ws=None, splits=1, ln=None):
     b = max(1, g.batch)
     if g.conv:
@@ -235,8 +249,9 @@ def _ffn_fused(a):
 def _ffn_fused_split(a):
     rd, wr = _ffn_fused(a)
     ws, ws_floats, cnt, ncnt = a[16:20]
-    # the workspace and the counters are written and read inside the launch
-    return rd, wr + [dense(_p(ws), ws_floats * F), dense(_p(cnt), ncnt * 4)]
+    # the workspace is written and read inside the launch; the counters must be ZERO at the launch (their prior content is an
+    # input) and are zero again when it ends
+    return rd + [dense(_p(cnt), ncnt * 4)], wr + [dense(_p(ws), ws_floats * F), dense(_p(cnt), ncnt * 4)]
 
 
 def _ffn_pack(a, batched):
@@ -291,16 +306,21 @@ def _resize_ln(a):
             [dense(_p(out), T * ho * wo * Cn * F)])
 
 
-def _win(a):
+def _win(a, rows):
+    """rows of the relative position bias table: 13 * 13 (2-D windows), 15 * 13 * 13 (3-D windows)"""
     qkv, qb, table, out, T, H, W, Cn, nH = a[:9]
-    return ([dense(_p(qkv), T * H * W * 3 * Cn * F), dense(_p(qb), 3 * Cn * F)], [dense(_p(out), T * H * W * Cn * F)])
+    return ([dense(_p(qkv), T * H * W * 3 * Cn * F), dense(_p(qb), 3 * Cn * F), dense(_p(table), rows * nH * F)],
+            [dense(_p(out), T * H * W * Cn * F)])
 
 
-def _embed(a):
-    ids, pos_ids, word, pos, type0, gamma, beta, out, L, Cn = a[:10]
-    rd = [dense(_p(ids), L * 8), dense(_p(gamma), Cn * F), dense(_p(beta), Cn * F)]
+def _embed(ids, pos_ids, word, pos, type0, gamma, beta, out, L, Cn, pad_id, seq_len):
+    """word rows are gathered by id: the whole declared table; position ids derived in the kernel run up to pad_id + seq_len"""
+    rd = [dense(_p(ids), L * 8), _table(word, "the word embedding table"), dense(_p(type0), Cn * F), dense(_p(gamma), Cn * F),
+          dense(_p(beta), Cn * F)]
     if pos_ids:
-        rd.append(dense(_p(pos_ids), L * 8))
+        rd += [dense(_p(pos_ids), L * 8), _table(pos, "the position embedding table")]
+    else:
+        rd.append(dense(_p(pos), (pad_id + seq_len + 1) * Cn * F))
     return rd, [dense(_p(out), L * Cn * F)]
 
 
@@ -321,11 +341,13 @@ MODELS = {
                                       [dense(_p(a[3]), a[4] * ((a[5] - 1) // 2 + 1) * ((a[6] - 1) // 2 + 1) * 64 * F)]),
     "tce_maxpool3x3s2_cl_f32": lambda a: ([dense(_p(a[0]), a[2] * a[3] * a[4] * a[5] * F)],
                                           [dense(_p(a[1]), a[2] * ((a[3] - 1) // 2 + 1) * ((a[4] - 1) // 2 + 1) * a[5] * F)]),
-    "tce_patch_embed_f32": lambda a: ([dense(_p(a[0]), a[6] * 3 * a[7] * a[8] * F), dense(_p(a[1]), a[9] * 48 * F)],
+    "tce_patch_embed_f32": lambda a: ([dense(_p(a[0]), a[6] * 3 * a[7] * a[8] * F), dense(_p(a[1]), a[9] * 48 * F),
+                                       dense(_p(a[2]), a[9] * F), dense(_p(a[3]), a[9] * F), dense(_p(a[4]), a[9] * F)],
                                       [dense(_p(a[5]), a[6] * ((a[7] + 3) // 4) * ((a[8] + 3) // 4) * a[9] * F)]),
-    "tce_window_attn_f32": _win,
-    "tce_window_attn3d_f32": _win,
-    "tce_patch_merge_ln_f32": lambda a: ([dense(_p(a[0]), a[4] * a[5] * a[6] * a[7] * F)],
+    "tce_window_attn_f32": lambda a: _win(a, 169),
+    "tce_window_attn3d_f32": lambda a: _win(a, 15 * 169),
+    "tce_patch_merge_ln_f32": lambda a: ([dense(_p(a[0]), a[4] * a[5] * a[6] * a[7] * F), dense(_p(a[1]), 4 * a[7] * F),
+                                          dense(_p(a[2]), 4 * a[7] * F)],
                                          [dense(_p(a[3]), a[4] * ((a[5] + 1) // 2) * ((a[6] + 1) // 2) * 4 * a[7] * F)]),
     "tce_mha_f32": lambda a: _mha(a[0], a[1], a[2], a[3], None, *a[4:17]),
     "tce_mha_ws_f32": lambda a: _mha(a[0], a[1], a[2], a[3], a[4], *a[5:18]),
@@ -334,7 +356,8 @@ MODELS = {
          dense(_p(a[3]), a[6] * a[10] * a[8] * a[11] * a[12] * 2 * F), dense(_p(a[4]), a[6] * a[10] * a[8] * a[11] * a[12] * F)],
         [dense(_p(a[5]), a[6] * a[10] * a[8] * a[9] * F)]),
     "tce_ms_deform_attn_backward_f32": lambda a: (
-        [dense(_p(a[0]), a[9] * a[10] * a[11] * a[12] * F), dense(_p(a[3]), a[9] * a[13] * a[11] * a[14] * a[15] * 2 * F),
+        [dense(_p(a[0]), a[9] * a[10] * a[11] * a[12] * F), dense(_p(a[1]), a[14] * 16), dense(_p(a[2]), a[14] * 8),
+         dense(_p(a[3]), a[9] * a[13] * a[11] * a[14] * a[15] * 2 * F),
          dense(_p(a[4]), a[9] * a[13] * a[11] * a[14] * a[15] * F), dense(_p(a[5]), a[9] * a[13] * a[11] * a[12] * F)],
         [dense(_p(a[6]), a[9] * a[10] * a[11] * a[12] * F), dense(_p(a[7]), a[9] * a[13] * a[11] * a[14] * a[15] * 2 * F),
          dense(_p(a[8]), a[9] * a[13] * a[11] * a[14] * a[15] * F)]),
@@ -363,9 +386,14 @@ MODELS = {
     "tce_mask_tail_f32": _mask_tail,
     "tce_select_masks_u8": lambda a: ([dense(_p(a[0]), a[4] * a[5] * a[6] * F), dense(_p(a[1]), a[4] * a[5] * a[7] * a[8] * F)],
                                       [dense(_p(a[2]), a[4] * a[9] * a[10]), dense(_p(a[3]), 4)]),
-    "tce_resize_h_u8": lambda a: ([dense(_p(a[0]), a[4] * a[5] * 3)], [dense(_p(a[3]), a[4] * a[6] * 3)]),
-    "tce_resize_v_norm_f32": lambda a: ([dense(_p(a[0]), a[5] * a[6] * a[7] * 3)], [dense(_p(a[4]), a[5] * 3 * a[8] * a[7] * F)]),
-    "tce_embed_ln_f32": _embed,
+    # in, coef [Wout, ksize] i32, bounds [Wout, 2] i32, tmp, rows, Win, Wout, ksize
+    "tce_resize_h_u8": lambda a: ([dense(_p(a[0]), a[4] * a[5] * 3), dense(_p(a[1]), a[6] * a[7] * 4), dense(_p(a[2]), a[6] * 8)],
+                                  [dense(_p(a[3]), a[4] * a[6] * 3)]),
+    # tmp, coef [Hout, ksize], bounds [Hout, 2], lut [3][256], out, T, Hin, W, Hout, ksize
+    "tce_resize_v_norm_f32": lambda a: ([dense(_p(a[0]), a[5] * a[6] * a[7] * 3), dense(_p(a[1]), a[8] * a[9] * 4), dense(_p(a[2]), a[8] * 8),
+                                         dense(_p(a[3]), 3 * 256 * F)],
+                                        [dense(_p(a[4]), a[5] * 3 * a[8] * a[7] * F)]),
+    "tce_embed_ln_f32": lambda a: _embed(*a[:10], a[11], a[8]),
     "tce_mha_small64_f32": lambda a: ([dense(_p(a[0]), a[2] * 3 * a[3] * 64 * F)], [dense(_p(a[1]), a[2] * a[3] * 64 * F)]),
     "tce_ffn_pack_f32": lambda a: _ffn_pack(a, False),
     "tce_ffn_pack_batched_f32": lambda a: _ffn_pack(a, True),
@@ -433,8 +461,7 @@ MODELS = {
     "tce_caption_lens_f32": lambda a: ([dense(_p(a[0]), a[1] * a[2] * 8)],
                                        [dense(_p(a[5]), a[1] * 4), dense(_p(a[6]), a[1] * a[2]), dense(_p(a[7]), a[1] * a[2] * a[4] * F)]),
     # ids, word, pos, type0, gamma, beta, out, nseq, seq_len, C
-    "tce_embed_ln_seqs_f32": lambda a: ([dense(_p(a[0]), a[7] * a[8] * 8), dense(_p(a[4]), a[9] * F), dense(_p(a[5]), a[9] * F)],
-                                        [dense(_p(a[6]), a[7] * a[8] * a[9] * F)]),
+    "tce_embed_ln_seqs_f32": lambda a: _embed(a[0], None, a[1], a[2], a[3], a[4], a[5], a[6], a[7] * a[8], a[9], a[11], a[8]),
     "tce_swin_attn_pack_f32": lambda a: ([dense(_p(a[0]), 3 * a[3] * a[3] * F), dense(_p(a[1]), a[3] * a[3] * F)],
                                          [dense(_p(a[2]), _lib.lib_raw().tce_swin_attn_packed_bytes(a[3]))]),
     # x, ldx, packed, qkv_bias, proj_bias, table, g1, be1, eps, out, ldo, T, H, W, C, shift
@@ -601,9 +628,12 @@ class _LibProxy:
 
 
 @contextlib.contextmanager
-def recording(dry=False):
-    """with hazard.recording() as rec: ...issue the launch program...; rec.analyse().  dry=True records without launching."""
+def recording(dry=False, tables=()):
+    """with hazard.recording() as rec: ...issue the launch program...; rec.analyse().  dry=True records without launching.
+    tables: tensors that a launch gathers rows from by index (embedding tables): their extents, for this recording."""
     rec = Recorder()
+    TABLES.clear()
+    TABLES.update({int(t.data_ptr()): int(t.numel() * t.element_size()) for t in tables})
     real = _lib.lib()
     Event, Stream = torch.cuda.Event, torch.cuda.Stream
     ev_record, ev_wait, ev_sync, st_sync, dev_sync = Event.record, Event.wait, Event.synchronize, Stream.synchronize, torch.cuda.synchronize
@@ -640,5 +670,6 @@ def recording(dry=False):
     try:
         yield rec
     finally:
+        TABLES.clear()
         _lib._LIB = real
         Event.record, Event.wait, Event.synchronize, Stream.synchronize, torch.cuda.synchronize = ev_record, ev_wait, ev_sync, st_sync, dev_sync

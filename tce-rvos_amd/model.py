@@ -952,13 +952,14 @@ class ReferFormer(nn.Module):
                 st[3])
 
     @torch.no_grad()
-    def hazard_check(self, frames, ids, img_hw=None, valid=None, slot=0, dry=False, groups=1, shared=False, ragged=False):
+    def hazard_check(self, frames, ids, img_hw=None, valid=None, slot=0, dry=False, groups=1, shared=False, ragged=False, observe=None):
         """Records ONE pass of the clip's launch program on the capture topology (the same arenas, side streams, forks and
         joins a captured graph is built from) and checks it for races: any two launches not ordered by a fork / join edge
         must touch disjoint memory (tce_rvos_amd/hazard.py).  frames [T,3,H,W] and token ids [1,L] on the GPU.
         dry=True: the recorded pass launches nothing (negative controls).  ragged=True: the ragged clip-group program
         (forward_group(..., ragged=True); ids [groups, Lmax] right-padded).  Returns a hazard.Report (`.clean`, `str()`);
-        results of the pass are discarded."""
+        results of the pass are discarded.  observe (tests): called as observe("before", resources, None) after the warm-up pass
+        and observe("after", resources, recorder) after the recorded one, everything synchronised; it only looks on."""
         from . import hazard
         frames = frames.to(torch.float32).contiguous()
         T, _, H0, W0 = frames.shape
@@ -974,9 +975,15 @@ class ReferFormer(nn.Module):
             if not dry:  # warm-up: per-shape constants and lazy initialisations (host syncs) happen here, not in the record
                 run()
             torch.cuda.synchronize()
-            with hazard.recording(dry=dry) as rec:
+            if observe is not None:
+                observe("before", res, None)
+                torch.cuda.synchronize()
+            sd = self._text_plan().sd  # rows of these are gathered by token id: the models need their extents
+            with hazard.recording(dry=dry, tables=[sd["embeddings.word_embeddings.weight"], sd["embeddings.position_embeddings.weight"]]) as rec:
                 run()
             torch.cuda.synchronize()
+            if observe is not None:
+                observe("after", res, rec)
         torch.cuda.current_stream().wait_stream(main)
         return rec.analyse()
 
