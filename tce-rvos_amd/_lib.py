@@ -61,6 +61,10 @@ class CopySeg(C.Structure):
     _fields_ = [("src", c_f), ("dst", c_f), ("rows", i64), ("row_words", i64), ("src_pitch_words", i64)]
 
 
+class LabelObj(C.Structure):
+    _fields_ = [("logits", c_f), ("masks", c_f)]
+
+
 # name -> (restype, argtypes); must list EVERY symbol of include/tce_rvos.h (tests check this)
 SIGNATURES = {
     "tce_abi_version": (i32, []),
@@ -171,6 +175,13 @@ DEBUG_SIGNATURES = {
     "tce_debug_conv3x3_set_pieces": (i32, [i32]),
 }
 
+# include/tce_rvos_video.h: driver-stage entry points (what the reference's inference drivers do with the outputs of several
+# forwards); must list every symbol of that header
+VIDEO_SIGNATURES = {
+    # objs (host table), n, labels, best_query, T, Q, K, h, w, H0, W0, threshold, background
+    "tce_label_objects_u8": (i32, [C.POINTER(LabelObj), i32, c_f, c_f, i32, i32, i32, i32, i32, i32, i32, f32, f32, c_f]),
+}
+
 _LIB = None
 
 
@@ -191,7 +202,7 @@ def lib():
             warnings.warn(f"tce_rvos_amd: GPU_MAX_HW_QUEUES={hwq} is set; the HIP runtime's default (4) is the only value this "
                           f"launch program runs well with (1-3 crash the runtime, 5-16 double the clip time)", RuntimeWarning)
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(DEBUG_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(DEBUG_SIGNATURES.items()) + list(VIDEO_SIGNATURES.items()):
             fn = getattr(l, name)  # AttributeError if the symbol is absent
             fn.restype = res
             fn.argtypes = args

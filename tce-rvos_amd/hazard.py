@@ -471,6 +471,22 @@ MODELS = {
          dense(_p(a[6]), a[14] * F), dense(_p(a[7]), a[14] * F)],
         [strided(_p(a[9]), a[14] * F, (a[11] * a[12] * a[13], a[10] * F))]),
 }
+
+
+def _label_objects(a):
+    """objs (host table), n, labels, best_query, T, Q, K, h, w, H0, W0: every object's logits and mask planes are read (any query
+    can be the best one); best_query is written by the first launch and read by the second (the write covers both)"""
+    objs, n, labels, best, T, Q, K, h, w, H0, W0 = a[:11]
+    rd = []
+    for i in range(n):
+        rd += [dense(_p(objs[i].logits), T * Q * K * F), dense(_p(objs[i].masks), T * Q * h * w * F)]
+    return rd, [dense(_p(labels), T * H0 * W0), dense(_p(best), n * 4)]
+
+
+# Entry points of include/tce_rvos_video.h (_lib.VIDEO_SIGNATURES): consulted after MODELS
+VIDEO_MODELS = {
+    "tce_label_objects_u8": _label_objects,
+}
 # Entry points that launch nothing (queries, process switches, graph helpers, tuning aids): passed through.
 NOT_LAUNCHES = {"tce_abi_version", "tce_last_error", "tce_gemm_select_tile", "tce_gemm_select_tile_ex", "tce_set_gemm_mode", "tce_set_gemm_mode_thread",
                 "tce_get_gemm_mode", "tce_set_range_flag", "tce_groupnorm_nsplit", "tce_mha_ws_bytes", "tce_ffn_packed_bytes", "tce_ffn_split_ws_floats", "tce_ffn_split_counters",
@@ -615,7 +631,7 @@ class _LibProxy:
         fn = getattr(self._real, name)
         if name in NOT_LAUNCHES or not name.startswith("tce_"):
             return fn
-        model = MODELS.get(name)
+        model = MODELS.get(name) or VIDEO_MODELS.get(name)
         if model is None:
             raise RuntimeError(f"hazard checker: no access model for {name} (add one to hazard.MODELS)")
         rec, dry = self._rec, self._dry

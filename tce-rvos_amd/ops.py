@@ -939,6 +939,56 @@ def select_masks(pred_logits, pred_masks, out_hw, threshold=0.5):
     return out, best
 
 
+LABEL_MAX_OBJS = 16  # TCE_LABEL_MAX_OBJS (include/tce_rvos_video.h)
+
+
+def label_objects(pred_logits, pred_masks, out_hw, threshold=0.5, background=0.1, out=None, best_out=None):
+    """Ref-DAVIS label map of one chunk (inference_davis.py:239-248, 293-298) on the GPU: the n objects of a label map, each with
+    its own forward's pred_logits [T,Q,K] and pred_masks [T,Q,h,w] (lists of n tensors, or stacked [n,T,Q,K] / [n,T,Q,h,w])
+    -> (labels uint8 [T,H0,W0]: 0 = background, k + 1 = object k; best-query indices int32 [n]).
+    The tensors' addresses go into the launch's table as they are: no stacked copy of the masks is made, so every tensor must be
+    contiguous float32 on the GPU.  out / best_out: write into these (e.g. a chunk's slice of a video's label map) instead of new tensors."""
+    lg = list(pred_logits.unbind(0)) if torch.is_tensor(pred_logits) else list(pred_logits)
+    pm = list(pred_masks.unbind(0)) if torch.is_tensor(pred_masks) else list(pred_masks)
+    n = len(lg)
+    if n < 1 or n > LABEL_MAX_OBJS:
+        raise ValueError(f"label_objects: 1..{LABEL_MAX_OBJS} objects per label map, got {n}")
+    if len(pm) != n:
+        raise ValueError(f"label_objects: {n} pred_logits but {len(pm)} pred_masks")
+    if lg[0].dim() != 3 or pm[0].dim() != 4:
+        raise ValueError("label_objects: pred_logits must be [T,Q,K] and pred_masks [T,Q,h,w] per object")
+    T, Q, K = (int(s) for s in lg[0].shape)
+    h, w = int(pm[0].shape[2]), int(pm[0].shape[3])
+    H0, W0 = int(out_hw[0]), int(out_hw[1])
+    for k in range(n):
+        if tuple(lg[k].shape) != (T, Q, K) or tuple(pm[k].shape) != (T, Q, h, w):
+            raise ValueError(f"label_objects: object {k} has pred_logits {tuple(lg[k].shape)} / pred_masks {tuple(pm[k].shape)}, "
+                             f"object 0 has {(T, Q, K)} / {(T, Q, h, w)}")
+    for k in range(n):
+        for t, name in ((lg[k], "pred_logits"), (pm[k], "pred_masks")):
+            if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.device != pm[0].device:
+                raise ValueError(f"label_objects: {name}[{k}] must be a contiguous float32 tensor on the GPU (one device), got "
+                                 f"{t.dtype} on {t.device}, contiguous={t.is_contiguous()}")
+    if min(T, Q, K, h, w, H0, W0) < 1:
+        raise ValueError("label_objects: empty extent")
+    dev = pm[0].device
+    if out is None:
+        out = torch.empty(T, H0, W0, dtype=torch.uint8, device=dev)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (T, H0, W0) or not out.is_contiguous() or out.device != dev:
+        raise ValueError("label_objects: out must be a contiguous uint8 [T,H0,W0] on the inputs' device")
+    if best_out is None:
+        best_out = torch.empty(n, dtype=torch.int32, device=dev)
+    elif best_out.dtype != torch.int32 or tuple(best_out.shape) != (n,) or not best_out.is_contiguous() or best_out.device != dev:
+        raise ValueError("label_objects: best_out must be a contiguous int32 [n] on the inputs' device")
+    from ._lib import LabelObj
+    table = (LabelObj * n)()  # read by the entry point on the host, at this call
+    for k in range(n):
+        table[k].logits, table[k].masks = lg[k].data_ptr(), pm[k].data_ptr()
+    check(lib().tce_label_objects_u8(table, n, out.data_ptr(), best_out.data_ptr(), T, Q, K, h, w, H0, W0, float(threshold),
+                                     float(background), _stream()), "tce_label_objects_u8")
+    return out, best_out
+
+
 def ffn_pack(w1, b1, w2, out=None):
     """Packs nn.Linear weights W1 [Hd,C], b1 [Hd], W2 [C,Hd] into the fused-FFN stream (csrc/chain.hip): fp16 hi/lo
     planes in MFMA-fragment order.  Done once per load_state_dict (static weights) or once per clip into an arena

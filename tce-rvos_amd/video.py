@@ -13,6 +13,10 @@ Two loops of the reference's callers, with the model call and the caller harness
   one length go through `model.forward_group` with the SAME clip tensor, so the backbone runs once per chunk and the rest of the
   program is shared by the group; each expression's result is what `run_video` returns for it.
 
+* `run_video_objects(...)` -- the Ref-DAVIS driver's end (inference_davis.py:185-199 and 293-298): the expressions of a video are
+  run ONCE per chunk (clip groups, as above), and each annotator's objects are combined into one uint8 label map per chunk by one
+  launch (ops.label_objects: best query, up-sampling, sigmoid, threshold, background plane and arg-max over the objects).
+
 A video's chunks share the caption, so with `model.text_cache_size > 0` RoBERTa runs once per expression instead of
 once per chunk (the reference recomputes it inside every forward).  Chunks of one length share a captured hipGraph
 (model._graphs is an LRU over shapes); a last, shorter chunk runs eagerly unless its shape comes back.
@@ -109,3 +113,86 @@ def run_video_expressions(model, frames: torch.Tensor, captions, origin_hw, clip
                 _collect(out, origin_hw, threshold, accs[i])
     ops.check_range(frames.device)
     return [{k: torch.cat(v, 0) for k, v in a.items()} for a in accs]
+
+
+def davis_annotator_sets(num_expressions: int):
+    """inference_davis.py:185-194: a Ref-DAVIS video lists its expressions object-major with 4 annotators per object
+    (expression obj * 4 + anno); annotator `anno`'s label map holds object `obj` as label obj + 1.  Returns the 4 index lists."""
+    num_obj = int(num_expressions) // 4
+    return [[obj * 4 + anno for obj in range(num_obj)] for anno in range(4)]
+
+
+def plan_object_forwards(lengths, n_frames, clip_size=32, object_sets=None, max_group: int = 4, mixed_lengths: bool = False):
+    """The forwards of run_video_objects, in order: (sets, [(lo, hi, [caption indices of one forward_group call]), ...]).  The chunk
+    loop is the outer one; inside a chunk every caption that some set names runs exactly once, however many sets name it, grouped
+    by plan_expression_groups.  sets = object_sets checked (default: one set of all captions, in order)."""
+    ncap = len(lengths)
+    sets = [list(range(ncap))] if object_sets is None else [[int(i) for i in s] for s in object_sets]
+    for s in sets:
+        if not 1 <= len(s) <= ops.LABEL_MAX_OBJS:
+            raise ValueError(f"run_video_objects: a label map holds 1..{ops.LABEL_MAX_OBJS} objects, a set has {len(s)}")
+        if any(i < 0 or i >= ncap for i in s) or len(set(s)) != len(s):
+            raise ValueError(f"run_video_objects: set {s} must name distinct captions out of {ncap}")
+    used = sorted({i for s in sets for i in s})
+    groups = [[used[j] for j in g] for g in plan_expression_groups([lengths[i] for i in used], max_group, mixed_lengths)]
+    step = int(n_frames) if not clip_size else int(clip_size)
+    return sets, [(lo, min(lo + step, int(n_frames)), g) for lo in range(0, int(n_frames), step) for g in groups]
+
+
+@torch.no_grad()
+def run_video_objects(model, frames: torch.Tensor, captions, origin_hw, clip_size: Optional[int] = 32, object_sets=None,
+                      max_group: int = 4, mixed_lengths: bool = False, threshold: float = 0.5, background: float = 0.1):
+    """The label maps of ONE video (inference_davis.py:185-298 without the PNG writing).  frames, captions, clip_size, max_group and
+    mixed_lengths as in run_video_expressions; object_sets: lists of caption indices, one list per label map (default: one map of
+    all captions in order; davis_annotator_sets gives the driver's four).  Label k + 1 of a map is the k-th caption of its set, 0
+    is background (no object's score reaches `threshold`; `background` is the driver's 0.1 plane).
+    Returns one dict per set: labels uint8 [N,H0,W0], best_query int32 [n, n_chunks], pred_logits [n,N,K], pred_boxes [n,N,4]
+    (per object what run_video_expressions returns for its caption).
+
+    A caption runs once per chunk whatever the number of sets that name it.  The chunk's forwards all finish (are issued) before its
+    label launches, so the outputs of several forward_group calls are read afterwards.  They stay valid: forward / forward_group hand
+    back FRESH tensors from every call -- the eager program clones its outputs out of the arena (pipeline.run_clip, clone_outputs),
+    a graph replay copies them out of the graph's static buffers into a new allocation (model._replay, ops.CopyPlan.clone) -- so a
+    later forward writes none of them, and this function holds them until the chunk's last label launch has been issued on the same
+    stream.  Each clip's pred_logits[0] / pred_masks[0] is a contiguous slice of such a tensor; its address goes into the launch's table."""
+    if frames.dim() != 4 or frames.shape[1] != 3 or frames.shape[0] == 0:
+        raise ValueError("run_video_objects: frames must be a non-empty [N,3,H,W]")
+    n = int(frames.shape[0])
+    H, W = int(frames.shape[-2]), int(frames.shape[-1])
+    H0, W0 = int(origin_hw[0]), int(origin_hw[1])
+    dev = frames.device
+    target = [{"size": torch.tensor([H, W])}]
+    ids = [c if torch.is_tensor(c) else model._tokenise([c], dev)[0] for c in captions]
+    sets, plan = plan_object_forwards([int(t.shape[1]) for t in ids], n, clip_size, object_sets, max_group, mixed_lengths)
+    toks = {}
+    for _, _, grp in plan:
+        if tuple(grp) not in toks:
+            if mixed_lengths:  # right-padded on the host (validated there), lengths derived again on the device
+                from .model import pad_captions
+                toks[tuple(grp)] = pad_captions([ids[i] for i in grp], model._pad_id())[0].to(dev)
+            else:
+                toks[tuple(grp)] = torch.cat([ids[i].to(dev) for i in grp], 0)
+    starts = sorted({lo for lo, _, _ in plan})
+    res = [{"labels": torch.empty(n, H0, W0, dtype=torch.uint8, device=dev),
+            "best_query": torch.empty(len(starts), len(s), dtype=torch.int32, device=dev), "pred_logits": [], "pred_boxes": []} for s in sets]
+    for c, lo in enumerate(starts):
+        hi, held = lo, {}
+        for plo, phi, grp in plan:
+            if plo != lo:
+                continue
+            hi = phi
+            clip = frames[lo:hi]
+            # one tensor, len(grp) captions: shared backbone
+            outs = model.forward_group([clip] * len(grp), toks[tuple(grp)], target, **({"ragged": True} if mixed_lengths else {}))
+            for i, out in zip(grp, outs):
+                held[i] = (out["pred_logits"][0], out["pred_masks"][0], out["pred_boxes"][0])
+        ar = torch.arange(hi - lo, device=dev)
+        for s, r in zip(sets, res):
+            _, best = ops.label_objects([held[i][0] for i in s], [held[i][1] for i in s], (H0, W0), threshold, background,
+                                        out=r["labels"][lo:hi], best_out=r["best_query"][c])
+            idx = best.long()
+            r["pred_logits"].append(torch.stack([held[i][0][ar, idx[k].expand(hi - lo)] for k, i in enumerate(s)], 0))
+            r["pred_boxes"].append(torch.stack([held[i][2][ar, idx[k].expand(hi - lo)] for k, i in enumerate(s)], 0))
+    ops.check_range(dev)
+    return [{"labels": r["labels"], "best_query": r["best_query"].t().contiguous(), "pred_logits": torch.cat(r["pred_logits"], 1),
+             "pred_boxes": torch.cat(r["pred_boxes"], 1)} for r in res]
