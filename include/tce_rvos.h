@@ -363,6 +363,15 @@ int tce_ffn_fused_f32(const float* x, int64_t ldx, const void* packed, const flo
  * sums -- the same bits whichever piece arrives last -- runs the epilogue and resets the counter): give each call site that can run
  * concurrently with another its own.  Results differ from tce_ffn_fused_f32's by fp32 round-off (one more addition per element). */
 int64_t tce_ffn_split_ws_floats(int32_t M, int32_t C, int32_t Hd, int32_t act);
+/* Cap on the workgroups of the calling THREAD's tce_ffn_fused_f32 / tce_xattn_fused_f32 launches (0 = none, the default; launches
+ * nothing).  A C = 256 launch (ReLU FFN, or a cross-attention fold) of more 128-row blocks in all than the cap runs as
+ * grid.x = max(1, cap / batch) persistent workgroups per batch entry, each walking its blocks with a static stride: it then occupies
+ * that many CUs for its whole duration and leaves the rest to the launches beside it.  Same bits as the uncapped launch, same bytes
+ * touched.  Other shapes, GELU, the split and the chained forms ignore the cap.  Like the arithmetic mode it is read when a launch
+ * is issued, so a captured graph keeps it per node.  tce_ffn_capped_grid: the launcher's arithmetic (grid.x, *persistent = 1 when
+ * the persistent form is taken) for `blocks` blocks on each of `batch` entries. */
+int tce_ffn_set_wg_cap(int32_t cap);
+int32_t tce_ffn_capped_grid(int32_t cap, int32_t batch, int32_t blocks, int32_t* persistent);
 int32_t tce_ffn_split_counters(int32_t M, int32_t C, int32_t Hd, int32_t act);
 int tce_ffn_fused_split_f32(const float* x, int64_t ldx, const void* packed, const float* b2, const float* g_in, const float* be_in,
                             float eps_in, const float* g_out, const float* be_out, float eps_out, float* out, int64_t ldo, int32_t M,

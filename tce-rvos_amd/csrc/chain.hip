@@ -329,9 +329,18 @@ struct FfnArgs {
 // branch in front of every step's two lo-term MFMAs (and around every hi / lo split), and the basic-block boundaries kept the
 // scheduler from overlapping a step's loads, DMA and split with its MFMAs: 192 -> 175 us at 24100 rows, 90 -> 79 us for the
 // C = 192 instantiation, the config-2 clip 6.87 -> 6.63 ms (A/B in one call, profiles/r04_single_template.txt).
-template <int C, int WAVES, int ACT, bool SINGLE, int ACT2 = 0, bool SPLIT = false>
+//
+// PERSIST: a workgroup runs the 128-row blocks blockIdx.x, blockIdx.x + gridDim.x, ... (static stride, no state between workgroups):
+// a launch of 72000 rows capped to a few dozen workgroups (ffn_grid_plan, tce_ffn_set_wg_cap) occupies that many CUs -- the 154 KiB of
+// LDS allow one workgroup per CU -- for its whole duration and leaves the others to the kernels beside it, as ONE graph node.  Per
+// block it does exactly what a workgroup of the plain form does (stream pointer back to wp0, ring stage 0 primed, x loaded,
+// accumulators zeroed, loop, epilogue), so the result is the same bits.  Re-priming is safe where it stands: every loop iteration ends
+// with vmcnt(0) + the workgroup barrier (the block's last prefetch has landed, no wave still reads the ring), the epilogue works in
+// the wave's private staging tile only, and a wave's LDS operations execute in order.
+template <int C, int WAVES, int ACT, bool SINGLE, int ACT2 = 0, bool SPLIT = false, bool PERSIST = false>
 __global__ void __launch_bounds__(64 * WAVES, (WAVES == 4 && C <= 128) ? 2 : WAVES / 4) ffn_fused_kernel(const FfnArgs p) {
   static_assert(!(SPLIT && ACT2 != 0), "a chain is not split");
+  static_assert(!PERSIST || (!SPLIT && ACT2 == 0 && !(WAVES == 4 && C <= 128)), "the persistent form is the plain kernel, staging tiles of its own");
   constexpr int KS = C / 16, NT = C / 32;
   // HALF (round 5): the C <= 128 kernels (packed for 8 waves = 256 rows per workgroup) as 128-row workgroups, TWO per CU, reading the
   // same stream.  72000 rows are 282 workgroups of 256 rows = 1.1 rounds of the chip that cost two; as 563 half workgroups the 51 of
@@ -396,8 +405,14 @@ __global__ void __launch_bounds__(64 * WAVES, (WAVES == 4 && C <= 128) ? 2 : WAV
   // i - 1 (a piece over chunks [c0, c1) is the stream's iterations c0 .. c1: the first applies W2[c0 - 1] to a zero H, the last
   // computes an H nobody reads)
   constexpr int NPC = SPLIT ? 2 : 1;
-  for (int pc = 0; pc < NPC; ++pc) {
+  // PERSIST: the passes of this workgroup (the launcher keeps gridDim.x <= blocks, so there is at least one)
+  const int npass = PERSIST ? ((p.M + 32 * WAVES - 1) / (32 * WAVES) - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x : NPC;
+  for (int pc = 0; pc < (PERSIST ? npass : NPC); ++pc) {
   int blk = blockIdx.x, nit = p.NI;
+  if constexpr (PERSIST) {
+    blk += pc * (int)gridDim.x;
+    wp = wp0;
+  }
   if constexpr (SPLIT) {
     const int q = p.sp_p + 1, g = blockIdx.x / q, i = blockIdx.x - g * q;
     int c0 = 0;
@@ -1094,6 +1109,19 @@ inline FfnSplitPlan ffn_split_plan(int M, int C, int Hd, int batch) {
 
 static int g_ffn_half = 0;  // tce_debug_ffn_set_half: 0 automatic, 1 always (C <= 128), -1 never
 
+// Capped launches (tce_ffn_set_wg_cap, PERSIST in ffn_fused_kernel): `blocks` 128-row blocks on each of `batch` grid.y entries under
+// a cap of `cap` workgroups.  A cap that the launch stays inside anyway (or 0) is the plain launch, one workgroup per block.
+struct FfnGridPlan {
+  int grid_x, persist;
+};
+inline FfnGridPlan ffn_grid_plan(int cap, int batch, int blocks) {
+  if (cap <= 0 || batch < 1 || (long long)blocks * batch <= cap) return {blocks, 0};
+  const int gx = cap / batch > 1 ? cap / batch : 1;
+  if (gx >= blocks) return {blocks, 0};  // (one block per entry, more entries than the cap)
+  return {gx, 1};
+}
+[[maybe_unused]] static thread_local int t_ffn_wg_cap = 0;  // tce_ffn_set_wg_cap: the calling thread's cap, 0 = none
+
 template <int C, int WAVES>
 void ffn_launch(const FfnArgs& a, int act, hipStream_t s, int batch = 1) {
   if constexpr (C == 256) {
@@ -1117,6 +1145,15 @@ void ffn_launch(const FfnArgs& a, int act, hipStream_t s, int batch = 1) {
       const dim3 grid(tce_cdiv(a.M, 128), batch), block(256);
       if (a.single) hipLaunchKernelGGL((ffn_fused_kernel<C, 4, 2, true>), grid, block, 0, s, a);
       else hipLaunchKernelGGL((ffn_fused_kernel<C, 4, 2, false>), grid, block, 0, s, a);
+      return;
+    }
+  }
+  if constexpr (C == 256) {
+    const FfnGridPlan gp = ffn_grid_plan(t_ffn_wg_cap, batch, tce_cdiv(a.M, 32 * WAVES));
+    if (gp.persist && act == 1) {
+      const dim3 grid(gp.grid_x, batch), block(64 * WAVES);
+      if (a.single) hipLaunchKernelGGL((ffn_fused_kernel<C, WAVES, 1, true, 0, false, true>), grid, block, 0, s, a);
+      else hipLaunchKernelGGL((ffn_fused_kernel<C, WAVES, 1, false, 0, false, true>), grid, block, 0, s, a);
       return;
     }
   }
@@ -1775,6 +1812,18 @@ extern "C" int tce_ffn_fused_f32(const float* x, int64_t ldx, const void* packed
   return TCE_OK;
 }
 
+extern "C" int tce_ffn_set_wg_cap(int32_t cap) {
+  TCE_CHECK_ARG(cap >= 0, "tce_ffn_set_wg_cap: cap must be >= 0 (0 = none)");
+  t_ffn_wg_cap = cap;
+  return TCE_OK;
+}
+
+extern "C" int32_t tce_ffn_capped_grid(int32_t cap, int32_t batch, int32_t blocks, int32_t* persistent) {
+  const FfnGridPlan gp = ffn_grid_plan(cap, batch, blocks);
+  if (persistent) *persistent = gp.persist;
+  return gp.grid_x;
+}
+
 extern "C" int tce_debug_ffn_set_half(int32_t mode) {
   TCE_CHECK_ARG(mode >= -1 && mode <= 1, "tce_debug_ffn_set_half: -1 (never), 0 (automatic) or 1 (always)");
   g_ffn_half = mode;
@@ -1936,6 +1985,19 @@ static int xattn_launch(const tceXattnArgs* args, const tceXattnFfnArgs* ffn, tc
       else hipLaunchKernelGGL((ffn_fused_kernel<256, 4, 4, false, 1>), grid, block, 0, (hipStream_t)stream, a);
     }
     TCE_CHECK_LAUNCH("tce_xattn_ffn_fused_f32");
+    return TCE_OK;
+  }
+  const FfnGridPlan gp = ffn_grid_plan(t_ffn_wg_cap, batch, tce_cdiv(a.M, 128));
+  if (gp.persist) {
+    const dim3 pgrid(gp.grid_x, batch);
+    if (a.single) {
+      if (q.group == 32) hipLaunchKernelGGL((ffn_fused_kernel<256, 4, 3, true, 0, false, true>), pgrid, block, 0, (hipStream_t)stream, a);
+      else hipLaunchKernelGGL((ffn_fused_kernel<256, 4, 4, true, 0, false, true>), pgrid, block, 0, (hipStream_t)stream, a);
+    } else {
+      if (q.group == 32) hipLaunchKernelGGL((ffn_fused_kernel<256, 4, 3, false, 0, false, true>), pgrid, block, 0, (hipStream_t)stream, a);
+      else hipLaunchKernelGGL((ffn_fused_kernel<256, 4, 4, false, 0, false, true>), pgrid, block, 0, (hipStream_t)stream, a);
+    }
+    TCE_CHECK_LAUNCH("tce_xattn_fused_f32");
     return TCE_OK;
   }
   if (a.single) {

@@ -490,6 +490,7 @@ VIDEO_MODELS = {
 # Entry points that launch nothing (queries, process switches, graph helpers, tuning aids): passed through.
 NOT_LAUNCHES = {"tce_abi_version", "tce_last_error", "tce_gemm_select_tile", "tce_gemm_select_tile_ex", "tce_set_gemm_mode", "tce_set_gemm_mode_thread",
                 "tce_get_gemm_mode", "tce_set_range_flag", "tce_groupnorm_nsplit", "tce_mha_ws_bytes", "tce_ffn_packed_bytes", "tce_ffn_split_ws_floats", "tce_ffn_split_counters",
+                "tce_ffn_set_wg_cap", "tce_ffn_capped_grid",
                 "tce_rowlin_packed_bytes", "tce_conv3x3_packed_bytes", "tce_conv3x3_split_ws_floats",
                 "tce_conv3x3_split_pieces", "tce_conv3x3_split_kstep", "tce_swin_attn_packed_bytes", "tce_thin_linear_splits", "tce_graph_begin", "tce_graph_end", "tce_graph_launch",
                 "tce_graph_destroy", "tce_graph_group"} | set(_lib.DEBUG_SIGNATURES)

@@ -133,6 +133,28 @@ class arith:
         return False
 
 
+class ffn_wg_cap:
+    """`with ops.ffn_wg_cap(n):` -- the fused-FFN / folded cross-attention launches inside occupy at most n workgroups (one per CU:
+    the persistent form of csrc/chain.hip, tce_ffn_set_wg_cap); 0 or None = no cap.  Same bits as the uncapped launches.  Like the
+    arithmetic mode the cap is per THREAD and read when a launch is issued: a captured graph keeps it per node."""
+
+    def __init__(self, n):
+        self.n, self.prev = int(n or 0), 0
+
+    def __enter__(self):
+        self.prev = getattr(_ARITH_TL, "wg_cap", 0)
+        if self.n != self.prev:
+            _ARITH_TL.wg_cap = self.n
+            check(lib().tce_ffn_set_wg_cap(self.n), "tce_ffn_set_wg_cap")
+        return self
+
+    def __exit__(self, *exc):
+        if self.n != self.prev:
+            _ARITH_TL.wg_cap = self.prev
+            check(lib().tce_ffn_set_wg_cap(self.prev), "tce_ffn_set_wg_cap")
+        return False
+
+
 def _stream():
     return torch.cuda.current_stream().cuda_stream
 

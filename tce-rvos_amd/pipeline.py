@@ -42,7 +42,7 @@ def _lin(A, x, M, K, w, b, N, **kw):
 # Environment switches of the launch program, read ONCE at import: they are constants of the process, so every capture of
 # the process is built from the same program (none of them needs to be part of a graph key).
 #   scheduling A/B switches (results identical): TCE_FEWROW, TCE_TEXT_LATE, TCE_TEXT_EARLY_EDGE, TCE_EARLY_PROJ, TCE_TOKFORK, TCE_ENCFORK,
-#       TCE_LAT1_AT; TCE_FEWROW_SITES (bisect aid: which sites take the few-row kernel)
+#       TCE_LAT1_AT, TCE_LAT1_CUS; TCE_FEWROW_SITES (bisect aid: which sites take the few-row kernel)
 #   DIAGNOSTICS that change what forward() returns -- set by tools/ only, announced with a warning at import:
 #       TCE_ABLATE (tools/ablate_times.py): the named stages are SKIPPED, results are garbage (the time that disappears is
 #           the stage's share of the critical path); model.forward() tags its output dict with out["ablated"];
@@ -57,7 +57,14 @@ EARLY_PROJ = os.environ.get("TCE_EARLY_PROJ", "1") != "0"
 TOKFORK = os.environ.get("TCE_TOKFORK", "1") != "0"
 ENCFORK = os.environ.get("TCE_ENCFORK", "1") != "0"
 DEFER_OUT_NORM = os.environ.get("TCE_DEFER_OUT_NORM", "1") != "0"  # A/B: 0 = every Swin stage's output norm on the backbone's own stream
-LAT1_AT = os.environ.get("TCE_LAT1_AT")
+LAT1_AT = os.environ.get("TCE_LAT1_AT")  # "text" (the text join, during the backbone), "backbone", "encN"
+# Workgroup cap of the stride-4 lateral branch's two 72000-row launches (ops.ffn_wg_cap): set = that cap wherever the branch runs
+# early (0 = none); unset = LAT1_CUS_DEFAULT where it was measured to pay (one clip per forward, a
+# Swin backbone, a stride-4 map of at least config 2's LAT1_CUS_MIN_BLOCKS 128-row blocks: profiles/r10_lat1_capped.txt), none
+# elsewhere.  A capped branch starts after the backbone unless TCE_LAT1_AT says otherwise, an uncapped one where it always did.
+LAT1_CUS = int(os.environ["TCE_LAT1_CUS"]) if os.environ.get("TCE_LAT1_CUS", "") != "" else None
+LAT1_CUS_DEFAULT = 64
+LAT1_CUS_MIN_BLOCKS = 563
 SWIN3_FC2_SPLITK = int(os.environ.get("TCE_SWIN3_FC2_SPLITK", 2))
 # norm1 / norm2 of the frame-token path in the prologue of the few-row launch that follows them (8 launches fewer per clip): measured
 # NOT faster -- 6.055 / 6.047 ms with it against 6.030 / 6.043 without (A/B twice in one call, gpurun_out/r6k): every workgroup of the
@@ -366,14 +373,32 @@ def _run_clip(model, frames, text, img_h, img_w, ar, side_arena=None, side_strea
         hw_i = sizes[i][0] * sizes[i][1]
         return feat[select * hw_i:(select + 1) * hw_i]
 
+    lat1_cap = LAT1_CUS
+    if lat1_cap is None:
+        measured = G == 1 and not cfg.is_resnet and not cfg.video and -(-(T * sizes[0][0] * sizes[0][1]) // 128) >= LAT1_CUS_MIN_BLOCKS
+        lat1_cap = LAT1_CUS_DEFAULT if measured else 0
     pending_norm0 = []  # stage 0's output norm, applied at the head of the stride-4 lateral branch (start_lat1)
 
+    def start_lat1(feat0=None, wait_text=False):
+        ar2.reset()
+        lat1_fork = _Fork(stream2)
+        with lat1_fork:
+            while pending_norm0:
+                pending_norm0.pop()()  # Swin stage 0's output norm, here where its only consumer runs
+            if wait_text:
+                text_fork.join()  # the branch's stream waits for the text branch (the folded stream of its cross-attention)
+            with ops.ffn_wg_cap(lat1_cap):  # its cross-attention fold and its FFN: the only launches of the branch that read the cap
+                return (lat1_fork, _lateral(model, sc, feats if feat0 is None else [feat0], None, vl_sites, T, L, ffn, ln_, 1, ar2, G))
+
     def on_stage(i, feat, finish=None):
+        nonlocal lat1
         if i == 0 and text_late:
             text_stage()
         if i == 0 and finish is not None:
             pending_norm0.append(finish)
         feat = pick(feat, i)
+        if i == 0 and LAT1_AT == "text" and ar2 is not None and stream2 is not None:
+            lat1 = start_lat1(feat, wait_text=True)  # TCE_LAT1_AT=text: from the text join on, beside Swin stages 1-3
         if early:
             if i in (1, 2):
                     arx, stx = fork3[i - 1]
@@ -403,20 +428,16 @@ def _run_clip(model, frames, text, img_h, img_w, ar, side_arena=None, side_strea
     # adapter_1 + GroupNorm + VisionLanguageBlock at stride 4 read the backbone's C2 map and the text only -- not the
     # encoder memory (segmentation.py:187-196 with the backbone feature as the last lateral input) -- so this millisecond
     # of work is a parallel graph branch, joined when the top-down chain reaches stride 4.
-    def start_lat1():
-        ar2.reset()
-        lat1_fork = _Fork(stream2)
-        with lat1_fork:
-            while pending_norm0:
-                pending_norm0.pop()()  # Swin stage 0's output norm, here where its only consumer runs
-            return (lat1_fork, _lateral(model, sc, feats, None, vl_sites, T, L, ffn, ln_, 1, ar2, G))
     # When it starts is a trade: its long kernels (72000-row cross-attention, FFN, GEMMs) slow down whatever runs beside
     # them, and it must be done when the chain reaches stride 4.  Measured at config 2 (ms per clip): right after Swin
     # stage 0 8.09, after the backbone 7.44, after encoder layer 0 / 1 / 2 / 3 (of 4) 7.41 / 7.37 / 7.27 / 7.71 ->
     # one encoder layer before the end ("backbone" / "encN" override for experiments).
-    lat1_when = LAT1_AT or (f"enc{cfg.enc_layers - 2}" if cfg.enc_layers >= 2 else "backbone")
-    if ar2 is not None and stream2 is not None and lat1_when == "backbone":
-        lat1 = start_lat1()
+    # With its two 72000-row launches capped to a few dozen CUs (lat1_cap: one persistent workgroup per CU, the other CUs stay free
+    # for the short critical kernels) the trade changes: started right after the backbone it runs beside the whole encoder, and
+    # the clip goes 6.19 -> 5.97 ms at 64 CUs (start x cap table and confirmation pairs: profiles/r10_lat1_capped.txt).
+    lat1_when = LAT1_AT or (f"enc{cfg.enc_layers - 2}" if cfg.enc_layers >= 2 and lat1_cap <= 0 else "backbone")
+    if ar2 is not None and stream2 is not None and lat1 is None and lat1_when in ("backbone", "text"):
+        lat1 = start_lat1()  # ("text" without a Swin stage callback -- a ResNet backbone -- starts here too)
     # ------------------------------------------------------------------ input_proj + early fusion (:258-307)
     # The four levels are independent (they write disjoint slices of src).  Without the early start: level 0 on the main
     # stream, levels 1-3 as one parallel branch on the side stream (idle here: the text branch has joined, the decoder
