@@ -184,6 +184,16 @@ VIDEO_SIGNATURES = {
     "tce_label_objects_u8": (i32, [C.POINTER(LabelObj), i32, c_f, c_f, i32, i32, i32, i32, i32, i32, i32, f32, f32, c_f]),
 }
 
+# include/tce_rvos_eval.h: evaluation-stage entry points (the A2D-Sentences / JHMDB-Sentences post-processor); must list every
+# symbol of that header
+EVAL_SIGNATURES = {
+    # masks [N,h,w], out [N,H0,W0], N, h, w, fh, fw, H0, W0, threshold
+    "tce_a2d_masks_u8": (i32, [c_f, c_f, i32, i32, i32, i32, i32, i32, i32, f32, c_f]),
+    "tce_rle_ws_bytes": (i64, [i32, i32, i32]),
+    # masks [P,H,W] u8, counts [P,H*W+1] u32, nruns [P] i32, ws, P, H, W
+    "tce_rle_counts_u32": (i32, [c_f, c_f, c_f, c_f, i32, i32, i32, c_f]),
+}
+
 _LIB = None
 
 
@@ -204,7 +214,8 @@ def lib():
             warnings.warn(f"tce_rvos_amd: GPU_MAX_HW_QUEUES={hwq} is set; the HIP runtime's default (4) is the only value this "
                           f"launch program runs well with (1-3 crash the runtime, 5-16 double the clip time)", RuntimeWarning)
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(DEBUG_SIGNATURES.items()) + list(VIDEO_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(DEBUG_SIGNATURES.items()) + list(VIDEO_SIGNATURES.items()) + \
+                list(EVAL_SIGNATURES.items()):
             fn = getattr(l, name)  # AttributeError if the symbol is absent
             fn.restype = res
             fn.argtypes = args

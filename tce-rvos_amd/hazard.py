@@ -487,13 +487,33 @@ def _label_objects(a):
 VIDEO_MODELS = {
     "tce_label_objects_u8": _label_objects,
 }
+def _a2d_masks(a):
+    """masks, out, N, h, w, fh, fw, H0, W0: any row of a plane can be a tap (the nearest resize skips none when it up-samples),
+    every output byte is written"""
+    masks, out, N, h, w, fh, fw, H0, W0 = a[:9]
+    return [dense(_p(masks), N * h * w * F)], [dense(_p(out), N * H0 * W0)]
+
+
+def _rle_counts(a):
+    """masks, counts, nruns, ws, P, H, W: every count row is written in full (the counts, then zeros); ws is written by the first
+    launch and read by the second"""
+    masks, counts, nruns, ws, P, H, W = a[:7]
+    wsb = dense(_p(ws), _lib.lib_raw().tce_rle_ws_bytes(P, H, W))
+    return [dense(_p(masks), P * H * W), wsb], [dense(_p(counts), P * (H * W + 1) * 4), dense(_p(nruns), P * 4), wsb]
+
+
+# Entry points of include/tce_rvos_eval.h (_lib.EVAL_SIGNATURES) that launch: consulted after VIDEO_MODELS
+EVAL_MODELS = {
+    "tce_a2d_masks_u8": _a2d_masks,
+    "tce_rle_counts_u32": _rle_counts,
+}
 # Entry points that launch nothing (queries, process switches, graph helpers, tuning aids): passed through.
 NOT_LAUNCHES = {"tce_abi_version", "tce_last_error", "tce_gemm_select_tile", "tce_gemm_select_tile_ex", "tce_set_gemm_mode", "tce_set_gemm_mode_thread",
                 "tce_get_gemm_mode", "tce_set_range_flag", "tce_groupnorm_nsplit", "tce_mha_ws_bytes", "tce_ffn_packed_bytes", "tce_ffn_split_ws_floats", "tce_ffn_split_counters",
                 "tce_ffn_set_wg_cap", "tce_ffn_capped_grid",
                 "tce_rowlin_packed_bytes", "tce_conv3x3_packed_bytes", "tce_conv3x3_split_ws_floats",
                 "tce_conv3x3_split_pieces", "tce_conv3x3_split_kstep", "tce_swin_attn_packed_bytes", "tce_thin_linear_splits", "tce_graph_begin", "tce_graph_end", "tce_graph_launch",
-                "tce_graph_destroy", "tce_graph_group"} | set(_lib.DEBUG_SIGNATURES)
+                "tce_graph_destroy", "tce_graph_group", "tce_rle_ws_bytes"} | set(_lib.DEBUG_SIGNATURES)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -617,7 +637,7 @@ def _site():
     best = "?"
     for fr in traceback.extract_stack(limit=24)[:-3]:
         fn = fr.filename.rsplit("/", 1)[-1]
-        if fn in ("pipeline.py", "text_encoder.py", "model.py", "video.py"):
+        if fn in ("pipeline.py", "text_encoder.py", "model.py", "video.py", "postprocess.py"):
             best = f"{fn}:{fr.lineno} {fr.name}"
     return best
 
@@ -632,7 +652,7 @@ class _LibProxy:
         fn = getattr(self._real, name)
         if name in NOT_LAUNCHES or not name.startswith("tce_"):
             return fn
-        model = MODELS.get(name) or VIDEO_MODELS.get(name)
+        model = MODELS.get(name) or VIDEO_MODELS.get(name) or EVAL_MODELS.get(name)
         if model is None:
             raise RuntimeError(f"hazard checker: no access model for {name} (add one to hazard.MODELS)")
         rec, dry = self._rec, self._dry

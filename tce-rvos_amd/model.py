@@ -1201,4 +1201,5 @@ def build_model(args):
     """models/__init__.py:4-5 -> tce_rvos.build :638-719.  Returns (model, criterion, postprocessors)."""
     cfg = config_from_args(args)
     model = ReferFormer(cfg, args=args)
-    return model, _Stub("SetCriterion"), {"segm": _Stub("PostProcessSegm")}
+    from .postprocess import build_postprocessors  # models/tce_rvos.py:717-719
+    return model, _Stub("SetCriterion"), build_postprocessors(args, getattr(args, "dataset_file", None))

@@ -1011,6 +1011,66 @@ def label_objects(pred_logits, pred_masks, out_hw, threshold=0.5, background=0.1
     return out, best_out
 
 
+def a2d_masks(pred_masks, size, orig_size, threshold=0.5, out=None):
+    """Dataset-size binary masks of one A2D-Sentences / JHMDB-Sentences sample (postprocessors.py:39-47) on the GPU, one launch:
+    pred_masks [N,h,w] (outputs['pred_masks'][b,0]), size = the un-padded model-input size (targets['size']), orig_size = the
+    dataset's frame size -> uint8 [N,H0,W0] of 0/1.  The view's address goes to the launch as it is, so it must be contiguous
+    float32 on the GPU.  out: write into this (any address) instead of a new tensor."""
+    t = pred_masks
+    if not torch.is_tensor(t) or t.dim() != 3:
+        raise ValueError("a2d_masks: pred_masks must be one sample's [N,h,w] tensor")
+    if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
+        raise ValueError(f"a2d_masks: pred_masks must be a contiguous float32 tensor on the GPU, got {t.dtype} on {t.device}, "
+                         f"contiguous={t.is_contiguous()}")
+    N, h, w = (int(s) for s in t.shape)
+    fh, fw = int(size[0]), int(size[1])
+    H0, W0 = int(orig_size[0]), int(orig_size[1])
+    if min(N, h, w, fh, fw, H0, W0) < 1:
+        raise ValueError("a2d_masks: empty extent")
+    if fh > 4 * h or fw > 4 * w:
+        raise ValueError(f"a2d_masks: size {(fh, fw)} exceeds 4x the mask plane {(h, w)}")
+    if N * H0 * W0 >= 2 ** 31 - 4096:
+        raise ValueError("a2d_masks: the output must stay below 2^31 elements")
+    if out is None:
+        out = torch.empty(N, H0, W0, dtype=torch.uint8, device=t.device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (N, H0, W0) or not out.is_contiguous() or out.device != t.device:
+        raise ValueError("a2d_masks: out must be a contiguous uint8 [N,H0,W0] on the input's device")
+    check(lib().tce_a2d_masks_u8(t.data_ptr(), out.data_ptr(), N, h, w, fh, fw, H0, W0, float(threshold), _stream()),
+          "tce_a2d_masks_u8")
+    return out
+
+
+def rle_counts(masks, counts=None, nruns=None, ws=None):
+    """Uncompressed COCO run lengths (cocoapi rleEncode, column-major) of uint8 masks [P,H,W] on the GPU -> (counts uint32-valued
+    int32 [P,H*W+1], nruns int32 [P]): row p holds its nruns[p] counts, zeros behind them.  Two launches, no host read-back."""
+    t = masks
+    if not torch.is_tensor(t) or t.dim() != 3:
+        raise ValueError("rle_counts: masks must be [P,H,W]")
+    if t.dtype != torch.uint8 or not t.is_cuda or not t.is_contiguous():
+        raise ValueError(f"rle_counts: masks must be a contiguous uint8 tensor on the GPU, got {t.dtype} on {t.device}, "
+                         f"contiguous={t.is_contiguous()}")
+    P, H, W = (int(s) for s in t.shape)
+    nbytes = lib().tce_rle_ws_bytes(P, H, W) if min(P, H, W) >= 1 and P <= 65535 else -1
+    if nbytes < 0:
+        raise ValueError(f"rle_counts: unsupported extents {(P, H, W)}")
+    dev = t.device
+    if counts is None:
+        counts = torch.empty(P, H * W + 1, dtype=torch.int32, device=dev)  # torch has no uint32 arithmetic; values are < 2^31
+    elif counts.dtype != torch.int32 or tuple(counts.shape) != (P, H * W + 1) or not counts.is_contiguous() or counts.device != dev:
+        raise ValueError("rle_counts: counts must be a contiguous int32 [P,H*W+1] on the input's device")
+    if nruns is None:
+        nruns = torch.empty(P, dtype=torch.int32, device=dev)
+    elif nruns.dtype != torch.int32 or tuple(nruns.shape) != (P,) or not nruns.is_contiguous() or nruns.device != dev:
+        raise ValueError("rle_counts: nruns must be a contiguous int32 [P] on the input's device")
+    if ws is None:
+        ws = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
+    elif ws.numel() * ws.element_size() < nbytes or ws.data_ptr() % 8 or ws.device != dev:
+        raise ValueError(f"rle_counts: ws must hold {nbytes} bytes on an 8-byte boundary on the input's device")
+    check(lib().tce_rle_counts_u32(t.data_ptr(), counts.data_ptr(), nruns.data_ptr(), ws.data_ptr(), P, H, W, _stream()),
+          "tce_rle_counts_u32")
+    return counts, nruns
+
+
 def ffn_pack(w1, b1, w2, out=None):
     """Packs nn.Linear weights W1 [Hd,C], b1 [Hd], W2 [C,Hd] into the fused-FFN stream (csrc/chain.hip): fp16 hi/lo
     planes in MFMA-fragment order.  Done once per load_state_dict (static weights) or once per clip into an arena
