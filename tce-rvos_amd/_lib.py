@@ -194,6 +194,13 @@ EVAL_SIGNATURES = {
     "tce_rle_counts_u32": (i32, [c_f, c_f, c_f, c_f, i32, i32, i32, c_f]),
 }
 
+# include/tce_rvos_score.h: scoring-stage entry points (the counts behind Ref-DAVIS J&F); must list every symbol of that header
+SCORE_SIGNATURES = {
+    "tce_jf_ws_bytes": (i64, [i32, i32, i32, i32, i32]),  # T, n, H, W, radius
+    # pred [T,H,W] u8, gt [T,H,W] u8, counts [n,T,6] i32, ws, T, n, H, W, radius
+    "tce_jf_counts_i32": (i32, [c_f, c_f, c_f, c_f, i32, i32, i32, i32, i32, c_f]),
+}
+
 _LIB = None
 
 
@@ -215,7 +222,7 @@ def lib():
                           f"launch program runs well with (1-3 crash the runtime, 5-16 double the clip time)", RuntimeWarning)
         l = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(DEBUG_SIGNATURES.items()) + list(VIDEO_SIGNATURES.items()) + \
-                list(EVAL_SIGNATURES.items()):
+                list(EVAL_SIGNATURES.items()) + list(SCORE_SIGNATURES.items()):
             fn = getattr(l, name)  # AttributeError if the symbol is absent
             fn.restype = res
             fn.argtypes = args

@@ -507,13 +507,25 @@ EVAL_MODELS = {
     "tce_a2d_masks_u8": _a2d_masks,
     "tce_rle_counts_u32": _rle_counts,
 }
+def _jf_counts(a):
+    """pred, gt, counts, ws, T, n, H, W, radius: both label stacks are read in full, every word of counts is written; ws is written
+    by the first launch (the tiles' partial sums) and read by the second"""
+    pred, gt, counts, ws, T, n, H, W, radius = a[:9]
+    wsb = dense(_p(ws), _lib.lib_raw().tce_jf_ws_bytes(T, n, H, W, radius))
+    return [dense(_p(pred), T * H * W), dense(_p(gt), T * H * W), wsb], [dense(_p(counts), n * T * 6 * 4), wsb]
+
+
+# Entry points of include/tce_rvos_score.h (_lib.SCORE_SIGNATURES) that launch: consulted after EVAL_MODELS
+SCORE_MODELS = {
+    "tce_jf_counts_i32": _jf_counts,
+}
 # Entry points that launch nothing (queries, process switches, graph helpers, tuning aids): passed through.
 NOT_LAUNCHES = {"tce_abi_version", "tce_last_error", "tce_gemm_select_tile", "tce_gemm_select_tile_ex", "tce_set_gemm_mode", "tce_set_gemm_mode_thread",
                 "tce_get_gemm_mode", "tce_set_range_flag", "tce_groupnorm_nsplit", "tce_mha_ws_bytes", "tce_ffn_packed_bytes", "tce_ffn_split_ws_floats", "tce_ffn_split_counters",
                 "tce_ffn_set_wg_cap", "tce_ffn_capped_grid",
                 "tce_rowlin_packed_bytes", "tce_conv3x3_packed_bytes", "tce_conv3x3_split_ws_floats",
                 "tce_conv3x3_split_pieces", "tce_conv3x3_split_kstep", "tce_swin_attn_packed_bytes", "tce_thin_linear_splits", "tce_graph_begin", "tce_graph_end", "tce_graph_launch",
-                "tce_graph_destroy", "tce_graph_group", "tce_rle_ws_bytes"} | set(_lib.DEBUG_SIGNATURES)
+                "tce_graph_destroy", "tce_graph_group", "tce_rle_ws_bytes", "tce_jf_ws_bytes"} | set(_lib.DEBUG_SIGNATURES)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -637,7 +649,7 @@ def _site():
     best = "?"
     for fr in traceback.extract_stack(limit=24)[:-3]:
         fn = fr.filename.rsplit("/", 1)[-1]
-        if fn in ("pipeline.py", "text_encoder.py", "model.py", "video.py", "postprocess.py"):
+        if fn in ("pipeline.py", "text_encoder.py", "model.py", "video.py", "postprocess.py", "score.py"):
             best = f"{fn}:{fr.lineno} {fr.name}"
     return best
 
@@ -652,7 +664,7 @@ class _LibProxy:
         fn = getattr(self._real, name)
         if name in NOT_LAUNCHES or not name.startswith("tce_"):
             return fn
-        model = MODELS.get(name) or VIDEO_MODELS.get(name) or EVAL_MODELS.get(name)
+        model = MODELS.get(name) or VIDEO_MODELS.get(name) or EVAL_MODELS.get(name) or SCORE_MODELS.get(name)
         if model is None:
             raise RuntimeError(f"hazard checker: no access model for {name} (add one to hazard.MODELS)")
         rec, dry = self._rec, self._dry

@@ -1071,6 +1071,38 @@ def rle_counts(masks, counts=None, nruns=None, ws=None):
     return counts, nruns
 
 
+def jf_counts(pred, gt, n, radius, counts=None, ws=None):
+    """The six counts behind Ref-DAVIS J&F (include/tce_rvos_score.h) of every (object, frame) pair of two uint8 label-map stacks
+    [T,H,W] on the GPU -> int32 [n,T,6]: intersection, union, the two boundary sizes, fg_match, gt_match.  Two launches, no host
+    read-back.  The views' addresses go to the launch as they are (any address), so both must be contiguous."""
+    for name, t in (("pred", pred), ("gt", gt)):
+        if not torch.is_tensor(t) or t.dim() != 3:
+            raise ValueError(f"jf_counts: {name} must be [T,H,W]")
+        if t.dtype != torch.uint8 or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f"jf_counts: {name} must be a contiguous uint8 tensor on the GPU, got {t.dtype} on {t.device}, "
+                             f"contiguous={t.is_contiguous()}")
+    if tuple(pred.shape) != tuple(gt.shape) or pred.device != gt.device:
+        raise ValueError(f"jf_counts: pred {tuple(pred.shape)} on {pred.device} and gt {tuple(gt.shape)} on {gt.device} must have "
+                         f"the same shape and device")
+    T, H, W = (int(s) for s in pred.shape)
+    n, radius = int(n), int(radius)
+    nbytes = lib().tce_jf_ws_bytes(T, n, H, W, radius) if min(T, H, W) >= 1 and T * H * W < 2 ** 31 else -1
+    if nbytes < 0:
+        raise ValueError(f"jf_counts: unsupported extents {(T, H, W)}, n = {n} (1 .. 16) or radius = {radius} (0 .. 40)")
+    dev = pred.device
+    if counts is None:
+        counts = torch.empty(n, T, 6, dtype=torch.int32, device=dev)
+    elif counts.dtype != torch.int32 or tuple(counts.shape) != (n, T, 6) or not counts.is_contiguous() or counts.device != dev:
+        raise ValueError("jf_counts: counts must be a contiguous int32 [n,T,6] on the input's device")
+    if ws is None:
+        ws = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
+    elif ws.numel() * ws.element_size() < nbytes or ws.data_ptr() % 8 or ws.device != dev:
+        raise ValueError(f"jf_counts: ws must hold {nbytes} bytes on an 8-byte boundary on the input's device")
+    check(lib().tce_jf_counts_i32(pred.data_ptr(), gt.data_ptr(), counts.data_ptr(), ws.data_ptr(), T, n, H, W, radius, _stream()),
+          "tce_jf_counts_i32")
+    return counts
+
+
 def ffn_pack(w1, b1, w2, out=None):
     """Packs nn.Linear weights W1 [Hd,C], b1 [Hd], W2 [C,Hd] into the fused-FFN stream (csrc/chain.hip): fp16 hi/lo
     planes in MFMA-fragment order.  Done once per load_state_dict (static weights) or once per clip into an arena
