@@ -65,7 +65,7 @@ class LabelObj(C.Structure):
     _fields_ = [("logits", c_f), ("masks", c_f)]
 
 
-# name -> (restype, argtypes); must list EVERY symbol of include/tce_rvos.h (tests check this)
+# name -> (restype, argtypes), one table per header of include/ (HEADERS): EVERY symbol of its header and no other (tests check this)
 SIGNATURES = {
     "tce_abi_version": (i32, []),
     "tce_last_error": (C.c_char_p, []),
@@ -177,15 +177,13 @@ DEBUG_SIGNATURES = {
     "tce_debug_conv3x3_set_pieces": (i32, [i32]),
 }
 
-# include/tce_rvos_video.h: driver-stage entry points (what the reference's inference drivers do with the outputs of several
-# forwards); must list every symbol of that header
+# include/tce_rvos_video.h: driver-stage entry points (what the reference's inference drivers do with the outputs of several forwards)
 VIDEO_SIGNATURES = {
     # objs (host table), n, labels, best_query, T, Q, K, h, w, H0, W0, threshold, background
     "tce_label_objects_u8": (i32, [C.POINTER(LabelObj), i32, c_f, c_f, i32, i32, i32, i32, i32, i32, i32, f32, f32, c_f]),
 }
 
-# include/tce_rvos_eval.h: evaluation-stage entry points (the A2D-Sentences / JHMDB-Sentences post-processor); must list every
-# symbol of that header
+# include/tce_rvos_eval.h: evaluation-stage entry points (the A2D-Sentences / JHMDB-Sentences post-processor)
 EVAL_SIGNATURES = {
     # masks [N,h,w], out [N,H0,W0], N, h, w, fh, fw, H0, W0, threshold
     "tce_a2d_masks_u8": (i32, [c_f, c_f, i32, i32, i32, i32, i32, i32, i32, f32, c_f]),
@@ -194,12 +192,15 @@ EVAL_SIGNATURES = {
     "tce_rle_counts_u32": (i32, [c_f, c_f, c_f, c_f, i32, i32, i32, c_f]),
 }
 
-# include/tce_rvos_score.h: scoring-stage entry points (the counts behind Ref-DAVIS J&F); must list every symbol of that header
+# include/tce_rvos_score.h: scoring-stage entry points (the counts behind Ref-DAVIS J&F)
 SCORE_SIGNATURES = {
     "tce_jf_ws_bytes": (i64, [i32, i32, i32, i32, i32]),  # T, n, H, W, radius
     # pred [T,H,W] u8, gt [T,H,W] u8, counts [n,T,6] i32, ws, T, n, H, W, radius
     "tce_jf_counts_i32": (i32, [c_f, c_f, c_f, c_f, i32, i32, i32, i32, i32, c_f]),
 }
+
+HEADERS = {"tce_rvos.h": SIGNATURES, "tce_rvos_debug.h": DEBUG_SIGNATURES, "tce_rvos_video.h": VIDEO_SIGNATURES,
+           "tce_rvos_eval.h": EVAL_SIGNATURES, "tce_rvos_score.h": SCORE_SIGNATURES}
 
 _LIB = None
 
@@ -221,11 +222,9 @@ def lib():
             warnings.warn(f"tce_rvos_amd: GPU_MAX_HW_QUEUES={hwq} is set; the HIP runtime's default (4) is the only value this "
                           f"launch program runs well with (1-3 crash the runtime, 5-16 double the clip time)", RuntimeWarning)
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(DEBUG_SIGNATURES.items()) + list(VIDEO_SIGNATURES.items()) + \
-                list(EVAL_SIGNATURES.items()) + list(SCORE_SIGNATURES.items()):
+        for name, (res, args) in [kv for table in HEADERS.values() for kv in table.items()]:
             fn = getattr(l, name)  # AttributeError if the symbol is absent
-            fn.restype = res
-            fn.argtypes = args
+            fn.restype, fn.argtypes = res, args
         _LIB = l
     return _LIB
 

@@ -32,15 +32,16 @@ def _newer(src_list, target):
     return any(os.path.getmtime(s) > t for s in src_list)
 
 
+def dependencies():
+    """Of every object, besides its own source: csrc's headers, every public header, chain.hip (text shared by two translation units)"""
+    return sorted(glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.inc")) +
+                  glob.glob(os.path.join(HERE, "..", "include", "*.h"))) + [os.path.join(CSRC, "chain.hip")]
+
+
 def build(verbose=True, force=False):
     os.makedirs(OBJ, exist_ok=True)
     os.makedirs(LIBDIR, exist_ok=True)
-    # chain.hip is text shared by two translation units (chain_ffn.hip / chain_rowlin.hip): a dependency like a header
-    headers = sorted(glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.inc"))) + [os.path.join(HERE, "..", "include", "tce_rvos.h"),
-                                                             os.path.join(HERE, "..", "include", "tce_rvos_video.h"),
-                                                             os.path.join(HERE, "..", "include", "tce_rvos_eval.h"),
-                                                             os.path.join(HERE, "..", "include", "tce_rvos_score.h"),
-                                                             os.path.join(CSRC, "chain.hip")]
+    headers = dependencies()
     objs, todo = [], []
     for s in SOURCES:
         src = os.path.join(CSRC, s)

@@ -1,46 +1,30 @@
 // Evaluation-stage kernels (include/tce_rvos_eval.h): the A2D-Sentences / JHMDB-Sentences post-processor's dataset-size masks and
 // their uncompressed COCO run lengths.
 #include "common.h"
+#include "mask_planes.h"
 #include "../../include/tce_rvos_eval.h"
 
 namespace {
 
-// postprocessors.py:39-47 per output pixel.  A thread owns the four bytes of one ALIGNED dword of the [N*H0*W0] plane taken as a
-// flat byte string (thread g: bytes 4g - shift .. 4g - shift + 3, shift = the plane's address mod 4), as label_pixels_kernel: only
-// the first and the last dword of the whole plane can be partial, and those go out byte by byte.  The nearest source index is ATen's
-// (one fp32 multiply, floorf, clamp); the tap rule is harness_kernel's at scale 0.25 (weights are multiples of 1/8).
-__global__ void __launch_bounds__(256) a2d_masks_kernel(const float* __restrict__ masks, uint8_t* __restrict__ out, const int h,
-                                                        const int w, const int fh, const int fw, const int H0, const int W0,
-                                                        const int total, const int shift, const float threshold) {
-  const int p0 = (blockIdx.x * 256 + threadIdx.x) * 4 - shift;
+// postprocessors.py:39-47 per output pixel, a byte quad of the [N*H0*W0] output per thread (mask_planes.h).  The nearest source
+// index is ATen's (one fp32 multiply, floorf, clamp); the value there is the resampling rule's at scale 0.25 (weights are multiples
+// of 1/8).
+__global__ void __launch_bounds__(QUAD_THREADS) a2d_masks_kernel(const float* __restrict__ masks, uint8_t* __restrict__ out, const int h,
+                                                                 const int w, const int fh, const int fw, const int H0, const int W0,
+                                                                 const int total, const int shift, const float threshold) {
+  const int p0 = byte_quad_p0(shift);
   if (p0 >= total) return;
   const float sy = (float)fh / (float)H0, sx = (float)fw / (float)W0;
-  const long long hw = (long long)h * w;
+  QuadPixel px[4];
+  byte_quad_pixels(p0, total, H0, W0, px);
   uint32_t bit[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    // pixels outside [0, total) (head of the first dword, tail of the last) take the coordinates of the nearest real one: every
-    // load stays inside the planes, and their bytes are not stored
-    const int c = min(max(p0 + j, 0), total - 1);
-    const int xo = c % W0, r = c / W0;
-    const int yo = r % H0, n = r / H0;
-    const int ys = min((int)floorf((float)yo * sy), fh - 1), xs = min((int)floorf((float)xo * sx), fw - 1);
-    const float fy = fmaxf(0.25f * ((float)ys + 0.5f) - 0.5f, 0.f);
-    const float fx = fmaxf(0.25f * ((float)xs + 0.5f) - 0.5f, 0.f);
-    const int y0 = min((int)fy, h - 1), x0 = min((int)fx, w - 1);
-    const int y1 = y0 + (y0 < h - 1 ? 1 : 0), x1 = x0 + (x0 < w - 1 ? 1 : 0);
-    const float ly = fy - (float)y0, lx = fx - (float)x0, hy = 1.f - ly, hx = 1.f - lx;
-    const float* __restrict__ mp = masks + n * hw;
-    const float v = hy * (hx * mp[y0 * w + x0] + lx * mp[y0 * w + x1]) + ly * (hx * mp[y1 * w + x0] + lx * mp[y1 * w + x1]);
-    bit[j] = 1.f / (1.f + expf(-v)) > threshold ? 1u : 0u;
+    const int ys = min((int)floorf((float)px[j].y * sy), fh - 1), xs = min((int)floorf((float)px[j].x * sx), fw - 1);
+    const float v = mask_tap_value(masks + (long long)px[j].plane * h * w, mask_tap(ys, xs, h, w, 0.25f, 0.25f));
+    bit[j] = mask_sigmoid(v) > threshold ? 1u : 0u;
   }
-  if (p0 >= 0 && p0 + 4 <= total) {
-    *reinterpret_cast<uint32_t*>(out + p0) = bit[0] | (bit[1] << 8) | (bit[2] << 16) | (bit[3] << 24);
-    return;
-  }
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-    if (p0 + j >= 0 && p0 + j < total) out[p0 + j] = (uint8_t)bit[j];
+  byte_quad_store(out, p0, total, bit);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- run lengths
@@ -182,9 +166,9 @@ extern "C" int tce_a2d_masks_u8(const float* masks, uint8_t* out, int32_t N, int
   const long long total = (long long)N * H0 * W0;
   TCE_CHECK_ARG(total < (1ll << 31) - 4096 && (long long)N * h * w < (1ll << 31),
                 "tce_a2d_masks_u8: the output and the mask planes must stay below 2^31 elements");
-  const int shift = (int)((uintptr_t)out & 3u);
-  hipLaunchKernelGGL(a2d_masks_kernel, dim3(tce_cdiv(tce_cdiv(total + shift, 4), 256)), dim3(256), 0, (hipStream_t)stream, masks,
-                     out, h, w, fh, fw, H0, W0, (int)total, shift, threshold);
+  const ByteQuadLaunch ql = byte_quad_launch(out, total);
+  hipLaunchKernelGGL(a2d_masks_kernel, dim3(ql.blocks), dim3(QUAD_THREADS), 0, (hipStream_t)stream, masks, out, h, w, fh, fw, H0, W0,
+                     (int)total, ql.shift, threshold);
   TCE_CHECK_LAUNCH("tce_a2d_masks_u8");
   return TCE_OK;
 }

@@ -1,6 +1,7 @@
 // Small HBM-bound kernels: sine position maps, nearest / bilinear resampling on channels-last maps,
 // elementwise helpers of the decoder, and the dynamic mask head's pack + tail stages.
 #include "common.h"
+#include "mask_planes.h"
 #include "../../include/tce_rvos.h"
 
 namespace {
@@ -161,23 +162,18 @@ __global__ void __launch_bounds__(256) box_refine_kernel(const float* __restrict
 }
 
 // ---- caller harness H (inference_ytvos.py:238-250): best query, bilinear up-sampling, sigmoid, threshold ----
+// (the score and the resampling rule are mask_planes.h's; one byte per thread, the score redone by thread 0 of each workgroup)
 __global__ void __launch_bounds__(256) harness_kernel(const float* __restrict__ logits, const float* __restrict__ masks,
                                                       uint8_t* __restrict__ out, int* __restrict__ best_out, int T,
                                                       int Q, int K, int h, int w, int H0, int W0, float threshold) {
   __shared__ int s_best;
   if (threadIdx.x == 0) {
-    // pred_scores = sigmoid(logits).mean(frames); max over classes; argmax over queries (first maximum wins)
     float best = -1.f;
     int bq = 0;
     for (int q = 0; q < Q; ++q) {
-      float mx = -1.f;
-      for (int k = 0; k < K; ++k) {
-        float sum = 0.f;
-        for (int t = 0; t < T; ++t) sum += 1.f / (1.f + expf(-logits[((long long)t * Q + q) * K + k]));
-        mx = fmaxf(mx, sum / (float)T);
-      }
-      if (mx > best) {
-        best = mx;
+      const float s = mask_query_score(logits, q, T, Q, K);
+      if (s > best) {
+        best = s;
         bq = q;
       }
     }
@@ -185,23 +181,15 @@ __global__ void __launch_bounds__(256) harness_kernel(const float* __restrict__ 
     if (blockIdx.x == 0 && best_out) *best_out = bq;
   }
   __syncthreads();
-  const int bq = s_best;
   const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
   const long long total = (long long)T * H0 * W0;
   if (idx >= total) return;
   const int xo = (int)(idx % W0);
   const int yo = (int)((idx / W0) % H0);
   const int t = (int)(idx / ((long long)W0 * H0));
-  const float sy = (float)h / (float)H0, sx = (float)w / (float)W0;
-  const float fy = fmaxf(sy * ((float)yo + 0.5f) - 0.5f, 0.f);
-  const float fx = fmaxf(sx * ((float)xo + 0.5f) - 0.5f, 0.f);
-  const int y0 = min((int)fy, h - 1), x0 = min((int)fx, w - 1);
-  const int y1 = y0 + (y0 < h - 1 ? 1 : 0), x1 = x0 + (x0 < w - 1 ? 1 : 0);
-  const float ly = fy - (float)y0, lx = fx - (float)x0;
-  const float hy = 1.f - ly, hx = 1.f - lx;
-  const float* m = masks + ((long long)t * Q + bq) * h * w;
-  const float v = hy * (hx * m[y0 * w + x0] + lx * m[y0 * w + x1]) + ly * (hx * m[y1 * w + x0] + lx * m[y1 * w + x1]);
-  out[idx] = (1.f / (1.f + expf(-v)) > threshold) ? 1 : 0;
+  const MaskTap tap = mask_tap(yo, xo, h, w, (float)h / (float)H0, (float)w / (float)W0);
+  const float v = mask_tap_value(masks + ((long long)t * Q + s_best) * h * w, tap);
+  out[idx] = mask_sigmoid(v) > threshold ? 1 : 0;
 }
 
 // ---- dynamic mask head -------------------------------------------------------------------------------

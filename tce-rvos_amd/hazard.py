@@ -9,7 +9,7 @@ checks it statically.
 
   * every C-ABI launch (`lib().tce_*`) is intercepted: the stream it was issued on and -- from the same pointers and sizes
     the kernel receives -- the exact byte ranges it reads and writes (`MODELS`, one access model per entry point of
-    include/tce_rvos.h; an entry point without a model is an error, so coverage cannot rot);
+    the headers of include/ (_lib.HEADERS); an entry point without a model is an error, so coverage cannot rot);
   * every event record / wait (torch's `wait_stream` is `wait_event(record_event())`) and every host synchronisation is
     intercepted and turned into vector clocks: launch A happens-before launch B iff B's clock has seen A's tick;
   * `analyse()` then asserts that any two launches NOT ordered by happens-before touch disjoint memory (write/write and
@@ -329,6 +329,39 @@ def _pos(a, valid):
     return ([dense(_p(add), 2 * Fh * F)] if add else []), [dense(_p(out), T * h * w * 2 * Fh * F)]
 
 
+def _label_objects(a):
+    """objs (host table), n, labels, best_query, T, Q, K, h, w, H0, W0: every object's logits and mask planes are read (any query
+    can be the best one); best_query is written by the first launch and read by the second (the write covers both)"""
+    objs, n, labels, best, T, Q, K, h, w, H0, W0 = a[:11]
+    rd = []
+    for i in range(n):
+        rd += [dense(_p(objs[i].logits), T * Q * K * F), dense(_p(objs[i].masks), T * Q * h * w * F)]
+    return rd, [dense(_p(labels), T * H0 * W0), dense(_p(best), n * 4)]
+
+
+def _a2d_masks(a):
+    """masks, out, N, h, w, fh, fw, H0, W0: any row of a plane can be a tap (the nearest resize skips none when it up-samples),
+    every output byte is written"""
+    masks, out, N, h, w, fh, fw, H0, W0 = a[:9]
+    return [dense(_p(masks), N * h * w * F)], [dense(_p(out), N * H0 * W0)]
+
+
+def _rle_counts(a):
+    """masks, counts, nruns, ws, P, H, W: every count row is written in full (the counts, then zeros); ws is written by the first
+    launch and read by the second"""
+    masks, counts, nruns, ws, P, H, W = a[:7]
+    wsb = dense(_p(ws), _lib.lib_raw().tce_rle_ws_bytes(P, H, W))
+    return [dense(_p(masks), P * H * W), wsb], [dense(_p(counts), P * (H * W + 1) * 4), dense(_p(nruns), P * 4), wsb]
+
+
+def _jf_counts(a):
+    """pred, gt, counts, ws, T, n, H, W, radius: both label stacks are read in full, every word of counts is written; ws is written
+    by the first launch (the tiles' partial sums) and read by the second"""
+    pred, gt, counts, ws, T, n, H, W, radius = a[:9]
+    wsb = dense(_p(ws), _lib.lib_raw().tce_jf_ws_bytes(T, n, H, W, radius))
+    return [dense(_p(pred), T * H * W), dense(_p(gt), T * H * W), wsb], [dense(_p(counts), n * T * 6 * 4), wsb]
+
+
 MODELS = {
     "tce_gemm_f32": lambda a: _gemm(_st(a[0])),
     "tce_gemm_splitk_f32": lambda a: _gemm(_st(a[0]), ws=a[2], splits=a[1]),
@@ -470,55 +503,13 @@ MODELS = {
          dense(_p(a[3]), 3 * a[14] * F), dense(_p(a[4]), a[14] * F), dense(_p(a[5]), 169 * (a[14] // 32) * F),
          dense(_p(a[6]), a[14] * F), dense(_p(a[7]), a[14] * F)],
         [strided(_p(a[9]), a[14] * F, (a[11] * a[12] * a[13], a[10] * F))]),
-}
-
-
-def _label_objects(a):
-    """objs (host table), n, labels, best_query, T, Q, K, h, w, H0, W0: every object's logits and mask planes are read (any query
-    can be the best one); best_query is written by the first launch and read by the second (the write covers both)"""
-    objs, n, labels, best, T, Q, K, h, w, H0, W0 = a[:11]
-    rd = []
-    for i in range(n):
-        rd += [dense(_p(objs[i].logits), T * Q * K * F), dense(_p(objs[i].masks), T * Q * h * w * F)]
-    return rd, [dense(_p(labels), T * H0 * W0), dense(_p(best), n * 4)]
-
-
-# Entry points of include/tce_rvos_video.h (_lib.VIDEO_SIGNATURES): consulted after MODELS
-VIDEO_MODELS = {
     "tce_label_objects_u8": _label_objects,
-}
-def _a2d_masks(a):
-    """masks, out, N, h, w, fh, fw, H0, W0: any row of a plane can be a tap (the nearest resize skips none when it up-samples),
-    every output byte is written"""
-    masks, out, N, h, w, fh, fw, H0, W0 = a[:9]
-    return [dense(_p(masks), N * h * w * F)], [dense(_p(out), N * H0 * W0)]
-
-
-def _rle_counts(a):
-    """masks, counts, nruns, ws, P, H, W: every count row is written in full (the counts, then zeros); ws is written by the first
-    launch and read by the second"""
-    masks, counts, nruns, ws, P, H, W = a[:7]
-    wsb = dense(_p(ws), _lib.lib_raw().tce_rle_ws_bytes(P, H, W))
-    return [dense(_p(masks), P * H * W), wsb], [dense(_p(counts), P * (H * W + 1) * 4), dense(_p(nruns), P * 4), wsb]
-
-
-# Entry points of include/tce_rvos_eval.h (_lib.EVAL_SIGNATURES) that launch: consulted after VIDEO_MODELS
-EVAL_MODELS = {
     "tce_a2d_masks_u8": _a2d_masks,
     "tce_rle_counts_u32": _rle_counts,
-}
-def _jf_counts(a):
-    """pred, gt, counts, ws, T, n, H, W, radius: both label stacks are read in full, every word of counts is written; ws is written
-    by the first launch (the tiles' partial sums) and read by the second"""
-    pred, gt, counts, ws, T, n, H, W, radius = a[:9]
-    wsb = dense(_p(ws), _lib.lib_raw().tce_jf_ws_bytes(T, n, H, W, radius))
-    return [dense(_p(pred), T * H * W), dense(_p(gt), T * H * W), wsb], [dense(_p(counts), n * T * 6 * 4), wsb]
-
-
-# Entry points of include/tce_rvos_score.h (_lib.SCORE_SIGNATURES) that launch: consulted after EVAL_MODELS
-SCORE_MODELS = {
     "tce_jf_counts_i32": _jf_counts,
 }
+
+
 # Entry points that launch nothing (queries, process switches, graph helpers, tuning aids): passed through.
 NOT_LAUNCHES = {"tce_abi_version", "tce_last_error", "tce_gemm_select_tile", "tce_gemm_select_tile_ex", "tce_set_gemm_mode", "tce_set_gemm_mode_thread",
                 "tce_get_gemm_mode", "tce_set_range_flag", "tce_groupnorm_nsplit", "tce_mha_ws_bytes", "tce_ffn_packed_bytes", "tce_ffn_split_ws_floats", "tce_ffn_split_counters",
@@ -664,7 +655,7 @@ class _LibProxy:
         fn = getattr(self._real, name)
         if name in NOT_LAUNCHES or not name.startswith("tce_"):
             return fn
-        model = MODELS.get(name) or VIDEO_MODELS.get(name) or EVAL_MODELS.get(name) or SCORE_MODELS.get(name)
+        model = MODELS.get(name)
         if model is None:
             raise RuntimeError(f"hazard checker: no access model for {name} (add one to hazard.MODELS)")
         rec, dry = self._rec, self._dry

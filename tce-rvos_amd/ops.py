@@ -961,6 +961,24 @@ def select_masks(pred_logits, pred_masks, out_hw, threshold=0.5):
     return out, best
 
 
+def _out_tensor(t, what, dtype, shape, dev):
+    """A caller-supplied output of an output stage (`what` = "op: name ... [dims]", for the message), or a new one."""
+    if t is None:
+        return torch.empty(shape, dtype=dtype, device=dev)
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous() or t.device != dev:
+        raise ValueError(f"{what} must be a contiguous {str(dtype)[6:]} {list(shape)} on the inputs' device")
+    return t
+
+
+def _workspace(t, op, nbytes, dev):
+    """A caller-supplied workspace of an output stage, or a new one: nbytes on an 8-byte boundary."""
+    if t is None:
+        return torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
+    if t.numel() * t.element_size() < nbytes or t.data_ptr() % 8 or t.device != dev:
+        raise ValueError(f"{op}: ws must hold {nbytes} bytes on an 8-byte boundary on the inputs' device")
+    return t
+
+
 LABEL_MAX_OBJS = 16  # TCE_LABEL_MAX_OBJS (include/tce_rvos_video.h)
 
 
@@ -994,14 +1012,8 @@ def label_objects(pred_logits, pred_masks, out_hw, threshold=0.5, background=0.1
     if min(T, Q, K, h, w, H0, W0) < 1:
         raise ValueError("label_objects: empty extent")
     dev = pm[0].device
-    if out is None:
-        out = torch.empty(T, H0, W0, dtype=torch.uint8, device=dev)
-    elif out.dtype != torch.uint8 or tuple(out.shape) != (T, H0, W0) or not out.is_contiguous() or out.device != dev:
-        raise ValueError("label_objects: out must be a contiguous uint8 [T,H0,W0] on the inputs' device")
-    if best_out is None:
-        best_out = torch.empty(n, dtype=torch.int32, device=dev)
-    elif best_out.dtype != torch.int32 or tuple(best_out.shape) != (n,) or not best_out.is_contiguous() or best_out.device != dev:
-        raise ValueError("label_objects: best_out must be a contiguous int32 [n] on the inputs' device")
+    out = _out_tensor(out, "label_objects: out [T,H0,W0]", torch.uint8, (T, H0, W0), dev)
+    best_out = _out_tensor(best_out, "label_objects: best_out [n]", torch.int32, (n,), dev)
     from ._lib import LabelObj
     table = (LabelObj * n)()  # read by the entry point on the host, at this call
     for k in range(n):
@@ -1031,10 +1043,7 @@ def a2d_masks(pred_masks, size, orig_size, threshold=0.5, out=None):
         raise ValueError(f"a2d_masks: size {(fh, fw)} exceeds 4x the mask plane {(h, w)}")
     if N * H0 * W0 >= 2 ** 31 - 4096:
         raise ValueError("a2d_masks: the output must stay below 2^31 elements")
-    if out is None:
-        out = torch.empty(N, H0, W0, dtype=torch.uint8, device=t.device)
-    elif out.dtype != torch.uint8 or tuple(out.shape) != (N, H0, W0) or not out.is_contiguous() or out.device != t.device:
-        raise ValueError("a2d_masks: out must be a contiguous uint8 [N,H0,W0] on the input's device")
+    out = _out_tensor(out, "a2d_masks: out [N,H0,W0]", torch.uint8, (N, H0, W0), t.device)
     check(lib().tce_a2d_masks_u8(t.data_ptr(), out.data_ptr(), N, h, w, fh, fw, H0, W0, float(threshold), _stream()),
           "tce_a2d_masks_u8")
     return out
@@ -1054,18 +1063,9 @@ def rle_counts(masks, counts=None, nruns=None, ws=None):
     if nbytes < 0:
         raise ValueError(f"rle_counts: unsupported extents {(P, H, W)}")
     dev = t.device
-    if counts is None:
-        counts = torch.empty(P, H * W + 1, dtype=torch.int32, device=dev)  # torch has no uint32 arithmetic; values are < 2^31
-    elif counts.dtype != torch.int32 or tuple(counts.shape) != (P, H * W + 1) or not counts.is_contiguous() or counts.device != dev:
-        raise ValueError("rle_counts: counts must be a contiguous int32 [P,H*W+1] on the input's device")
-    if nruns is None:
-        nruns = torch.empty(P, dtype=torch.int32, device=dev)
-    elif nruns.dtype != torch.int32 or tuple(nruns.shape) != (P,) or not nruns.is_contiguous() or nruns.device != dev:
-        raise ValueError("rle_counts: nruns must be a contiguous int32 [P] on the input's device")
-    if ws is None:
-        ws = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
-    elif ws.numel() * ws.element_size() < nbytes or ws.data_ptr() % 8 or ws.device != dev:
-        raise ValueError(f"rle_counts: ws must hold {nbytes} bytes on an 8-byte boundary on the input's device")
+    counts = _out_tensor(counts, "rle_counts: counts [P,H*W+1]", torch.int32, (P, H * W + 1), dev)  # no uint32 arithmetic in torch
+    nruns = _out_tensor(nruns, "rle_counts: nruns [P]", torch.int32, (P,), dev)
+    ws = _workspace(ws, "rle_counts", nbytes, dev)
     check(lib().tce_rle_counts_u32(t.data_ptr(), counts.data_ptr(), nruns.data_ptr(), ws.data_ptr(), P, H, W, _stream()),
           "tce_rle_counts_u32")
     return counts, nruns
@@ -1090,14 +1090,8 @@ def jf_counts(pred, gt, n, radius, counts=None, ws=None):
     if nbytes < 0:
         raise ValueError(f"jf_counts: unsupported extents {(T, H, W)}, n = {n} (1 .. 16) or radius = {radius} (0 .. 40)")
     dev = pred.device
-    if counts is None:
-        counts = torch.empty(n, T, 6, dtype=torch.int32, device=dev)
-    elif counts.dtype != torch.int32 or tuple(counts.shape) != (n, T, 6) or not counts.is_contiguous() or counts.device != dev:
-        raise ValueError("jf_counts: counts must be a contiguous int32 [n,T,6] on the input's device")
-    if ws is None:
-        ws = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
-    elif ws.numel() * ws.element_size() < nbytes or ws.data_ptr() % 8 or ws.device != dev:
-        raise ValueError(f"jf_counts: ws must hold {nbytes} bytes on an 8-byte boundary on the input's device")
+    counts = _out_tensor(counts, "jf_counts: counts [n,T,6]", torch.int32, (n, T, 6), dev)
+    ws = _workspace(ws, "jf_counts", nbytes, dev)
     check(lib().tce_jf_counts_i32(pred.data_ptr(), gt.data_ptr(), counts.data_ptr(), ws.data_ptr(), T, n, H, W, radius, _stream()),
           "tce_jf_counts_i32")
     return counts

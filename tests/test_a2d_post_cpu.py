@@ -1,11 +1,9 @@
-"""The A2D-Sentences / JHMDB-Sentences post-processor, the parts that need no GPU: the evaluation-stage header against its binding
-table, the exported symbols and the access models; the two access models on hand-made argument blocks; rle_to_string against the
-plain-loop restatement of cocoapi (tests/_a2d.py), the issue's check values and the committed fixture; build_postprocessors; the
-argument checks of ops.a2d_masks / ops.rle_counts."""
+"""The A2D-Sentences / JHMDB-Sentences post-processor, the parts that need no GPU (the evaluation-stage header against its binding
+table, the exported symbols and the access models: tests/test_host_cpu.py, with every other header): the two access models on
+hand-made argument blocks; rle_to_string against the plain-loop restatement of cocoapi (tests/_a2d.py), the issue's check values
+and the committed fixture; build_postprocessors; the argument checks of ops.a2d_masks / ops.rle_counts."""
 import argparse
-import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
@@ -17,30 +15,6 @@ from tce_rvos_amd.postprocess import A2DSentencesPostProcess, build_postprocesso
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIXTURE = os.path.join(ROOT, "tests", "golden", "a2d_post_cases.npz")
-
-
-def test_eval_header_symbols_bound_exported_and_modelled():
-    from tce_rvos_amd import build as b
-    hdr = open(os.path.join(ROOT, "include", "tce_rvos_eval.h")).read()
-    declared = set(re.findall(r"\b(tce_[a-z0-9_]+)\s*\(", hdr))
-    assert declared == set(_lib.EVAL_SIGNATURES) == {"tce_a2d_masks_u8", "tce_rle_ws_bytes", "tce_rle_counts_u32"}, declared ^ set(_lib.EVAL_SIGNATURES)
-    assert set(hazard.EVAL_MODELS) | {"tce_rle_ws_bytes"} == declared and "tce_rle_ws_bytes" not in hazard.EVAL_MODELS
-    assert "tce_rle_ws_bytes" in hazard.NOT_LAUNCHES
-    for other in (_lib.SIGNATURES, _lib.DEBUG_SIGNATURES, _lib.VIDEO_SIGNATURES, hazard.MODELS, hazard.VIDEO_MODELS):
-        assert not (declared & set(other))
-    assert not (set(hazard.EVAL_MODELS) & hazard.NOT_LAUNCHES)
-    for name in ("tce_rvos.h", "tce_rvos_video.h", "tce_rvos_debug.h"):
-        other = open(os.path.join(ROOT, "include", name)).read()
-        assert not (declared & set(re.findall(r"\b(tce_[a-z0-9_]+)\s*\(", other))), name
-    l = ctypes.CDLL(b.build(verbose=False))
-    for name in declared:
-        assert hasattr(l, name), name
-    for name, (res, args) in _lib.EVAL_SIGNATURES.items():  # lib() applies the table
-        fn = getattr(_lib.lib(), name)
-        assert fn.restype is res and list(fn.argtypes) == args, name
-    assert _lib.lib().tce_abi_version() == 5
-    assert '"tce_rvos_eval.h"' in open(os.path.join(ROOT, "tce-rvos_amd", "build.py")).read()  # a dependency of every object
-    assert "eval.hip" in b.SOURCES
 
 
 def test_rle_ws_bytes_and_host_side_rejections_need_no_device():
@@ -70,14 +44,14 @@ def test_rle_ws_bytes_and_host_side_rejections_need_no_device():
 def test_access_models_on_hand_made_blocks():
     N, h, w, fh, fw, H0, W0 = 5, 18, 25, 72, 100, 111, 151
     masks, out = 0x100000, 0x900003  # out on an odd address
-    rd, wr = hazard.EVAL_MODELS["tce_a2d_masks_u8"]((masks, out, N, h, w, fh, fw, H0, W0, 0.5, 0))
+    rd, wr = hazard.MODELS["tce_a2d_masks_u8"]((masks, out, N, h, w, fh, fw, H0, W0, 0.5, 0))
     assert hazard.union(*rd).tolist() == [[masks, masks + N * h * w * 4]]
     assert hazard.union(*wr).tolist() == [[out, out + N * H0 * W0]]
     P, H, W = 3, 87, 145
     m, counts, nruns, ws = 0x200001, 0x400000, 0x800000, 0xA00000  # masks on an odd address
     wsb = _lib.lib().tce_rle_ws_bytes(P, H, W)
     assert wsb == P * -(-H * W // 1024) * 8
-    rd, wr = hazard.EVAL_MODELS["tce_rle_counts_u32"]((m, counts, nruns, ws, P, H, W, 0))
+    rd, wr = hazard.MODELS["tce_rle_counts_u32"]((m, counts, nruns, ws, P, H, W, 0))
     assert hazard.union(*rd).tolist() == [[m, m + P * H * W], [ws, ws + wsb]]
     assert hazard.union(*wr).tolist() == [[counts, counts + P * (H * W + 1) * 4], [nruns, nruns + 4 * P], [ws, ws + wsb]]
 

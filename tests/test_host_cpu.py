@@ -18,19 +18,48 @@ def built_lib():
     return b.build(verbose=False)
 
 
-def test_header_symbols_all_exported_and_bound(built_lib):
-    hdr = open(os.path.join(ROOT, "include", "tce_rvos.h")).read()
-    declared = set(re.findall(r"\b(tce_[a-z0-9_]+)\s*\(", hdr))
-    from tce_rvos_amd import _lib
-    assert declared == set(_lib.SIGNATURES), (declared ^ set(_lib.SIGNATURES))
-    dbg = open(os.path.join(ROOT, "include", "tce_rvos_debug.h")).read()
-    declared_dbg = set(re.findall(r"\b(tce_[a-z0-9_]+)\s*\(", dbg))
-    assert declared_dbg == set(_lib.DEBUG_SIGNATURES), (declared_dbg ^ set(_lib.DEBUG_SIGNATURES))
-    assert not (declared & declared_dbg)
-    l = ctypes.CDLL(built_lib)
-    for name in declared | declared_dbg:
+def _declared(header):
+    return set(re.findall(r"\b(tce_[a-z0-9_]+)\s*\(", open(os.path.join(ROOT, "include", header)).read()))
+
+
+# header, its symbols spelled out (None: its table is the record), those of them that launch nothing (None: not spelled out; "all":
+# every one), its translation unit (None: several)
+HEADER_CASES = [
+    ("tce_rvos.h", None, None, None),
+    ("tce_rvos_debug.h", None, "all", None),
+    ("tce_rvos_video.h", {"tce_label_objects_u8"}, set(), "label.hip"),
+    ("tce_rvos_eval.h", {"tce_a2d_masks_u8", "tce_rle_ws_bytes", "tce_rle_counts_u32"}, {"tce_rle_ws_bytes"}, "eval.hip"),
+    ("tce_rvos_score.h", {"tce_jf_ws_bytes", "tce_jf_counts_i32"}, {"tce_jf_ws_bytes"}, "score.hip"),
+]
+
+
+@pytest.mark.parametrize("header,symbols,launch_free,source", HEADER_CASES, ids=[c[0] for c in HEADER_CASES])
+def test_header_symbols_bound_exported_and_modelled(built_lib, header, symbols, launch_free, source):
+    """Every header of include/ against its binding table (_lib.HEADERS), the built library and the hazard checker's tables."""
+    from tce_rvos_amd import _lib, hazard
+    from tce_rvos_amd import build as b
+    assert [c[0] for c in HEADER_CASES] == list(_lib.HEADERS) and set(os.listdir(os.path.join(ROOT, "include"))) == set(_lib.HEADERS)
+    table, declared = _lib.HEADERS[header], _declared(header)
+    assert declared == set(table), declared ^ set(table)
+    assert symbols is None or declared == symbols
+    for other, other_table in _lib.HEADERS.items():  # a symbol lives in one header and in one table
+        if other != header:
+            assert not (declared & set(other_table)) and not (declared & _declared(other)), other
+    l, bound = ctypes.CDLL(built_lib), _lib.lib()  # lib() applies the tables
+    for name, (res, args) in table.items():
         assert hasattr(l, name), name
-    assert _lib.lib().tce_abi_version() == 5
+        fn = getattr(bound, name)
+        assert fn.restype is res and list(fn.argtypes) == args, name
+    assert bound.tce_abi_version() == 5
+    # modelled or declared launch-free, never both; the checker's tables hold nothing else
+    modelled, free = declared & set(hazard.MODELS), declared & hazard.NOT_LAUNCHES
+    assert modelled | free == declared and not (modelled & free), declared - modelled - free
+    assert launch_free is None or free == (declared if launch_free == "all" else launch_free)
+    every = set().union(*_lib.HEADERS.values())
+    assert set(hazard.MODELS) <= every and hazard.NOT_LAUNCHES <= every
+    # every object is rebuilt when the header changes, and the stage's translation unit is built
+    assert os.path.realpath(os.path.join(ROOT, "include", header)) in {os.path.realpath(d) for d in b.dependencies()}
+    assert source is None or source in b.SOURCES
 
 
 def test_bad_arguments_are_rejected_with_a_message(built_lib):

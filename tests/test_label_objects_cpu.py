@@ -1,9 +1,8 @@
-"""Ref-DAVIS label maps, the parts that need no GPU: the driver-stage header against its binding table, the exported symbols and
-the access models; the access model of tce_label_objects_u8 on a hand-made argument block; the annotator sets and the forward plan
-of run_video_objects; the committed fixture's contested-share cap; the argument checks of ops.label_objects."""
-import ctypes
+"""Ref-DAVIS label maps, the parts that need no GPU (the driver-stage header against its binding table, the exported symbols and
+the access models: tests/test_host_cpu.py, with every other header): the access model of tce_label_objects_u8 on a hand-made
+argument block; the annotator sets and the forward plan of run_video_objects; the committed fixture's contested-share cap; the
+argument checks of ops.label_objects."""
 import os
-import re
 
 import numpy as np
 import pytest
@@ -14,25 +13,6 @@ from tce_rvos_amd import _lib, hazard, video
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIXTURE = os.path.join(ROOT, "tests", "golden", "davis_label_cases.npz")
-
-
-def test_video_header_symbols_bound_exported_and_modelled():
-    from tce_rvos_amd import build as b
-    hdr = open(os.path.join(ROOT, "include", "tce_rvos_video.h")).read()
-    declared = set(re.findall(r"\b(tce_[a-z0-9_]+)\s*\(", hdr))
-    assert declared == set(_lib.VIDEO_SIGNATURES) == {"tce_label_objects_u8"}, declared ^ set(_lib.VIDEO_SIGNATURES)
-    assert set(hazard.VIDEO_MODELS) == declared  # every driver-stage entry launches, and is modelled
-    for other in (_lib.SIGNATURES, _lib.DEBUG_SIGNATURES, hazard.MODELS, hazard.NOT_LAUNCHES):
-        assert not (declared & set(other))
-    main = open(os.path.join(ROOT, "include", "tce_rvos.h")).read()
-    assert not (declared & set(re.findall(r"\b(tce_[a-z0-9_]+)\s*\(", main)))
-    l = ctypes.CDLL(b.LIB)
-    for name in declared:
-        assert hasattr(l, name), name
-    fn = getattr(_lib.lib(), "tce_label_objects_u8")  # lib() applies the table
-    assert fn.restype is _lib.i32 and list(fn.argtypes) == _lib.VIDEO_SIGNATURES["tce_label_objects_u8"][1]
-    assert '"tce_rvos_video.h"' in open(os.path.join(ROOT, "tce-rvos_amd", "build.py")).read()  # a dependency of every object
-    assert "label.hip" in b.SOURCES
 
 
 def _table(ptrs):
@@ -46,13 +26,13 @@ def test_label_objects_access_model_on_a_hand_made_block():
     n, T, Q, K, h, w, H0, W0 = 3, 4, 5, 2, 6, 7, 25, 31
     ptrs = [(0x100000 * (k + 1), 0x100000 * (k + 1) + 0x40000) for k in (2, 0, 1)]  # table order != address order
     labels, best = 0x900003, 0xA00000  # labels on an odd address
-    rd, wr = hazard.VIDEO_MODELS["tce_label_objects_u8"]((_table(ptrs), n, labels, best, T, Q, K, h, w, H0, W0, 0.5, 0.1, 0))
+    rd, wr = hazard.MODELS["tce_label_objects_u8"]((_table(ptrs), n, labels, best, T, Q, K, h, w, H0, W0, 0.5, 0.1, 0))
     want_rd = sorted([[lg, lg + T * Q * K * 4] for lg, _ in ptrs] + [[pm, pm + T * Q * h * w * 4] for _, pm in ptrs])
     assert hazard.union(*rd).tolist() == want_rd
     assert hazard.union(*wr).tolist() == [[labels, labels + T * H0 * W0], [best, best + 4 * n]]
     assert len(rd) == 2 * n
     # n = 1: one logits and one masks block, 4 bytes of best_query
-    rd, wr = hazard.VIDEO_MODELS["tce_label_objects_u8"]((_table(ptrs[:1]), 1, labels, best, T, Q, K, h, w, H0, W0, 0.5, 0.1, 0))
+    rd, wr = hazard.MODELS["tce_label_objects_u8"]((_table(ptrs[:1]), 1, labels, best, T, Q, K, h, w, H0, W0, 0.5, 0.1, 0))
     assert len(rd) == 2 and hazard.union(*wr).tolist() == [[labels, labels + T * H0 * W0], [best, best + 4]]
 
 
