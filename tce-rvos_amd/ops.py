@@ -1097,6 +1097,63 @@ def jf_counts(pred, gt, n, radius, counts=None, ws=None):
     return counts
 
 
+def rle_decode(counts, nruns, hw, out=None, ws=None):
+    """Planes of P run-length masks on the GPU (csrc/tce_rvos_a2d_score.h: cocoapi rleDecode, the inverse of rle_counts):
+    counts int32 [P,stride] (uint32-valued, as rle_counts leaves them; any stride >= 1), nruns int32 [P], hw = (H, W) -> uint8
+    [P,H,W] of 0/1.  Three launches, no host read-back: nruns is read on the device.  out: write into this (any address, e.g. a
+    slice of a slab) instead of a new tensor."""
+    from ._lib import lib_raw
+    for name, t, dims in (("counts", counts, 2), ("nruns", nruns, 1)):
+        if not torch.is_tensor(t) or t.dim() != dims:
+            raise ValueError(f"rle_decode: {name} must be {'[P,stride]' if dims == 2 else '[P]'}")
+        if t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f"rle_decode: {name} must be a contiguous int32 tensor on the GPU, got {t.dtype} on {t.device}, "
+                             f"contiguous={t.is_contiguous()}")
+    P, stride = (int(s) for s in counts.shape)
+    if int(nruns.shape[0]) != P or nruns.device != counts.device:
+        raise ValueError(f"rle_decode: counts {tuple(counts.shape)} on {counts.device} and nruns {tuple(nruns.shape)} on "
+                         f"{nruns.device} must agree in P and device")
+    H, W = int(hw[0]), int(hw[1])
+    # the *_ws_bytes queries launch nothing: asked of the library itself, so that a recording (hazard.py) meets the launching entry
+    nbytes = lib_raw().tce_rle_decode_ws_bytes(P, H, W, stride) if min(P, H, W, stride) >= 1 and H * W < 2 ** 31 else -1
+    if nbytes < 0:
+        raise ValueError(f"rle_decode: unsupported extents P = {P} (1 .. 65535), (H, W) = {(H, W)} (below 2^31 - 4096 pixels), "
+                         f"stride = {stride}")
+    dev = counts.device
+    out = _out_tensor(out, "rle_decode: out [P,H,W]", torch.uint8, (P, H, W), dev)
+    ws = _workspace(ws, "rle_decode", nbytes, dev)
+    check(lib().tce_rle_decode_u8(counts.data_ptr(), nruns.data_ptr(), out.data_ptr(), ws.data_ptr(), P, H, W, stride, _stream()),
+          "tce_rle_decode_u8")
+    return out
+
+
+def mask_overlap(pred, gt, counts=None, ws=None):
+    """Overlap counts of N uint8 prediction planes [N,H,W] against one ground-truth plane [H,W] on the GPU
+    (csrc/tce_rvos_a2d_score.h) -> int32 [N,3]: per prediction (intersection, prediction area, ground-truth area), any nonzero
+    byte counting as set.  Two launches, no host read-back.  The views' addresses go to the launch as they are (any address), so
+    both must be contiguous.  counts: write into this (e.g. a slice of a slab) instead of a new tensor."""
+    from ._lib import lib_raw
+    for name, t, dims in (("pred", pred, 3), ("gt", gt, 2)):
+        if not torch.is_tensor(t) or t.dim() != dims:
+            raise ValueError(f"mask_overlap: {name} must be {'[N,H,W]' if dims == 3 else '[H,W]'}")
+        if t.dtype != torch.uint8 or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f"mask_overlap: {name} must be a contiguous uint8 tensor on the GPU, got {t.dtype} on {t.device}, "
+                             f"contiguous={t.is_contiguous()}")
+    if tuple(pred.shape[1:]) != tuple(gt.shape) or pred.device != gt.device:
+        raise ValueError(f"mask_overlap: pred {tuple(pred.shape)} on {pred.device} and gt {tuple(gt.shape)} on {gt.device} must "
+                         f"have the same plane and device")
+    N, H, W = (int(s) for s in pred.shape)
+    nbytes = lib_raw().tce_mask_overlap_ws_bytes(N, H, W) if min(N, H, W) >= 1 and H * W < 2 ** 31 else -1
+    if nbytes < 0:
+        raise ValueError(f"mask_overlap: unsupported extents N = {N} (1 .. 65535), (H, W) = {(H, W)} (below 2^31 - 4096 pixels)")
+    dev = pred.device
+    counts = _out_tensor(counts, "mask_overlap: counts [N,3]", torch.int32, (N, 3), dev)
+    ws = _workspace(ws, "mask_overlap", nbytes, dev)
+    check(lib().tce_mask_overlap_i32(pred.data_ptr(), gt.data_ptr(), counts.data_ptr(), ws.data_ptr(), N, H, W, _stream()),
+          "tce_mask_overlap_i32")
+    return counts
+
+
 def ffn_pack(w1, b1, w2, out=None):
     """Packs nn.Linear weights W1 [Hd,C], b1 [Hd], W2 [C,Hd] into the fused-FFN stream (csrc/chain.hip): fp16 hi/lo
     planes in MFMA-fragment order.  Done once per load_state_dict (static weights) or once per clip into an arena

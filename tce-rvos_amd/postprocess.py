@@ -69,11 +69,14 @@ class A2DSentencesPostProcess(nn.Module):
     Like the reference class it binarises at 0.5 whatever `threshold` it was built with (postprocessors.py:40 hard-codes 0.5);
     the attribute is kept because callers set and read it.
     Per sample one masks launch and one run-length call over the N queries; per call one read-back of the run counts, then one of
-    the used run lengths.  The float masks never leave the GPU."""
+    the used run lengths.  The float masks never leave the GPU.
+    rle=False: no run-length launches, no read-back and no 'rle_masks' key -- for a caller that scores `masks` on the device
+    (a2d_score.A2DScorer.update) and needs no strings."""
 
-    def __init__(self, threshold=0.5):
+    def __init__(self, threshold=0.5, rle=True):
         super().__init__()
         self.threshold = threshold
+        self.rle = rle
 
     @torch.no_grad()
     def forward(self, outputs, orig_target_sizes, max_target_sizes):
@@ -85,8 +88,10 @@ class A2DSentencesPostProcess(nn.Module):
         for (lg, pm), sz, og in zip(samples, size, orig):
             scores = ops.sigmoid(lg.to(torch.float32).contiguous())
             masks = ops.a2d_masks(pm.to(torch.float32).contiguous(), sz, og, threshold=0.5)
-            counts, nruns = ops.rle_counts(masks)
+            counts, nruns = ops.rle_counts(masks) if self.rle else (None, None)
             held.append((scores, masks, counts, nruns))
+        if not self.rle:
+            return [{"scores": scores, "masks": masks.unsqueeze(1)} for scores, masks, _, _ in held]
         nruns = torch.cat([h[3] for h in held]).cpu().tolist()               # read-back 1: B*N integers
         k, used = 0, []
         for _, _, counts, nr in held:
