@@ -216,6 +216,17 @@ STAGED_SIGNATURES = {
     "tce_mask_overlap_i32": (i32, [c_f, c_f, c_f, c_f, i32, i32, i32, c_f]),
 }
 
+# csrc/tce_rvos_png.h: PNG-writing stage entry points (the zlib stream of every output plane), staged beside the table above for the
+# same reasons and on the same terms: bound by lib() after it, outside HEADERS, no access model, refused by hazard._LibProxy
+# (tests/test_png_cpu.py holds this table to its header).
+PNG_HEADER = os.path.join(HERE, "csrc", "tce_rvos_png.h")
+PNG_SIGNATURES = {
+    "tce_png_stream_bound": (i64, [i32, i32, i32]),  # H, W, rows_per_strip
+    "tce_png_ws_bytes": (i64, [i32, i32, i32, i32]),  # P, H, W, rows_per_strip
+    # planes [P,H,W] u8, streams [P,bound] u8, nbytes [P] i32, ws, P, H, W, rows_per_strip, nonzero_value
+    "tce_png_deflate_u8": (i32, [c_f, c_f, c_f, c_f, i32, i32, i32, i32, i32, c_f]),
+}
+
 _LIB = None
 
 
@@ -236,7 +247,7 @@ def lib():
             warnings.warn(f"tce_rvos_amd: GPU_MAX_HW_QUEUES={hwq} is set; the HIP runtime's default (4) is the only value this "
                           f"launch program runs well with (1-3 crash the runtime, 5-16 double the clip time)", RuntimeWarning)
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in [kv for table in list(HEADERS.values()) + [STAGED_SIGNATURES] for kv in table.items()]:
+        for name, (res, args) in [kv for table in list(HEADERS.values()) + [STAGED_SIGNATURES, PNG_SIGNATURES] for kv in table.items()]:
             fn = getattr(l, name)  # AttributeError if the symbol is absent
             fn.restype, fn.argtypes = res, args
         _LIB = l

@@ -1,0 +1,460 @@
+// PNG-writing stage kernels (csrc/tce_rvos_png.h): the zlib stream of every uint8 output plane -- filter bytes, RLE-only deflate with
+// the fixed Huffman code, Adler-32 -- in three launches.  Byte and bit kernels: bound by LDS traffic and barriers, not by arithmetic.
+#include "common.h"
+#include "tce_rvos_png.h"
+
+namespace {
+
+constexpr int PT = 256, PWAVES = PT / 64, PER = 8;  // a thread owns PER consecutive filtered bytes of a pass
+static_assert(PT * PER == TCE_PNG_PASS, "pass length");
+constexpr int REP = 4;                 // matches of length 258 per thread and sub-pass of a long run
+constexpr int MATCH258_BITS = 13;      // symbol 285 (8 bits, 0xC5 -> 0xA3 least significant bit first) + distance code 0 (5 bits)
+constexpr uint32_t MATCH258 = 0xA3u;
+// The bit window.  It holds the bits behind the last whole dword flushed: at most 31 of them, the block header (3), head and tail of
+// a carried run (9 + 36), and then EITHER the runs that lie inside a pass (at most 9 bits a byte: 18432) OR a sub-pass of
+// PT * REP matches of length 258 (13312) OR the strip's end (7 + 3 + 7 + 32): below 18600 bits = 582 dwords.
+constexpr int WIN_DW = 640;
+static_assert(31 + 3 + 45 + 9 * TCE_PNG_PASS + 64 < 32 * (WIN_DW - 1) && 31 + 45 + PT * REP * MATCH258_BITS + 64 < 32 * (WIN_DW - 1), "window");
+constexpr uint32_t ADLER = 65521u;
+
+struct Tok {
+  uint32_t v;  // the bits, first bit of the stream in bit 0
+  int n;
+};
+
+// a Huffman code goes in most significant bit first
+__device__ __forceinline__ uint32_t huff(const uint32_t code, const int n) { return __brev(code) >> (32 - n); }
+
+__device__ __forceinline__ Tok lit_tok(const uint32_t b) {
+  return b < 144u ? Tok{huff(0x30u + b, 8), 8} : Tok{huff(0x190u + (b - 144u), 9), 9};
+}
+
+// a match of length 3 .. 258 at distance 1: length symbol 257 + i of the largest base <= len (258: always i = 28), its extra bits
+// least significant first, five zero bits of distance code 0.  Bases: 3 .. 10 one apart; from 11 on, four codes per extra-bit count
+// e >= 1, spaced 2^e: with l = len - 3 >= 8, e = floor(log2 l) - 2 and the code within its group of four is (l >> e) & 3.
+__device__ __forceinline__ Tok match_tok(const int len) {
+  int i, e = 0;
+  uint32_t x = 0u;
+  if (len == 258) {
+    i = 28;
+  } else if (len < 11) {
+    i = len - 3;
+  } else {
+    const int l = len - 3;
+    e = 29 - __clz(l);
+    i = 4 * e + 4 + ((l >> e) & 3);
+    x = (uint32_t)l & ((1u << e) - 1u);
+  }
+  const int n = i < 23 ? 7 : 8;  // symbols 256 .. 279: 7 bits, x - 256; 280 .. 287: 8 bits, 0xC0 + (x - 280)
+  const uint32_t code = i < 23 ? (uint32_t)(i + 1) : 0xC0u + (uint32_t)(i - 23);
+  return Tok{huff(code, n) | (x << n), n + e + 5};
+}
+
+// what follows the matches of length 258 of a run of byte b: r < 261, r != 258 more bytes
+template <class F>
+__device__ __forceinline__ void run_tail(const uint32_t b, int r, F&& f) {
+  if (r == 259 || r == 260) {
+    f(match_tok(r - 3));
+    r = 3;
+  }
+  if (r >= 3) {
+    f(match_tok(r));
+  } else {
+    for (int k = 0; k < r; ++k) f(lit_tok(b));
+  }
+}
+
+// every token of a run of L >= 1 bytes b (a run inside a pass: L <= TCE_PNG_PASS, a handful of tokens)
+template <class F>
+__device__ __forceinline__ void run_tokens(const uint32_t b, const int L, F&& f) {
+  f(lit_tok(b));
+  int r = L - 1;
+  while (r >= 261 || r == 258) {
+    f(Tok{MATCH258, MATCH258_BITS});
+    r -= 258;
+  }
+  run_tail(b, r, f);
+}
+
+// ORs a token into the window at bit `at`: LDS atomics, so tokens of different threads may share a dword
+__device__ __forceinline__ void put(uint32_t* win, const int at, const Tok t) {
+  const unsigned long long v = (unsigned long long)t.v << (at & 31);
+  if ((uint32_t)v) atomicOr(&win[at >> 5], (uint32_t)v);
+  if ((uint32_t)(v >> 32)) atomicOr(&win[(at >> 5) + 1], (uint32_t)(v >> 32));
+}
+
+// the window's whole dwords go to the strip's workspace, the bits behind them (wb & 31) to the window's start.  Every thread calls it.
+__device__ __forceinline__ void flush(uint32_t* win, uint32_t* __restrict__ out, long long& flushed, int& wb) {
+  __syncthreads();  // every token is in
+  const int nfull = wb >> 5;
+  for (int i = threadIdx.x; i < nfull; i += PT) out[flushed + i] = win[i];
+  const uint32_t part = win[nfull];
+  __syncthreads();
+  for (int i = threadIdx.x; i <= nfull; i += PT) win[i] = i == 0 ? part : 0u;
+  __syncthreads();
+  flushed += nfull;
+  wb &= 31;
+}
+
+// A run that began in an earlier pass (or the strip's last run), of any length: the whole workgroup writes it.  b, L, wb, flushed
+// are the same in every thread.  Thread 0 puts the literal and the tail; the matches of length 258 between them, one 13-bit
+// pattern M times, go in sub-passes of PT * REP, the window flushed after each.
+__device__ __forceinline__ void long_run(uint32_t* win, uint32_t* __restrict__ out, long long& flushed, int& wb, const uint32_t b,
+                                         const int L) {
+  const int r0 = L - 1;
+  int M = 0, r = r0;
+  if (r0 >= 258) {  // the loop "while r >= 261 or r == 258" in closed form: its last step leaves r0 % 258, legal unless that is 1 or 2
+    const int q = r0 / 258, m = r0 - q * 258;
+    M = (m == 0 || m >= 3) ? q : q - 1;
+    r = r0 - 258 * M;
+  }
+  const Tok head = lit_tok(b);
+  if (threadIdx.x == 0) put(win, wb, head);
+  wb += head.n;
+  for (int done = 0; done < M; done += PT * REP) {
+    const int cnt = min(PT * REP, M - done);
+#pragma unroll
+    for (int k = 0; k < REP; ++k) {
+      const int idx = threadIdx.x + k * PT;
+      if (idx < cnt) put(win, wb + MATCH258_BITS * idx, Tok{MATCH258, MATCH258_BITS});
+    }
+    wb += MATCH258_BITS * cnt;
+    flush(win, out, flushed, wb);
+  }
+  int at = wb;
+  const bool t0 = threadIdx.x == 0;
+  run_tail(b, r, [&](const Tok t) {
+    if (t0) put(win, at, t);
+    at += t.n;
+  });
+  wb = at;
+}
+
+// bytes f .. f+3 of the strip's ns plane bytes at b, (b + f) on a 4-byte boundary: one dword where all four are inside the strip,
+// byte by byte (0 for those outside) at its two ends
+__device__ __forceinline__ uint32_t strip_dword(const uint8_t* __restrict__ b, const int f, const int ns) {
+  if (f >= 0 && f + 4 <= ns) return *reinterpret_cast<const uint32_t*>(b + f);
+  uint32_t d = 0u;
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+    if (f + q >= 0 && f + q < ns) d |= (uint32_t)b[f + q] << (8 * q);
+  return d;
+}
+
+// ws: meta [P*nstrips][2] = (bytes of the strip, Adler a | b << 16), offs [P*nstrips], then the strips' bytes, stride_dw dwords each
+//
+// First launch: a workgroup per (plane, strip).  The strip's filtered bytes f = 0 .. n-1 are walked in passes of TCE_PNG_PASS.  A run
+// is written when its end is seen: at a BOUNDARY f (byte f differs from byte f-1), by the thread that owns byte f, and at the
+// strip's end.  Carried from pass to pass, the same in every thread: open_start (the last boundary so far), open_val (the last byte
+// so far), the window's bit count wb and the dwords flushed.
+__global__ void __launch_bounds__(PT) png_strip_kernel(const uint8_t* __restrict__ planes, uint32_t* __restrict__ ws, const int H, const int W,
+                                                       const int S, const int nstrips, const long long stride_dw, const int nonzero) {
+  __shared__ uint32_t win[WIN_DW];
+  __shared__ uint32_t raw[TCE_PNG_PASS / 4 + 4];  // the pass's plane bytes as the aligned dwords that hold them
+  __shared__ int sc_max[PWAVES], sc_min[PWAVES], sc_sum[PWAVES];
+  __shared__ uint32_t last_val;
+  __shared__ uint32_t red[2][PWAVES];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int strip = blockIdx.x, p = blockIdx.y;
+  const long long sidx = (long long)p * nstrips + strip, nstr = (long long)gridDim.y * nstrips;
+  const int row0 = strip * S, rows = min(S, H - row0), W1 = W + 1;
+  const int n = rows * W1, ns = rows * W;  // filtered bytes, plane bytes
+  const uint8_t* __restrict__ pl = planes + ((long long)p * H + row0) * W;
+  uint32_t* __restrict__ out = ws + nstr * 3 + sidx * stride_dw;
+  const uint8_t* rawb = reinterpret_cast<const uint8_t*>(raw);
+
+  for (int i = tid; i < WIN_DW; i += PT) win[i] = 0u;
+  __syncthreads();
+  if (tid == 0) put(win, 0, Tok{2u, 3});  // BFINAL = 0, BTYPE = 01 (least significant bit first)
+  int wb = 3, open_start = 0;
+  long long flushed = 0;
+  uint32_t open_val = 0u;
+  unsigned long long sa = 0ull, sb = 0ull;  // sum of bytes; sum of byte * (n - f): both fit (n < 2^31, a thread owns n / PT bytes)
+
+  for (int f0 = 0; f0 < n; f0 += TCE_PNG_PASS) {
+    const int len = min(TCE_PNG_PASS, n - f0);
+    // the pass's plane bytes q0 .. q1-1 (strip-relative): filtered byte f of row r = f / W1, column c = f % W1 > 0 is plane byte f - r - 1
+    const int r0 = f0 / W1, c0 = f0 - r0 * W1, fe = f0 + len - 1, re = fe / W1;
+    const int q0 = f0 - r0 - (c0 ? 1 : 0), q1 = fe - re;  // q1 - 1 = the last plane byte at or before fe
+    const int lead = (int)((reinterpret_cast<uintptr_t>(pl) + (uintptr_t)q0) & 3u);
+    for (int j = tid; 4 * j < lead + (q1 - q0); j += PT) raw[j] = strip_dword(pl, q0 - lead + 4 * j, ns);
+    __syncthreads();
+
+    // the thread's bytes, its boundaries, its share of the Adler sums
+    const int f = f0 + tid * PER;
+    uint32_t v[PER + 1];  // v[0]: the byte before the thread's own, v[j + 1]: its byte j
+    uint32_t bmask = 0u;
+    v[0] = open_val;
+    if (f < f0 + len) {
+      int r = f / W1, c = f - r * W1;
+      auto fbyte = [&](const int ff, const int rr, const int cc) -> uint32_t {
+        if (cc == 0) return 0u;
+        const uint32_t x = rawb[lead + (ff - rr - 1 - q0)];
+        return nonzero ? (x ? (uint32_t)nonzero : 0u) : x;
+      };
+      if (tid > 0) v[0] = c > 0 ? fbyte(f - 1, r, c - 1) : fbyte(f - 1, r - 1, W);  // (tid > 0: f - 1 >= f0 is in this pass)
+#pragma unroll
+      for (int j = 0; j < PER; ++j) {
+        v[j + 1] = 0u;
+        if (f + j < f0 + len) {
+          v[j + 1] = fbyte(f + j, r, c);
+          if (f + j > 0 && v[j + 1] != v[j]) bmask |= 1u << j;
+          sa += v[j + 1];
+          sb += (unsigned long long)v[j + 1] * (unsigned)(n - (f + j));
+          if (f + j == fe) last_val = v[j + 1];
+          if (++c == W1) {
+            c = 0;
+            ++r;
+          }
+        }
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < PER; ++j) v[j + 1] = 0u;
+    }
+    const int lastb = bmask ? f + (31 - __clz(bmask)) : -1, firstb = bmask ? f + (__ffs(bmask) - 1) : 0x7fffffff;
+
+    // the boundary before the thread's bytes (exclusive max-scan, starting from open_start) and the pass's first boundary
+    int sm = lastb, mn = firstb;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int a = __shfl_up(sm, o, 64);
+      if (lane >= o) sm = max(sm, a);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mn = min(mn, __shfl_xor(mn, o, 64));
+    if (lane == 63) sc_max[wave] = sm;
+    if (lane == 0) sc_min[wave] = mn;
+    __syncthreads();
+    int s_in = __shfl_up(sm, 1, 64);
+    if (lane == 0) s_in = -1;
+    s_in = max(s_in, open_start);
+    for (int k = 0; k < wave; ++k) s_in = max(s_in, sc_max[k]);
+    int new_open = open_start;
+    for (int k = 0; k < PWAVES; ++k) new_open = max(new_open, sc_max[k]);
+    const int first = min(min(sc_min[0], sc_min[1]), min(sc_min[2], sc_min[3]));
+
+    // the run carried into this pass ends at the pass's first boundary
+    if (f0 > 0 && first != 0x7fffffff) long_run(win, out, flushed, wb, open_val, first - open_start);
+
+    // the runs inside the pass: bit counts, their prefix sum, the bits
+    int bits = 0;
+    {
+      int s = s_in;
+#pragma unroll
+      for (int j = 0; j < PER; ++j) {
+        if (bmask & (1u << j)) {
+          if (s >= f0) run_tokens(v[j], f + j - s, [&](const Tok t) { bits += t.n; });
+          s = f + j;
+        }
+      }
+    }
+    int sum = bits;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int a = __shfl_up(sum, o, 64);
+      if (lane >= o) sum += a;
+    }
+    if (lane == 63) sc_sum[wave] = sum;
+    __syncthreads();  // (also: last_val is in)
+    int at = wb + sum - bits, total = 0;
+    for (int k = 0; k < PWAVES; ++k) {
+      if (k < wave) at += sc_sum[k];
+      total += sc_sum[k];
+    }
+    {
+      int s = s_in;
+#pragma unroll
+      for (int j = 0; j < PER; ++j) {
+        if (bmask & (1u << j)) {
+          if (s >= f0)
+            run_tokens(v[j], f + j - s, [&](const Tok t) {
+              put(win, at, t);
+              at += t.n;
+            });
+          s = f + j;
+        }
+      }
+    }
+    wb += total;
+    open_start = new_open;
+    open_val = last_val;
+    flush(win, out, flushed, wb);  // its barriers also protect raw, last_val and the scan words for the next pass
+  }
+
+  // the last run, end of block, a stored-block header, zero bits to the byte boundary, 00 00 FF FF
+  long_run(win, out, flushed, wb, open_val, n - open_start);
+  wb = (wb + 7 + 3 + 7) & ~7;
+  if (tid == 0) put(win, wb + 16, Tok{0xFFFFu, 16});
+  wb += 32;
+  __syncthreads();
+  const int ndw = (wb + 31) >> 5;
+  for (int i = tid; i < ndw; i += PT) out[flushed + i] = win[i];
+
+  // Adler pair of the strip's filtered bytes: a = 1 + sum of bytes, b = n + sum of byte_f * (n - f), mod 65521
+  uint32_t ra = (uint32_t)(sa % ADLER), rb = (uint32_t)(sb % ADLER);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    ra += (uint32_t)__shfl_xor((int)ra, o, 64);  // 64 * 65520 < 2^32
+    rb += (uint32_t)__shfl_xor((int)rb, o, 64);
+  }
+  if (lane == 0) {
+    red[0][wave] = ra;
+    red[1][wave] = rb;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    const uint32_t a = (1u + red[0][0] + red[0][1] + red[0][2] + red[0][3]) % ADLER;
+    const uint32_t b = ((uint32_t)(n % (int)ADLER) + red[1][0] + red[1][1] + red[1][2] + red[1][3]) % ADLER;
+    ws[sidx * 2] = (uint32_t)(flushed * 4 + (wb >> 3));
+    ws[sidx * 2 + 1] = a | (b << 16);
+  }
+}
+
+// Second launch: a workgroup per plane.  Offsets of the strips (2 + the exclusive scan of their byte counts), the Adler pair of the
+// whole plane, the header, the final block, the trailer, nbytes[p].  The pairs combine in strip order as
+//   a = 1 + sum_s (a_s - 1),  b = sum_s b_s + sum_s (a_s - 1) * (filtered bytes behind strip s)      (mod 65521)
+// which is the rule (a1 + a2 - 1, b1 + b2 + len(B) * (a1 - 1)) applied from the left: a sum, so no scan is needed for it.
+__global__ void __launch_bounds__(PT) png_plane_kernel(uint32_t* __restrict__ ws, uint8_t* __restrict__ streams, int* __restrict__ nbytes,
+                                                       const int H, const int W, const int S, const int nstrips, const long long bound) {
+  __shared__ uint32_t sc[PWAVES];
+  __shared__ uint32_t red[2][PWAVES];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, p = blockIdx.x;
+  const long long nstr = (long long)gridDim.x * nstrips, base = (long long)p * nstrips;
+  const uint32_t* __restrict__ meta = ws + base * 2;
+  uint32_t* __restrict__ offs = ws + nstr * 2 + base;
+  const long long ntot = (long long)H * (W + 1);
+  uint32_t carry = 2u;                // bytes in front of the strip: below 2^31 (tce_png_stream_bound)
+  unsigned long long sa = 0ull, sb = 0ull;  // at most nstrips / PT terms below 2^17: no overflow
+  for (int s0 = 0; s0 < nstrips; s0 += PT) {
+    const int s = s0 + tid;
+    uint32_t nb = 0u;
+    if (s < nstrips) {
+      nb = meta[2 * (long long)s];
+      const uint32_t ad = meta[2 * (long long)s + 1];
+      const uint32_t a1 = ((ad & 0xFFFFu) + ADLER - 1u) % ADLER;  // a_s - 1
+      const long long end = min((long long)(s + 1) * S, (long long)H) * (W + 1);
+      sa += a1;
+      sb += (ad >> 16) + (a1 * (uint32_t)((ntot - end) % ADLER)) % ADLER;  // 65520^2 < 2^32
+    }
+    uint32_t sum = nb;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const uint32_t a = (uint32_t)__shfl_up((int)sum, o, 64);
+      if (lane >= o) sum += a;
+    }
+    __syncthreads();  // the readers of sc of the pass before are done
+    if (lane == 63) sc[wave] = sum;
+    __syncthreads();
+    uint32_t at = carry + sum - nb;
+    for (int k = 0; k < wave; ++k) at += sc[k];
+    if (s < nstrips) offs[s] = at;
+    carry += sc[0] + sc[1] + sc[2] + sc[3];
+  }
+  uint32_t ra = (uint32_t)(sa % ADLER), rb = (uint32_t)(sb % ADLER);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    ra += (uint32_t)__shfl_xor((int)ra, o, 64);
+    rb += (uint32_t)__shfl_xor((int)rb, o, 64);
+  }
+  if (lane == 0) {
+    red[0][wave] = ra;
+    red[1][wave] = rb;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    const uint32_t a = (1u + red[0][0] + red[0][1] + red[0][2] + red[0][3]) % ADLER;
+    const uint32_t b = (red[1][0] + red[1][1] + red[1][2] + red[1][3]) % ADLER;
+    uint8_t* __restrict__ row = streams + (long long)p * bound;
+    row[0] = 0x78;
+    row[1] = 0x01;
+    uint8_t* __restrict__ t = row + carry;
+    t[0] = 0x03;  // BFINAL = 1, BTYPE = 01, symbol 256 (seven zero bits), zero bits to the byte boundary
+    t[1] = 0x00;
+    t[2] = (uint8_t)(b >> 8);
+    t[3] = (uint8_t)b;
+    t[4] = (uint8_t)(a >> 8);
+    t[5] = (uint8_t)a;
+    nbytes[p] = (int)(carry + 6u);
+  }
+}
+
+// Third launch: a workgroup per (plane, strip) copies the strip's bytes to their place.  A thread owns an ALIGNED dword of the
+// destination (the row of streams starts at any address, the offset is any number); its four bytes come out of the two workspace
+// dwords that hold them.  The strip's first and last dword go byte by byte.
+__global__ void __launch_bounds__(PT) png_copy_kernel(const uint32_t* __restrict__ ws, uint8_t* __restrict__ streams, const int nstrips,
+                                                      const long long stride_dw, const long long bound) {
+  const int strip = blockIdx.x, p = blockIdx.y;
+  const long long sidx = (long long)p * nstrips + strip, nstr = (long long)gridDim.y * nstrips;
+  const int nb = (int)ws[sidx * 2];
+  const uint32_t* __restrict__ src = ws + nstr * 3 + sidx * stride_dw;
+  uint8_t* __restrict__ dst = streams + (long long)p * bound + ws[nstr * 2 + sidx];
+  const int shift = (int)(reinterpret_cast<uintptr_t>(dst) & 3u);
+  for (int g = threadIdx.x; 4 * g - shift < nb; g += PT) {
+    const int k0 = 4 * g - shift;
+    if (k0 >= 0 && k0 + 4 <= nb) {
+      const int a = k0 >> 2, sh = (k0 & 3) * 8;
+      uint32_t d = src[a];
+      if (sh) d = (d >> sh) | (src[a + 1] << (32 - sh));  // byte 4 (a + 1) <= k0 + 3 < nb: inside the strip
+      *reinterpret_cast<uint32_t*>(dst + k0) = d;
+    } else {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int k = k0 + q;
+        if (k >= 0 && k < nb) dst[k] = (uint8_t)(src[k >> 2] >> ((k & 3) * 8));
+      }
+    }
+  }
+}
+
+struct PngPlan {
+  long long bound, stride_dw;
+  int nstrips;
+};
+
+// false: bad extents
+bool png_plan(const int H, const int W, const int S, PngPlan* pl) {
+  if (H <= 0 || W <= 0 || S <= 0 || (long long)H * W >= (1ll << 31)) return false;
+  const long long rows = S < H ? S : H, W1 = (long long)W + 1, full = H / rows, rest = H % rows;
+  const long long sb = TCE_PNG_STRIP_BOUND(rows * W1);
+  pl->bound = 2 + full * sb + (rest ? TCE_PNG_STRIP_BOUND(rest * W1) : 0) + 2 + 4;
+  pl->stride_dw = (sb + 3) / 4;
+  pl->nstrips = (int)(full + (rest ? 1 : 0));
+  // nbytes is int32, and byte offsets of a plane's stream stay ints with room for a workgroup's stride; a grid holds nstrips * 256 threads
+  return pl->bound < (1ll << 31) - 4096 && pl->nstrips <= TCE_PNG_MAX_STRIPS;
+}
+
+}  // namespace
+
+extern "C" int64_t tce_png_stream_bound(int32_t H, int32_t W, int32_t rows_per_strip) {
+  PngPlan pl;
+  return png_plan(H, W, rows_per_strip, &pl) ? pl.bound : -1;
+}
+
+extern "C" int64_t tce_png_ws_bytes(int32_t P, int32_t H, int32_t W, int32_t rows_per_strip) {
+  PngPlan pl;
+  if (P <= 0 || P > 65535 || !png_plan(H, W, rows_per_strip, &pl)) return -1;
+  const int64_t dwords = (int64_t)P * pl.nstrips * (3 + pl.stride_dw);
+  return (dwords * 4 + 7) & ~(int64_t)7;
+}
+
+extern "C" int tce_png_deflate_u8(const uint8_t* planes, uint8_t* streams, int32_t* nbytes, void* ws, int32_t P, int32_t H, int32_t W,
+                                  int32_t rows_per_strip, int32_t nonzero_value, tceStream stream) {
+  PngPlan pl;
+  TCE_CHECK_ARG(P > 0 && H > 0 && W > 0 && rows_per_strip > 0, "tce_png_deflate_u8: non-positive extent");
+  TCE_CHECK_ARG(P <= 65535 && png_plan(H, W, rows_per_strip, &pl),
+                "tce_png_deflate_u8: a plane must stay below 2^31 elements, its stream bound below 2^31 - 4096 bytes, its strips at or below 2^22 and P at or below 65535");
+  TCE_CHECK_ARG(nonzero_value >= 0 && nonzero_value <= 255, "tce_png_deflate_u8: nonzero_value %d outside 0 .. 255", nonzero_value);
+  TCE_CHECK_ARG(planes && streams && nbytes && ws, "tce_png_deflate_u8: null pointer");
+  TCE_CHECK_ARG(((uintptr_t)ws & 7u) == 0 && ((uintptr_t)nbytes & 3u) == 0,
+                "tce_png_deflate_u8: ws must be 8-byte aligned, nbytes 4-byte aligned");
+  const int S = rows_per_strip < H ? rows_per_strip : H;  // the same strips, and s * S stays an int
+  hipLaunchKernelGGL(png_strip_kernel, dim3(pl.nstrips, P), dim3(PT), 0, (hipStream_t)stream, planes, (uint32_t*)ws, H, W, S, pl.nstrips,
+                     pl.stride_dw, nonzero_value);
+  hipLaunchKernelGGL(png_plane_kernel, dim3(P), dim3(PT), 0, (hipStream_t)stream, (uint32_t*)ws, streams, nbytes, H, W, S, pl.nstrips,
+                     pl.bound);
+  hipLaunchKernelGGL(png_copy_kernel, dim3(pl.nstrips, P), dim3(PT), 0, (hipStream_t)stream, (const uint32_t*)ws, streams, pl.nstrips,
+                     pl.stride_dw, pl.bound);
+  TCE_CHECK_LAUNCH("tce_png_deflate_u8");
+  return TCE_OK;
+}

@@ -1154,6 +1154,39 @@ def mask_overlap(pred, gt, counts=None, ws=None):
     return counts
 
 
+def png_deflate(planes, rows_per_strip=8, nonzero_value=0, streams=None, nbytes=None, ws=None):
+    """The zlib stream of every uint8 plane [P,H,W] on the GPU (csrc/tce_rvos_png.h: PNG filter type 0 on every row, RLE-only
+    deflate with the fixed Huffman code in strips of rows_per_strip rows, Adler-32) -> (streams uint8 [P,bound], nbytes int32 [P]):
+    row p holds its nbytes[p] bytes; what lies behind them is not written.  nonzero_value = v in 1..255: every nonzero byte is
+    encoded as v (0/1 masks as 0/255); 0: bytes as they are (label maps).  Three launches, no host read-back.  The planes' address
+    goes to the launch as it is (any address), so they must be contiguous."""
+    from ._lib import lib_raw
+    t = planes
+    if not torch.is_tensor(t) or t.dim() != 3:
+        raise ValueError("png_deflate: planes must be [P,H,W]")
+    if t.dtype != torch.uint8 or not t.is_cuda or not t.is_contiguous():
+        raise ValueError(f"png_deflate: planes must be a contiguous uint8 tensor on the GPU, got {t.dtype} on {t.device}, "
+                         f"contiguous={t.is_contiguous()}")
+    P, H, W = (int(s) for s in t.shape)
+    S, v = int(rows_per_strip), int(nonzero_value)
+    if not 0 <= v <= 255:
+        raise ValueError(f"png_deflate: nonzero_value = {v} outside 0 .. 255")
+    ok = min(P, H, W, S) >= 1 and H * W < 2 ** 31 and S < 2 ** 31
+    # the two queries launch nothing: asked of the library itself, so that a recording (hazard.py) meets the launching entry
+    bound = lib_raw().tce_png_stream_bound(H, W, S) if ok else -1
+    need = lib_raw().tce_png_ws_bytes(P, H, W, S) if ok else -1
+    if bound < 0 or need < 0:
+        raise ValueError(f"png_deflate: unsupported extents P = {P} (1 .. 65535), (H, W) = {(H, W)} (below 2^31 pixels, the stream "
+                         f"bound below 2^31 bytes), rows_per_strip = {S} (>= 1, at most 2^22 strips)")
+    dev = t.device
+    streams = _out_tensor(streams, "png_deflate: streams [P,bound]", torch.uint8, (P, bound), dev)
+    nbytes = _out_tensor(nbytes, "png_deflate: nbytes [P]", torch.int32, (P,), dev)
+    ws = _workspace(ws, "png_deflate", need, dev)
+    check(lib().tce_png_deflate_u8(t.data_ptr(), streams.data_ptr(), nbytes.data_ptr(), ws.data_ptr(), P, H, W, S, v, _stream()),
+          "tce_png_deflate_u8")
+    return streams, nbytes
+
+
 def ffn_pack(w1, b1, w2, out=None):
     """Packs nn.Linear weights W1 [Hd,C], b1 [Hd], W2 [C,Hd] into the fused-FFN stream (csrc/chain.hip): fp16 hi/lo
     planes in MFMA-fragment order.  Done once per load_state_dict (static weights) or once per clip into an arena

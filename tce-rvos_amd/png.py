@@ -1,0 +1,82 @@
+"""PNG files of output planes that stay on the GPU: what the reference's inference drivers end with.
+
+    inference_ytvos.py:354-363   Image.fromarray(mask * 255).convert('L').save(...)       -> mask_pngs(run_video(...)["masks"])
+    inference_davis.py:300-311   Image.fromarray(labels), putpalette(palette), save(...)  -> label_pngs(run_video_objects(...)[i]["labels"], palette)
+
+The device makes each plane's complete zlib stream (ops.png_deflate, csrc/tce_rvos_png.h: filter bytes, deflate, Adler-32); the host
+reads back the byte counts and then only the bytes in use -- a few KB per mask instead of the plane -- and adds the chunk framing
+below.  The files decode to the same pixels as the reference's; they are several times LARGER than Pillow's (fixed Huffman codes,
+run-length matches only, a flush per strip of rows).  The framing functions need neither the GPU nor the shared library.
+"""
+import struct
+import zlib
+
+SIGNATURE = b"\x89PNG\r\n\x1a\n"
+COLOUR_TYPE = {"L": 0, "P": 3}
+
+
+def chunk(kind, data):
+    """length, type, data, CRC-32 of type and data"""
+    return struct.pack(">I", len(data)) + kind + data + struct.pack(">I", zlib.crc32(kind + data) & 0xFFFFFFFF)
+
+
+def palette_bytes(palette):
+    """The PLTE data of a palette given the way Image.putpalette takes it: bytes, or a flat sequence of R, G, B values; 1 .. 256 entries"""
+    data = bytes(palette)
+    if len(data) == 0 or len(data) % 3 or len(data) > 768:
+        raise ValueError(f"png: a palette holds 1 .. 256 RGB triples, got {len(data)} bytes")
+    return data
+
+
+def frame(stream, width, height, mode, palette=None):
+    """One complete PNG file around a zlib stream of the height * (width + 1) filtered bytes of an 8-bit image: signature, IHDR
+    (bit depth 8, colour type 0 for 'L' and 3 for 'P', no interlace), PLTE for 'P', one IDAT, IEND."""
+    if mode not in COLOUR_TYPE:
+        raise ValueError(f"png: mode must be 'L' or 'P', got {mode!r}")
+    if (palette is None) != (mode == "L"):
+        raise ValueError("png: mode 'P' needs a palette and mode 'L' takes none")
+    width, height = int(width), int(height)
+    if not (0 < width < 2 ** 31 and 0 < height < 2 ** 31):
+        raise ValueError(f"png: bad size {(width, height)}")
+    out = [SIGNATURE, chunk(b"IHDR", struct.pack(">IIBBBBB", width, height, 8, COLOUR_TYPE[mode], 0, 0, 0))]
+    if mode == "P":
+        out.append(chunk(b"PLTE", palette_bytes(palette)))
+    out += [chunk(b"IDAT", bytes(stream)), chunk(b"IEND", b"")]
+    return b"".join(out)
+
+
+def encode(planes, mode, palette=None, nonzero_value=0, rows_per_strip=8):
+    """One complete PNG file (bytes) per plane of a uint8 [P,H,W] tensor on the GPU.  One device call (three launches), one
+    read-back of the P byte counts, one read-back of the streams' prefixes in use, then the framing."""
+    from . import ops
+    if mode not in COLOUR_TYPE or (palette is None) != (mode == "L"):
+        frame(b"", 1, 1, mode, palette)  # raises with the message
+    if mode == "P":
+        palette = palette_bytes(palette)
+    streams, nbytes = ops.png_deflate(planes, rows_per_strip=rows_per_strip, nonzero_value=nonzero_value)
+    used = nbytes.cpu().tolist()                                   # read-back 1: P integers
+    flat = streams[:, :max(used)].cpu().numpy()                    # read-back 2: the bytes in use (the longest stream's prefix of every row)
+    H, W = int(planes.shape[1]), int(planes.shape[2])
+    return [frame(flat[p, :n].tobytes(), W, H, mode, palette) for p, n in enumerate(used)]
+
+
+def mask_pngs(masks, rows_per_strip=8):
+    """The files inference_ytvos.py:354-363 writes, from run_video(...)["masks"] (uint8 [N,H0,W0] of 0/1 on the GPU): mode 'L',
+    0 and 255."""
+    return encode(masks, "L", nonzero_value=255, rows_per_strip=rows_per_strip)
+
+
+def label_pngs(labels, palette, rows_per_strip=8):
+    """The files inference_davis.py:308-311 writes, from run_video_objects(...)[i]["labels"] (uint8 [T,H0,W0] on the GPU): mode
+    'P' with the caller's palette bytes (what Image.putpalette takes), the labels as they are."""
+    return encode(labels, "P", palette=palette, rows_per_strip=rows_per_strip)
+
+
+def write_files(paths, blobs):
+    """blobs[k] -> paths[k].  Directory layout and file names are the caller's business; the directories must exist."""
+    paths, blobs = list(paths), list(blobs)
+    if len(paths) != len(blobs):
+        raise ValueError(f"png: {len(paths)} paths for {len(blobs)} files")
+    for path, blob in zip(paths, blobs):
+        with open(path, "wb") as f:
+            f.write(blob)
