@@ -227,6 +227,14 @@ PNG_SIGNATURES = {
     "tce_png_deflate_u8": (i32, [c_f, c_f, c_f, c_f, i32, i32, i32, i32, i32, c_f]),
 }
 
+# csrc/tce_rvos_png_dyn.h: the PNG stage's second encoding (the cheaper of the fixed code and a code of its own per strip), staged on the
+# same terms in a header and a table of its own, bound by lib() after PNG_SIGNATURES (tests/test_png_dyn_cpu.py holds it to its header).
+PNG_DYN_HEADER = os.path.join(HERE, "csrc", "tce_rvos_png_dyn.h")
+PNG_DYN_SIGNATURES = {
+    # planes [P,H,W] u8, streams [P,bound] u8, nbytes [P] i32, ws, P, H, W, rows_per_strip, nonzero_value
+    "tce_png_deflate_dyn_u8": (i32, [c_f, c_f, c_f, c_f, i32, i32, i32, i32, i32, c_f]),
+}
+
 _LIB = None
 
 
@@ -247,7 +255,7 @@ def lib():
             warnings.warn(f"tce_rvos_amd: GPU_MAX_HW_QUEUES={hwq} is set; the HIP runtime's default (4) is the only value this "
                           f"launch program runs well with (1-3 crash the runtime, 5-16 double the clip time)", RuntimeWarning)
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in [kv for table in list(HEADERS.values()) + [STAGED_SIGNATURES, PNG_SIGNATURES] for kv in table.items()]:
+        for name, (res, args) in [kv for table in list(HEADERS.values()) + [STAGED_SIGNATURES, PNG_SIGNATURES, PNG_DYN_SIGNATURES] for kv in table.items()]:
             fn = getattr(l, name)  # AttributeError if the symbol is absent
             fn.restype, fn.argtypes = res, args
         _LIB = l

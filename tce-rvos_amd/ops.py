@@ -1154,13 +1154,17 @@ def mask_overlap(pred, gt, counts=None, ws=None):
     return counts
 
 
-def png_deflate(planes, rows_per_strip=8, nonzero_value=0, streams=None, nbytes=None, ws=None):
+def png_deflate(planes, rows_per_strip=8, nonzero_value=0, streams=None, nbytes=None, ws=None, codes="fixed"):
     """The zlib stream of every uint8 plane [P,H,W] on the GPU (csrc/tce_rvos_png.h: PNG filter type 0 on every row, RLE-only
     deflate with the fixed Huffman code in strips of rows_per_strip rows, Adler-32) -> (streams uint8 [P,bound], nbytes int32 [P]):
     row p holds its nbytes[p] bytes; what lies behind them is not written.  nonzero_value = v in 1..255: every nonzero byte is
     encoded as v (0/1 masks as 0/255); 0: bytes as they are (label maps).  Three launches, no host read-back.  The planes' address
-    goes to the launch as it is (any address), so they must be contiguous."""
+    goes to the launch as it is (any address), so they must be contiguous.  codes = "dynamic": every strip's block with the cheaper
+    of the fixed code and a Huffman code of its own (csrc/tce_rvos_png_dyn.h); the same sizes of streams and ws, never more bytes."""
     from ._lib import lib_raw
+    if codes not in ("fixed", "dynamic"):
+        raise ValueError(f"png_deflate: codes must be 'fixed' or 'dynamic', got {codes!r}")
+    entry = "tce_png_deflate_u8" if codes == "fixed" else "tce_png_deflate_dyn_u8"
     t = planes
     if not torch.is_tensor(t) or t.dim() != 3:
         raise ValueError("png_deflate: planes must be [P,H,W]")
@@ -1182,8 +1186,7 @@ def png_deflate(planes, rows_per_strip=8, nonzero_value=0, streams=None, nbytes=
     streams = _out_tensor(streams, "png_deflate: streams [P,bound]", torch.uint8, (P, bound), dev)
     nbytes = _out_tensor(nbytes, "png_deflate: nbytes [P]", torch.int32, (P,), dev)
     ws = _workspace(ws, "png_deflate", need, dev)
-    check(lib().tce_png_deflate_u8(t.data_ptr(), streams.data_ptr(), nbytes.data_ptr(), ws.data_ptr(), P, H, W, S, v, _stream()),
-          "tce_png_deflate_u8")
+    check(getattr(lib(), entry)(t.data_ptr(), streams.data_ptr(), nbytes.data_ptr(), ws.data_ptr(), P, H, W, S, v, _stream()), entry)
     return streams, nbytes
 
 

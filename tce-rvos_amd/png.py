@@ -5,14 +5,21 @@
 
 The device makes each plane's complete zlib stream (ops.png_deflate, csrc/tce_rvos_png.h: filter bytes, deflate, Adler-32); the host
 reads back the byte counts and then only the bytes in use -- a few KB per mask instead of the plane -- and adds the chunk framing
-below.  The files decode to the same pixels as the reference's; they are several times LARGER than Pillow's (fixed Huffman codes,
-run-length matches only, a flush per strip of rows).  The framing functions need neither the GPU nor the shared library.
+below.  The files decode to the same pixels as the reference's.  With codes="fixed" (the default: the stream as it always was) they
+are several times LARGER than Pillow's (fixed Huffman codes, run-length matches only, a flush per strip of 8 rows).  With
+codes="dynamic" every strip's block takes the cheaper of the fixed code and a Huffman code of its own (csrc/tce_rvos_png_dyn.h) and
+the strips are DYNAMIC_ROWS_PER_STRIP rows: files about the size of Pillow's (DESIGN.md section 3.16 has the measured sizes and
+times), never longer than the fixed stream of the same strips.  The framing functions need neither the GPU nor the shared library.
 """
 import struct
 import zlib
 
 SIGNATURE = b"\x89PNG\r\n\x1a\n"
 COLOUR_TYPE = {"L": 0, "P": 3}
+FIXED_ROWS_PER_STRIP = 8
+# of 16, 32 and 64 (tools/png_bench.py, profiles/r15_png_dyn.txt): none is as fast as the fixed code; 32 is the fastest at 720 x 1280,
+# 9 % behind 16 at 480 x 854 with files 16 % smaller; 64 is the slowest at both for 8 % smaller files (DESIGN.md section 3.16)
+DYNAMIC_ROWS_PER_STRIP = 32
 
 
 def chunk(kind, data):
@@ -45,31 +52,36 @@ def frame(stream, width, height, mode, palette=None):
     return b"".join(out)
 
 
-def encode(planes, mode, palette=None, nonzero_value=0, rows_per_strip=8):
+def encode(planes, mode, palette=None, nonzero_value=0, rows_per_strip=None, codes="fixed"):
     """One complete PNG file (bytes) per plane of a uint8 [P,H,W] tensor on the GPU.  One device call (three launches), one
-    read-back of the P byte counts, one read-back of the streams' prefixes in use, then the framing."""
+    read-back of the P byte counts, one read-back of the streams' prefixes in use, then the framing.  codes: "fixed" or "dynamic";
+    rows_per_strip = None: 8 for the fixed code, DYNAMIC_ROWS_PER_STRIP for dynamic codes."""
     from . import ops
+    if codes not in ("fixed", "dynamic"):
+        raise ValueError(f"png: codes must be 'fixed' or 'dynamic', got {codes!r}")
+    if rows_per_strip is None:
+        rows_per_strip = FIXED_ROWS_PER_STRIP if codes == "fixed" else DYNAMIC_ROWS_PER_STRIP
     if mode not in COLOUR_TYPE or (palette is None) != (mode == "L"):
         frame(b"", 1, 1, mode, palette)  # raises with the message
     if mode == "P":
         palette = palette_bytes(palette)
-    streams, nbytes = ops.png_deflate(planes, rows_per_strip=rows_per_strip, nonzero_value=nonzero_value)
+    streams, nbytes = ops.png_deflate(planes, rows_per_strip=rows_per_strip, nonzero_value=nonzero_value, codes=codes)
     used = nbytes.cpu().tolist()                                   # read-back 1: P integers
     flat = streams[:, :max(used)].cpu().numpy()                    # read-back 2: the bytes in use (the longest stream's prefix of every row)
     H, W = int(planes.shape[1]), int(planes.shape[2])
     return [frame(flat[p, :n].tobytes(), W, H, mode, palette) for p, n in enumerate(used)]
 
 
-def mask_pngs(masks, rows_per_strip=8):
+def mask_pngs(masks, rows_per_strip=None, codes="fixed"):
     """The files inference_ytvos.py:354-363 writes, from run_video(...)["masks"] (uint8 [N,H0,W0] of 0/1 on the GPU): mode 'L',
     0 and 255."""
-    return encode(masks, "L", nonzero_value=255, rows_per_strip=rows_per_strip)
+    return encode(masks, "L", nonzero_value=255, rows_per_strip=rows_per_strip, codes=codes)
 
 
-def label_pngs(labels, palette, rows_per_strip=8):
+def label_pngs(labels, palette, rows_per_strip=None, codes="fixed"):
     """The files inference_davis.py:308-311 writes, from run_video_objects(...)[i]["labels"] (uint8 [T,H0,W0] on the GPU): mode
     'P' with the caller's palette bytes (what Image.putpalette takes), the labels as they are."""
-    return encode(labels, "P", palette=palette, rows_per_strip=rows_per_strip)
+    return encode(labels, "P", palette=palette, rows_per_strip=rows_per_strip, codes=codes)
 
 
 def write_files(paths, blobs):

@@ -3,12 +3,16 @@ the path a caller has without it, on the same GPU in the same process.
 
   A  existing   masks.cpu(), then per mask the reference's own lines (inference_ytvos.py:354-363) saved to memory:
                 Image.fromarray(mask.astype(float32) * 255).convert('L').save(buffer, 'PNG')  -- Pillow's zlib at its default level
-  B  png.encode png.mask_pngs(masks, rows_per_strip=S) for S = 1, 8, 32: three launches, the byte counts, the used bytes, the framing
+  F<S>          png.mask_pngs(masks, rows_per_strip=S, codes="fixed") for S = 8, 32: three launches, the byte counts, the used bytes,
+                the framing
+  D<S>          the same with codes="dynamic" for S = 16, 32, 64 (a Huffman code per strip where it is cheaper than the fixed one)
   shapes        720 x 1280 and 480 x 854, one chunk of 32 planes of blob-like masks (an ellipse with a wavy edge per plane)
   wall          host time from the device tensor to the list of finished files, device idle before and after, per mask
   device        device-event time of ops.png_deflate alone (the three launches), per mask
   bytes         the mean file size of each path
-  Interleaved rounds in one process; one JSON line per measurement, to stdout and to --out (default profiles/r14_png.txt).
+  default       the strip height for dynamic codes: the smallest files among the D<S> whose fastest round stays within the spread F8
+                shows between its own rounds (max / min); if none does, the fastest D<S>
+  Interleaved rounds in one process; one JSON line per measurement, to stdout and to --out (default profiles/r15_png_dyn.txt).
 
   python tools/png_bench.py [--reps N] [--reps-a N] [--rounds R] [--out PATH]"""
 import argparse
@@ -30,12 +34,13 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--reps", type=int, default=20)
 ap.add_argument("--reps-a", type=int, default=2)
 ap.add_argument("--rounds", type=int, default=3)
-ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r14_png.txt"))
+ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r15_png_dyn.txt"))
 args = ap.parse_args()
 if not torch.cuda.is_available():
     sys.exit("png_bench: needs the GPU (a time taken elsewhere says nothing)")
 
-P, STRIPS = 32, (1, 8, 32)
+P = 32
+CONFIGS = (("F8", "fixed", 8), ("F32", "fixed", 32), ("D16", "dynamic", 16), ("D32", "dynamic", 32), ("D64", "dynamic", 64))
 lines = []
 
 
@@ -93,31 +98,46 @@ for H, W in ((720, 1280), (480, 854)):
     host = blob_masks(P, H, W, H)
     masks = torch.from_numpy(host).cuda()
     shape = f"{P} x {H} x {W}"
-    # agreement first: every file of both paths decodes to the same pixels
+    # agreement first: every file of every path decodes to the same pixels
     files = {"A": path_a(masks)}
-    for S in STRIPS:
-        files[f"B{S}"] = png.mask_pngs(masks, rows_per_strip=S)
+    for key, codes, S in CONFIGS:
+        files[key] = png.mask_pngs(masks, rows_per_strip=S, codes=codes)
     for key, fs in files.items():
         for m, f in zip(host, fs):
             im = Image.open(io.BytesIO(f))
             assert im.mode == "L" and np.array_equal(np.asarray(im), m * 255), key
+    size = {key: sum(len(f) for f in fs) / P for key, fs in files.items()}
     emit({"measure": "bytes_per_file", "shape": shape, "foreground_share": round(float(host.mean()), 4),
-          **{key: round(sum(len(f) for f in fs) / P) for key, fs in files.items()},
-          "plane_bytes": H * W, "B8_over_A": round(sum(len(f) for f in files["B8"]) / sum(len(f) for f in files["A"]), 2)})
+          **{key: round(b) for key, b in size.items()}, "plane_bytes": H * W,
+          **{f"{key}_over_A": round(size[key] / size["A"], 2) for key, _, _ in CONFIGS}})
     for _ in range(3):                                    # warm-up: code objects, the allocator's blocks
-        for S in STRIPS:
-            png.mask_pngs(masks, rows_per_strip=S)
+        for key, codes, S in CONFIGS:
+            png.mask_pngs(masks, rows_per_strip=S, codes=codes)
     wall = {"A": []}
-    wall.update({f"B{S}": [] for S in STRIPS})
-    dev = {f"B{S}": [] for S in STRIPS}
+    wall.update({key: [] for key, _, _ in CONFIGS})
+    dev = {key: [] for key, _, _ in CONFIGS}
     for _ in range(args.rounds):                          # interleaved
         wall["A"].append(round(wall_ms(lambda: path_a(masks), args.reps_a) / P, 4))
-        for S in STRIPS:
-            wall[f"B{S}"].append(round(wall_ms(lambda: png.mask_pngs(masks, rows_per_strip=S), args.reps) / P, 4))
-            dev[f"B{S}"].append(round(device_ms(lambda: ops.png_deflate(masks, rows_per_strip=S, nonzero_value=255), args.reps) / P, 5))
+        for key, codes, S in CONFIGS:
+            wall[key].append(round(wall_ms(lambda: png.mask_pngs(masks, rows_per_strip=S, codes=codes), args.reps) / P, 4))
+            dev[key].append(round(device_ms(lambda: ops.png_deflate(masks, rows_per_strip=S, nonzero_value=255, codes=codes), args.reps) / P, 5))
     emit({"measure": "wall_ms_per_mask", "shape": shape, **wall,
-          "A_over_B8": round(min(wall["A"]) / min(wall["B8"]), 2), "B8_faster": max(wall["B8"]) < min(wall["A"])})
+          "A_over_F8": round(min(wall["A"]) / min(wall["F8"]), 2), "F8_faster": max(wall["F8"]) < min(wall["A"]),
+          **{f"{key}_over_F8": round(min(wall[key]) / min(wall["F8"]), 2) for key in ("D16", "D32", "D64")}})
     emit({"measure": "device_event_ms_per_mask (ops.png_deflate alone, allocations included)", "shape": shape, **dev})
+    spread = max(wall["F8"]) / min(wall["F8"])
+    within = [key for key in ("D16", "D32", "D64") if min(wall[key]) <= min(wall["F8"]) * spread]
+    pick = min(within, key=lambda k: size[k]) if within else min(("D16", "D32", "D64"), key=lambda k: min(wall[k]))
+    emit({"measure": "default strip height for dynamic codes", "shape": shape, "F8_spread_max_over_min": round(spread, 3),
+          "within_the_spread": within, "pick": pick, "rule": "smallest files within the spread" if within else "none within: the fastest"})
+# the one mask the CPU test of the sizes uses (tests/test_png_dyn_cpu.py, tests/_png.blob), at the defaults of png.py
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+from _png import blob  # noqa: E402
+for H, W in ((720, 1280), (480, 854)):
+    m = torch.from_numpy(blob(H, W)[None]).cuda()
+    a, f, d = len(path_a(m)[0]), len(png.mask_pngs(m)[0]), len(png.mask_pngs(m, codes="dynamic")[0])
+    emit({"measure": "bytes of tests/_png.blob at the defaults", "shape": f"{H} x {W}", "A": a, "fixed": f, "dynamic": d,
+          "dynamic_rows_per_strip": png.DYNAMIC_ROWS_PER_STRIP, "dynamic_over_A": round(d / a, 2), "dynamic_over_fixed": round(d / f, 2)})
 os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
 with open(args.out, "w") as f:
     f.write("\n".join(lines) + "\n")
