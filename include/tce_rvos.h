@@ -181,7 +181,11 @@ int tce_ms_deform_attn_backward_f32(const float* value, const int64_t* spatial_s
 /* Fused form used by the model: takes the raw projection output proj [N*Lq, M*L*P*3] = (sampling offsets
  * [M,L,P,2] | attention logits [M,L*P]) and the reference points ref [N,Lq,ref_dim] (level-independent,
  * valid_ratios == 1), does softmax over L*P, the offset normalisation (ref_dim 2: / (W_l,H_l); ref_dim 4:
- * / P * wh * 0.5), and the bilinear gather.  Reference: ms_deform_attn.py:98-114 + the native kernel. */
+ * / P * wh * 0.5), and the bilinear gather.  Reference: ms_deform_attn.py:98-114 + the native kernel.
+ * Contract: every element of value is FINITE.  The branch-free forms (four / two points in flight, LDS-staged) load a clamped,
+ * valid address for a corner that is absent (outside the level, on padding, a sample outside the map) and multiply it by a zero
+ * coefficient, so a NaN / Inf row anywhere in a level can reach outputs that the loop forms keep clean; with finite rows all
+ * forms agree bit for bit up to the sign of a zero (tests/test_msda_probe_gpu.py). */
 int tce_msda_fused_f32(const float* value, const float* proj, const float* ref, float* out,
                        const int32_t* shapes_hw /* host, [L,2] */, int32_t N, int32_t S, int32_t M, int32_t Lq,
                        int32_t L, int32_t P, int32_t ref_dim, int32_t ref_per_frame, tceStream stream);
