@@ -65,6 +65,11 @@ class LabelObj(C.Structure):
     _fields_ = [("logits", c_f), ("masks", c_f)]
 
 
+class A2dGroupSample(C.Structure):  # tceA2dGroupSample (csrc/tce_rvos_a2d_group.h)
+    _fields_ = [("masks", c_f), ("logits", c_f), ("out", c_f), ("scores", c_f), ("fh", i32), ("fw", i32), ("H0", i32), ("W0", i32),
+                ("logit_stride", i32), ("reserved", i32)]
+
+
 # name -> (restype, argtypes), one table per header of include/ (HEADERS): EVERY symbol of its header and no other (tests check this)
 SIGNATURES = {
     "tce_abi_version": (i32, []),
@@ -235,6 +240,16 @@ PNG_DYN_SIGNATURES = {
     "tce_png_deflate_dyn_u8": (i32, [c_f, c_f, c_f, c_f, i32, i32, i32, i32, i32, c_f]),
 }
 
+# csrc/tce_rvos_a2d_group.h: the A2D / JHMDB post-processor's output stage for a group of samples (one launch for the masks and
+# scores of up to A2D_GROUP_MAX samples), staged on the same terms in a header and a table of its own, bound by lib() after
+# PNG_DYN_SIGNATURES (tests/test_single_frame_groups_cpu.py holds it to its header).
+A2D_GROUP_HEADER = os.path.join(HERE, "csrc", "tce_rvos_a2d_group.h")
+A2D_GROUP_MAX = 16  # TCE_A2D_GROUP_MAX
+A2D_GROUP_SIGNATURES = {
+    # samples (host table), B, N, h, w, threshold
+    "tce_a2d_group_masks_u8": (i32, [C.POINTER(A2dGroupSample), i32, i32, i32, i32, f32, c_f]),
+}
+
 _LIB = None
 
 
@@ -255,7 +270,7 @@ def lib():
             warnings.warn(f"tce_rvos_amd: GPU_MAX_HW_QUEUES={hwq} is set; the HIP runtime's default (4) is the only value this "
                           f"launch program runs well with (1-3 crash the runtime, 5-16 double the clip time)", RuntimeWarning)
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in [kv for table in list(HEADERS.values()) + [STAGED_SIGNATURES, PNG_SIGNATURES, PNG_DYN_SIGNATURES] for kv in table.items()]:
+        for name, (res, args) in [kv for table in list(HEADERS.values()) + [STAGED_SIGNATURES, PNG_SIGNATURES, PNG_DYN_SIGNATURES, A2D_GROUP_SIGNATURES] for kv in table.items()]:
             fn = getattr(l, name)  # AttributeError if the symbol is absent
             fn.restype, fn.argtypes = res, args
         _LIB = l

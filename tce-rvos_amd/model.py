@@ -718,7 +718,18 @@ class ReferFormer(nn.Module):
         with an interior pad or an empty caption raise ValueError.  Each clip's result is its B = 1 forward on the un-padded
         caption: the text self-attention and every text cross-attention take the pads as masked keys, the 1-D position map is
         normalised by each caption's length (position_encoding.py:28-50).  One captured graph serves every length mix of a
-        (G, Lmax, clip shape)."""
+        (G, Lmax, clip shape).
+
+        Single-frame groups (A2D-Sentences / JHMDB-Sentences: one annotated frame per clip, tce_rvos.py:233-243): EVERY target
+        carries 'valid_indices' (an int or a 1-element tensor, as the datasets give it; `targets` then holds G entries).  The
+        backbone sees all G*Tc frames (Video-Swin's windows stay per clip), after every stage the rows of frame valid_indices[g] of
+        clip g are gathered into a dense map (pipeline.pick_segments, tce_copy_segments) and the rest is the group program with one
+        frame per clip.  Each result is what forward([clip], caption, [{'size', 'valid_indices'}]) returns.  The indices are read on
+        the host (device tensors: one read-back) and the index tuple is part of the graph key: the gather's source addresses are
+        baked into the copy launches' arguments, so every distinct tuple of a shape captures a graph of its own (the LRU bound on
+        the graph cache, max_graphs / max_graph_bytes, limits what that costs; callers bucket by index -- video.plan_single_frame_groups).
+        A shared group (the same tensor G times) runs the backbone once; the indices may differ per caption.  Targets of which some
+        carry 'valid_indices' and others do not raise ValueError, an index outside the clip IndexError."""
         G = len(clips)
         if ragged:
             pad_id = self._pad_id()
@@ -747,8 +758,7 @@ class ReferFormer(nn.Module):
         img_h, img_w = float(size[0]), float(size[1])
         if any((float(t["size"][0]), float(t["size"][1])) != (img_h, img_w) for t in targets[1:]):
             raise ValueError("clip groups: the clips of a group share one target size")
-        if any("valid_indices" in t for t in targets):
-            raise NotImplementedError("clip groups: the single-frame path (targets[i]['valid_indices']) runs through forward(), one clip at a time")
+        sel = self._group_select(targets, G, shp[0])
         self._ensure_packed()
         ops.range_poll(clips[0].device)
         Tc = shp[0]
@@ -761,12 +771,14 @@ class ReferFormer(nn.Module):
             ids = ids.to(torch.int64).contiguous()
         # ragged: the flag, never the lengths (they live in the static id buffer)
         key = ("group", G, shared, shp, tuple(ids.shape), img_h, img_w, self.training, int(slot), self._stamp) + (("ragged",) if ragged else ())
+        if sel is not None:  # the selection's source addresses are arguments of the captured copy launches: one graph per index tuple
+            key += (("select", sel),)
 
         def frames_now():
             return srcs[0].to(torch.float32).contiguous() if shared else torch.cat([c.to(torch.float32) for c in srcs], 0)
 
         def eager():
-            return self._run(frames_now(), self._group_text(ids, ragged), img_h, img_w, None, slot, groups=G, shared=shared)
+            return self._run(frames_now(), self._group_text(ids, ragged), img_h, img_w, None, slot, groups=G, shared=shared, select=sel)
 
         if not ragged and key not in self._group_checked:
             self._group_checked.add(key)
@@ -785,7 +797,8 @@ class ReferFormer(nn.Module):
                 st = (frames_now().clone() if shared else frames_now(), ids.clone())
                 text_fn = self._group_text(st[1], ragged)
                 like = types.SimpleNamespace(shape=(G * Tc,) + shp[1:], device=dev)  # arenas are sized for the whole group
-                ent = self._capture(key, st, lambda res: self._run(st[0], text_fn, img_h, img_w, res, groups=G, shared=shared), like, slot)
+                ent = self._capture(key, st, lambda res: self._run(st[0], text_fn, img_h, img_w, res, groups=G, shared=shared, select=sel),
+                                    like, slot)
             if ent is None:
                 out = eager()
             else:  # the clips go straight into their slices of the graph's static frame buffer (one copy launch)
@@ -793,7 +806,10 @@ class ReferFormer(nn.Module):
                 statics = [ent[1][0][g * Tc:(g + 1) * Tc] for g in range(n)] + [ent[1][1]]
                 out = self._replay(key, (ent[0], statics) + tuple(ent[2:]), srcs + [ids])
         ops.range_snapshot_async(clips[0].device)
+        return self._split_group(out, G, Tc if sel is None else 1)
 
+    def _split_group(self, out, G, Tc):
+        """The output dict of a whole group -> one dict per clip (Tc output frames each)."""
         def part(v, g):  # clip g's slice of an output of the whole group
             if v.dim() >= 2 and v.shape[0] == 1 and v.shape[1] == G * Tc:
                 return v[:, g * Tc:(g + 1) * Tc]
@@ -809,6 +825,27 @@ class ReferFormer(nn.Module):
                     o[k] = [{kk: part(vv, g) for kk, vv in a.items()} for a in v]
             outs.append(self._tag_diagnostics(o))
         return outs
+
+    @staticmethod
+    def _group_select(targets, G, Tc):
+        """The per-clip annotated-frame indices of a group's targets as a tuple of G ints, or None when no target carries
+        'valid_indices'.  Read on the host; device tensors cost ONE read-back for the group."""
+        has = ["valid_indices" in t for t in targets]
+        if not any(has):
+            return None
+        if not all(has) or len(targets) != G:
+            raise ValueError("clip groups: the single-frame path needs 'valid_indices' in every one of the G targets")
+        vals = [t["valid_indices"] for t in targets]
+        if any(torch.is_tensor(v) and v.numel() != 1 for v in vals):
+            raise ValueError("clip groups: valid_indices is one index per clip (an int or a 1-element tensor)")
+        if any(torch.is_tensor(v) and v.is_cuda for v in vals):
+            dev = next(v.device for v in vals if torch.is_tensor(v) and v.is_cuda)
+            vals = torch.stack([torch.as_tensor(v).reshape(()).to(dev, torch.int64) for v in vals]).tolist()
+        sel = tuple(int(v) for v in vals)
+        for v in sel:
+            if not 0 <= v < Tc:
+                raise IndexError(f"valid_indices {v} outside the clip's {Tc} frames")
+        return sel
 
     @staticmethod
     def _tag_diagnostics(out):
@@ -952,12 +989,14 @@ class ReferFormer(nn.Module):
                 st[3])
 
     @torch.no_grad()
-    def hazard_check(self, frames, ids, img_hw=None, valid=None, slot=0, dry=False, groups=1, shared=False, ragged=False, observe=None):
+    def hazard_check(self, frames, ids, img_hw=None, valid=None, slot=0, dry=False, groups=1, shared=False, ragged=False, observe=None,
+                     select=None):
         """Records ONE pass of the clip's launch program on the capture topology (the same arenas, side streams, forks and
         joins a captured graph is built from) and checks it for races: any two launches not ordered by a fork / join edge
         must touch disjoint memory (tce_rvos_amd/hazard.py).  frames [T,3,H,W] and token ids [1,L] on the GPU.
         dry=True: the recorded pass launches nothing (negative controls).  ragged=True: the ragged clip-group program
-        (forward_group(..., ragged=True); ids [groups, Lmax] right-padded).  Returns a hazard.Report (`.clean`, `str()`);
+        (forward_group(..., ragged=True); ids [groups, Lmax] right-padded).  select: the single-frame path -- one index (groups = 1)
+        or one per clip of the group (with groups= / shared=: forward_group's valid_indices program).  Returns a hazard.Report (`.clean`, `str()`);
         results of the pass are discarded.  observe (tests): called as observe("before", resources, None) after the warm-up pass
         and observe("after", resources, recorder) after the recorded one, everything synchronised; it only looks on."""
         from . import hazard
@@ -967,8 +1006,10 @@ class ReferFormer(nn.Module):
         self._ensure_packed()
         res = self._branch_resources(types.SimpleNamespace(shape=(T * (groups if shared else 1), 3, H0, W0), device=frames.device), slot)
         st = (frames.clone(), ids.to(frames.device).clone())
+        if select is not None:
+            select = int(select) if groups == 1 and not isinstance(select, (tuple, list)) else tuple(int(v) for v in select)
         run = lambda: self._run(st[0], self._group_text(st[1], ragged), img_h, img_w, res, valid=valid, shared=shared,  # noqa: E731
-                                groups=groups)
+                                groups=groups, select=select)
         main = torch.cuda.Stream(device=frames.device)  # like a capture: never the legacy default stream (it syncs with all)
         main.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(main):
@@ -1072,10 +1113,17 @@ class ReferFormer(nn.Module):
         return hid[None], pooled[None]
 
     @torch.no_grad()
-    def forward_features(self, frames, text_hidden, text_pooled, img_h, img_w, slot=0, valid_hw=None, select=None):
+    def forward_features(self, frames, text_hidden, text_pooled, img_h, img_w, slot=0, valid_hw=None, select=None, groups=1,
+                         shared=False):
         """Everything after the text encoder.  frames [T,3,H,W]; text_hidden [L,768]; text_pooled [768].  valid_hw = (rows,
         columns) of the frames that are not padding (a clip zero-padded at the bottom / right; None: un-padded).  select: the
-        annotated frame of the single-frame path (targets[0]['valid_indices'], tce_rvos.py:233-243; None: every frame)."""
+        annotated frame of the single-frame path (targets[0]['valid_indices'], tce_rvos.py:233-243; None: every frame).
+        groups = G > 1: a clip group from given text features (forward_group's program): frames [G*Tc,3,H,W] (the clips back to
+        back; shared=True: ONE clip's [Tc,3,H,W]), text_hidden [G*L,768] caption-major, text_pooled [G,768], select None or a
+        sequence of G indices (one per clip); un-padded clips only.  Returns a list of G output dicts."""
+        if int(groups) > 1:
+            return self._forward_features_group(frames, text_hidden, text_pooled, img_h, img_w, slot, valid_hw, select, int(groups),
+                                                bool(shared))
         if valid_hw is not None:
             valid_hw = (int(valid_hw[0]), int(valid_hw[1]))
             if valid_hw == (int(frames.shape[-2]), int(frames.shape[-1])):
@@ -1097,6 +1145,45 @@ class ReferFormer(nn.Module):
                 return self._tag_diagnostics(self._run(frames, (text_hidden, text_pooled), img_h, img_w, None, slot, valid=valid_hw,
                                                        select=select))
         return self._tag_diagnostics(self._replay(key, ent, (frames, text_hidden, text_pooled)))
+
+
+    def _forward_features_group(self, frames, text_hidden, text_pooled, img_h, img_w, slot, valid_hw, select, G, shared):
+        if valid_hw is not None and (int(valid_hw[0]), int(valid_hw[1])) != (int(frames.shape[-2]), int(frames.shape[-1])):
+            raise NotImplementedError("clip groups: un-padded clips only")
+        Tb = int(frames.shape[0])
+        if frames.dim() != 4 or (not shared and Tb % G) or text_hidden.dim() != 2 or text_hidden.shape[0] % G or \
+                tuple(text_pooled.shape) != (G, text_hidden.shape[1]) or G > 64:
+            raise ValueError("clip groups from text features: frames [G*Tc,3,H,W] (shared: [Tc,3,H,W]), text_hidden [G*L,768], "
+                             "text_pooled [G,768], G <= 64")
+        Tc = Tb if shared else Tb // G
+        sel = None
+        if select is not None:
+            sel = tuple(int(v) for v in (select.tolist() if torch.is_tensor(select) else select))
+            if len(sel) != G:
+                raise ValueError(f"clip groups: {G} clips but {len(sel)} selected frames")
+            for v in sel:
+                if not 0 <= v < Tc:
+                    raise IndexError(f"valid_indices {v} outside the clip's {Tc} frames")
+        self._ensure_packed()
+        frames = frames.to(torch.float32).contiguous()
+        text_hidden, text_pooled = text_hidden.contiguous(), text_pooled.contiguous()
+        key = ("featgroup", G, shared, tuple(frames.shape), int(text_hidden.shape[0]), float(img_h), float(img_w), self.training,
+               int(slot), self._stamp, sel)
+
+        def eager():
+            return self._run(frames, (text_hidden, text_pooled), img_h, img_w, None, slot, groups=G, shared=shared, select=sel)
+
+        if not self._want_graph(key):
+            out = eager()
+        else:
+            ent = self._graphs.get(key)
+            if ent is None:
+                st = (frames.clone(), text_hidden.clone(), text_pooled.clone())
+                like = types.SimpleNamespace(shape=(G * Tc,) + tuple(frames.shape[1:]), device=frames.device)
+                ent = self._capture(key, st, lambda res: self._run(st[0], (st[1], st[2]), img_h, img_w, res, groups=G, shared=shared,
+                                                                   select=sel), like, slot)
+            out = eager() if ent is None else self._replay(key, ent, (frames, text_hidden, text_pooled))
+        return self._split_group(out, G, Tc if sel is None else 1)
 
 
 def caption_lengths(ids, pad_id):

@@ -786,6 +786,29 @@ def copy_many(dsts, srcs):
     flush()
 
 
+def copy_row_segments(src, segments, out):
+    """out <- the row segments of `src` back to back: src [R, C] and out dense float32 maps of one row length C; segments = a list
+    of (source row offset, rows, row words) with row words == C (pipeline.pick_segments).  One tce_copy_segments launch per 16."""
+    from ._lib import CopySeg
+    _chk(src, "src")
+    Cn = int(src.shape[-1])
+    if not out.is_contiguous() or out.dtype != torch.float32 or out.device != src.device:
+        raise ValueError("copy_row_segments: out must be a dense float32 tensor on src's device")
+    if any(rw != Cn or off < 0 or rows < 1 or (off + rows) * Cn > src.numel() for off, rows, rw in segments) or \
+            sum(rows for _, rows, _ in segments) * Cn != out.numel():
+        raise ValueError("copy_row_segments: segments must be whole rows inside src and fill out exactly")
+    st, at = _stream(), 0
+    sp, dp = src.data_ptr(), out.data_ptr()
+    for lo in range(0, len(segments), 16):
+        part = segments[lo:lo + 16]
+        segs = (CopySeg * len(part))()
+        for sg, (off, rows, rw) in zip(segs, part):
+            sg.src, sg.dst, sg.rows, sg.row_words, sg.src_pitch_words = sp + off * Cn * 4, dp + at * Cn * 4, rows, rw, Cn
+            at += rows
+        check(lib().tce_copy_segments(segs, len(part), st), "tce_copy_segments")
+    return out
+
+
 def tile(src, reps, out=None, alloc=None):
     """out = src repeated `reps` times along a new leading axis (flattened)."""
     _chk(src, "src")
@@ -1047,6 +1070,64 @@ def a2d_masks(pred_masks, size, orig_size, threshold=0.5, out=None):
     check(lib().tce_a2d_masks_u8(t.data_ptr(), out.data_ptr(), N, h, w, fh, fw, H0, W0, float(threshold), _stream()),
           "tce_a2d_masks_u8")
     return out
+
+
+A2D_GROUP_MAX = 16  # TCE_A2D_GROUP_MAX (csrc/tce_rvos_a2d_group.h): samples per launch
+
+
+def a2d_group_masks(pred_masks_list, logits_list, sizes, orig_sizes, threshold=0.5, outs=None):
+    """ops.a2d_masks and ops.sigmoid for the B samples of a group in ONE launch per A2D_GROUP_MAX samples
+    (csrc/tce_rvos_a2d_group.h).  pred_masks_list: B tensors [N,h,w] of one shape (each sample's outputs['pred_masks'][b,0]);
+    logits_list: B tensors [N] (outputs['pred_logits'][b,0,:,0]: a strided view is taken as it is); sizes / orig_sizes: B pairs
+    (the un-padded model-input size, the dataset's frame size) -> (masks: B uint8 [N,H0_b,W0_b] of 0/1, scores: B float32 [N]).
+    Every output byte is ops.a2d_masks', every score ops.sigmoid's.  The tensors' addresses go into the launch's table as they are,
+    so the masks must be contiguous float32 on the GPU.  outs: B tensors to write the masks into (any address) instead of new ones."""
+    pm, lg = list(pred_masks_list), list(logits_list)
+    B = len(pm)
+    if B < 1:
+        raise ValueError("a2d_group_masks: at least one sample")
+    if not (len(lg) == len(sizes) == len(orig_sizes) == B) or (outs is not None and len(outs) != B):
+        raise ValueError(f"a2d_group_masks: {B} pred_masks but {len(lg)} logits, {len(sizes)} sizes, {len(orig_sizes)} original sizes"
+                         + ("" if outs is None else f", {len(outs)} outs"))
+    t0 = pm[0]
+    if not torch.is_tensor(t0) or t0.dim() != 3:
+        raise ValueError("a2d_group_masks: pred_masks must be one [N,h,w] tensor per sample")
+    N, h, w = (int(s) for s in t0.shape)
+    dev = t0.device
+    geo = []
+    for b in range(B):
+        t, l = pm[b], lg[b]
+        if not torch.is_tensor(t) or tuple(t.shape) != (N, h, w):
+            raise ValueError(f"a2d_group_masks: sample {b} has pred_masks {tuple(getattr(t, 'shape', ()))}, sample 0 has {(N, h, w)}")
+        if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"a2d_group_masks: pred_masks[{b}] must be a contiguous float32 tensor on the GPU (one device), got "
+                             f"{t.dtype} on {t.device}, contiguous={t.is_contiguous()}")
+        if not torch.is_tensor(l) or l.dim() != 1 or int(l.shape[0]) != N or l.dtype != torch.float32 or l.device != dev:
+            raise ValueError(f"a2d_group_masks: logits[{b}] must be a float32 [N = {N}] tensor on the masks' device")
+        fh, fw = int(sizes[b][0]), int(sizes[b][1])
+        H0, W0 = int(orig_sizes[b][0]), int(orig_sizes[b][1])
+        if min(N, h, w, fh, fw, H0, W0) < 1:
+            raise ValueError("a2d_group_masks: empty extent")
+        if fh > 4 * h or fw > 4 * w:
+            raise ValueError(f"a2d_group_masks: size {(fh, fw)} of sample {b} exceeds 4x the mask plane {(h, w)}")
+        if N * H0 * W0 >= 2 ** 31 - 4096:
+            raise ValueError("a2d_group_masks: an output must stay below 2^31 elements")
+        geo.append((fh, fw, H0, W0))
+    res = [_out_tensor(None if outs is None else outs[b], f"a2d_group_masks: outs[{b}] [N,H0,W0]", torch.uint8, (N, g[2], g[3]), dev)
+           for b, g in enumerate(geo)]
+    scores = torch.empty(B, N, dtype=torch.float32, device=dev)
+    from ._lib import A2dGroupSample
+    st = _stream()
+    for lo in range(0, B, A2D_GROUP_MAX):
+        n = min(A2D_GROUP_MAX, B - lo)
+        table = (A2dGroupSample * n)()  # read by the entry point on the host, at this call
+        for k in range(n):
+            b, e = lo + k, table[k]
+            e.masks, e.logits, e.out, e.scores = pm[b].data_ptr(), lg[b].data_ptr(), res[b].data_ptr(), scores[b].data_ptr()
+            e.fh, e.fw, e.H0, e.W0 = geo[b]
+            e.logit_stride = max(1, int(lg[b].stride(0)))
+        check(lib().tce_a2d_group_masks_u8(table, n, N, h, w, float(threshold), st), "tce_a2d_group_masks_u8")
+    return res, list(scores.unbind(0))
 
 
 def rle_counts(masks, counts=None, nruns=None, ws=None):

@@ -123,10 +123,30 @@ class _Fork:
             torch.cuda.current_stream().wait_stream(self.side)
 
 
+def pick_segments(G, Tc, indices, sizes, channels, shared=False):
+    """The copy table of a clip group's single-frame selection (A2D / JHMDB: targets[g]['valid_indices']).  The backbone's map of
+    level i holds the frames of the G clips back to back, [G*Tc*hw_i, C_i] rows (shared: the ONE clip's Tc frames, [Tc*hw_i, C_i]);
+    clip g keeps frame indices[g] of its own clip.  Returns, per level, G segments (source row offset, rows, row words): segment g
+    moves rows [off, off + hw_i) of the map to rows [g*hw_i, (g + 1)*hw_i) of a dense [G*hw_i, C_i] map.  Pure host arithmetic."""
+    G, Tc = int(G), int(Tc)
+    idx = [int(v) for v in indices]
+    if len(idx) != G:
+        raise ValueError(f"pick_segments: {G} clips but {len(idx)} indices")
+    for v in idx:
+        if not 0 <= v < Tc:
+            raise IndexError(f"valid_indices {v} outside the clip's {Tc} frames")
+    table = []
+    for (h, w), c in zip(sizes, channels):
+        hw = int(h) * int(w)
+        table.append([(((0 if shared else g * Tc) + idx[g]) * hw, hw, int(c)) for g in range(G)])
+    return table
+
+
 def run_clip(model, frames, text, img_h, img_w, ar, side_arena=None, side_stream=None, clone_outputs=True, fork2=None,
              fork3=None, valid=None, groups=1, shared=False, select=None):
     """The clip's launch program with the model's own packed-weight routes active (ops.Routes).  valid = (rows, columns) of
-    the frames that are not padding (None: un-padded clip).  select = targets[0]['valid_indices'] (tce_rvos.py:233-243)."""
+    the frames that are not padding (None: un-padded clip).  select = targets[0]['valid_indices'] (tce_rvos.py:233-243); for a clip
+    group a sequence of `groups` indices, one per clip (pick_segments)."""
     with ops.routes(model._routes):
         return _run_clip(model, frames, text, img_h, img_w, ar, side_arena, side_stream, clone_outputs, fork2, fork3, valid, groups,
                          shared, select)
@@ -160,8 +180,21 @@ def _run_clip(model, frames, text, img_h, img_w, ar, side_arena=None, side_strea
     # select (the A2D / JHMDB single-frame path, tce_rvos.py:233-243): the backbone sees the clip's Tb frames (Video-Swin's
     # windows span them), every stage after it only frame `select` -- the reference index_selects the features, their masks and
     # position maps (frame independent here: same padding in every frame) and continues with t = 1
-    if select is not None:
-        if G != 1 or not 0 <= int(select) < Tb:
+    # A group with a selection (select = one index per clip): the backbone sees every frame of the G clips (shared: the one clip's
+    # frames, once); after every stage the rows of frame g*Tc + select[g] of each clip are gathered into a dense [G*hw_i, C_i] map
+    # (tce_copy_segments, one segment per clip and level: pick_segments) and the rest is the group program at T = G, Tc = 1.
+    sel_many = isinstance(select, (tuple, list)) and G > 1
+    seg_table = None
+    if sel_many:
+        select = tuple(int(v) for v in select)
+        Tcb = Tb if shared else Tb // G  # frames per clip in front of the backbone
+        if len(select) != G or any(not 0 <= v < Tcb for v in select):
+            raise ValueError("valid_indices: one index per clip of the group, each inside its clip")
+        T = G
+    elif select is not None:
+        if isinstance(select, (tuple, list)) and len(select) == 1:
+            select = select[0]
+        if G != 1 or isinstance(select, (tuple, list)) or not 0 <= int(select) < Tb:
             raise ValueError("valid_indices: one clip per forward, index inside the clip")
         select = int(select)
         T = 1
@@ -323,6 +356,8 @@ def _run_clip(model, frames, text, img_h, img_w, ar, side_arena=None, side_strea
     # branches of fork3 the two large levels start as soon as their Swin stage is done, beside the later stages (which
     # work on few tokens); the two small ones follow the backbone, each on its own stream.
     chs = cfg.num_channels
+    if sel_many:
+        seg_table = pick_segments(G, Tcb, select, sizes, chs, shared)
     early = (fork3 is not None and not cfg.is_resnet and fork3[0][1] is not None and fork3[1][1] is not None and
              side_stream is not None and EARLY_PROJ)
     src = A(T * S, D) if early else None  # [T, S, 256]: the encoder sequence
@@ -366,12 +401,18 @@ def _run_clip(model, frames, text, img_h, img_w, ar, side_arena=None, side_strea
         for arx, _ in fork3:
             arx.reset()
 
-    def pick(feat, i):
-        """the selected frame's rows of stage i's map (valid_indices), else the map"""
+    picked = [None] * 4  # a group's selection: the gathered map of stage i, once its consumer's branch has made it
+
+    def pick(feat, i, alloc=None):
+        """the selected frame's rows of stage i's map (valid_indices), else the map.  A group's selection is a gather: allocated
+        from `alloc` (default: the main arena) and issued on the current stream -- where the map's consumer runs."""
         if select is None:
             return feat
         hw_i = sizes[i][0] * sizes[i][1]
-        return feat[select * hw_i:(select + 1) * hw_i]
+        if not sel_many:
+            return feat[select * hw_i:(select + 1) * hw_i]
+        picked[i] = ops.copy_row_segments(feat, seg_table[i], (alloc or A)(G * hw_i, chs[i]))
+        return picked[i]
 
     lat1_cap = LAT1_CUS
     if lat1_cap is None:
@@ -385,6 +426,11 @@ def _run_clip(model, frames, text, img_h, img_w, ar, side_arena=None, side_strea
         with lat1_fork:
             while pending_norm0:
                 pending_norm0.pop()()  # Swin stage 0's output norm, here where its only consumer runs
+            if sel_many and picked[0] is None:  # a group's selection: stage 0's gather, in its consumer's arena and stream
+                if feat0 is None:
+                    feats[0] = pick(feats[0], 0, ar2.alloc)
+                else:
+                    feat0 = pick(feat0, 0, ar2.alloc)
             if wait_text:
                 text_fork.join()  # the branch's stream waits for the text branch (the folded stream of its cross-attention)
             with ops.ffn_wg_cap(lat1_cap):  # its cross-attention fold and its FFN: the only launches of the branch that read the cap
@@ -396,7 +442,8 @@ def _run_clip(model, frames, text, img_h, img_w, ar, side_arena=None, side_strea
             text_stage()
         if i == 0 and finish is not None:
             pending_norm0.append(finish)
-        feat = pick(feat, i)
+        if not sel_many:
+            feat = pick(feat, i)
         if i == 0 and LAT1_AT == "text" and ar2 is not None and stream2 is not None:
             lat1 = start_lat1(feat, wait_text=True)  # TCE_LAT1_AT=text: from the text join on, beside Swin stages 1-3
         if early:
@@ -406,6 +453,8 @@ def _run_clip(model, frames, text, img_h, img_w, ar, side_arena=None, side_strea
                     with fk_:
                         if finish is not None:
                             finish()  # the stage's output norm, in this branch
+                        if sel_many:
+                            feat = pick(feat, i, arx.alloc)  # this level's gather, in its consumer's arena and stream
                         text_fork.join()  # this level's stream waits for the text branch (keys / values of the fusion)
                         input_level(i - 1, feat, arx.alloc)
                     lvl_forks.append(fk_)
@@ -415,10 +464,16 @@ def _run_clip(model, frames, text, img_h, img_w, ar, side_arena=None, side_strea
         on_stage.defers = lambda i: select is None and ((i == 0 and ar2 is not None and stream2 is not None) or (i in (1, 2) and early))
     if cfg.is_resnet:
         with model.arith("backbone.merge"):  # a ResNet is convolutions only: one site group
-            feats = _resnet_backbone(model, frames, ar, sizes, rep=G if shared else 1)
+            feats = _resnet_backbone(model, frames, ar, sizes, rep=G if shared and not sel_many else 1)
     else:
-        feats = _swin_backbone(model, frames, ar, sizes, on_stage, 1 if shared else G, rep=G if shared else 1)
-    feats = [pick(f, i) for i, f in enumerate(feats)]
+        feats = _swin_backbone(model, frames, ar, sizes, on_stage, 1 if shared else G, rep=G if shared and not sel_many else 1)
+    if sel_many:
+        # stages whose consumer's branch has gathered them keep that map; stage 0 waits for the stride-4 lateral branch (start_lat1)
+        # where that branch exists; the others are read by the main stream's own work
+        later0 = ar2 is not None and stream2 is not None
+        feats = [picked[i] if picked[i] is not None else (f if i == 0 and later0 else pick(f, i)) for i, f in enumerate(feats)]
+    else:
+        feats = [pick(f, i) for i, f in enumerate(feats)]
 
     _stage("backbone")
     text_fork.join()
@@ -829,6 +884,8 @@ def _run_clip(model, frames, text, img_h, img_w, ar, side_arena=None, side_strea
     # ------------------------------------------------------------------ pixel decoder (segmentation.py:175-296)
     while pending_norm0:  # (the stride-4 lateral branch was never started: its input's norm runs here, before the decoder reads it)
         pending_norm0.pop()()
+    if sel_many and picked[0] is None:  # (and a group's selection of stage 0 with it)
+        feats[0] = pick(feats[0], 0)
     mask_feats = _pixel_decoder(model, ar, sc, feats, memory, vl_sites, T, L, ffn, ln_, lat1=lat1, par=fork3, G=G)
     dec_fork.join()
 

@@ -71,12 +71,31 @@ class A2DSentencesPostProcess(nn.Module):
     Per sample one masks launch and one run-length call over the N queries; per call one read-back of the run counts, then one of
     the used run lengths.  The float masks never leave the GPU.
     rle=False: no run-length launches, no read-back and no 'rle_masks' key -- for a caller that scores `masks` on the device
-    (a2d_score.A2DScorer.update) and needs no strings."""
+    (a2d_score.A2DScorer.update) and needs no strings.
+    grouped=True (opt-in): the samples of a call that share (N, h, w) -- a clip group's (model.forward_group with valid_indices) --
+    get their scores and masks from ONE launch per ops.A2D_GROUP_MAX samples (ops.a2d_group_masks) instead of a sigmoid and a masks
+    launch each; same bytes, same scores.  The run-length calls and the two read-backs stay as they are."""
 
-    def __init__(self, threshold=0.5, rle=True):
+    def __init__(self, threshold=0.5, rle=True, grouped=False):
         super().__init__()
         self.threshold = threshold
         self.rle = rle
+        self.grouped = grouped
+
+    def _held_grouped(self, samples, size, orig):
+        """(scores, masks, counts, nruns) per sample, the samples of one (N, h, w) served by one group launch"""
+        held = [None] * len(samples)
+        buckets = {}
+        for b, (_, pm) in enumerate(samples):
+            buckets.setdefault((tuple(pm.shape), pm.device), []).append(b)
+        for members in buckets.values():
+            masks, scores = ops.a2d_group_masks([samples[b][1].to(torch.float32).contiguous() for b in members],
+                                                [samples[b][0].to(torch.float32) for b in members],
+                                                [size[b] for b in members], [orig[b] for b in members], threshold=0.5)
+            for b, m, sc in zip(members, masks, scores):
+                counts, nruns = ops.rle_counts(m) if self.rle else (None, None)
+                held[b] = (sc, m, counts, nruns)
+        return held
 
     @torch.no_grad()
     def forward(self, outputs, orig_target_sizes, max_target_sizes):
@@ -84,12 +103,15 @@ class A2DSentencesPostProcess(nn.Module):
         orig, size = _sizes(orig_target_sizes), _sizes(max_target_sizes)
         if not len(orig) == len(size) == len(samples):
             raise ValueError(f"A2DSentencesPostProcess: {len(samples)} samples, {len(orig)} original sizes, {len(size)} sizes")
-        held = []
-        for (lg, pm), sz, og in zip(samples, size, orig):
-            scores = ops.sigmoid(lg.to(torch.float32).contiguous())
-            masks = ops.a2d_masks(pm.to(torch.float32).contiguous(), sz, og, threshold=0.5)
-            counts, nruns = ops.rle_counts(masks) if self.rle else (None, None)
-            held.append((scores, masks, counts, nruns))
+        if self.grouped:
+            held = self._held_grouped(samples, size, orig)
+        else:
+            held = []
+            for (lg, pm), sz, og in zip(samples, size, orig):
+                scores = ops.sigmoid(lg.to(torch.float32).contiguous())
+                masks = ops.a2d_masks(pm.to(torch.float32).contiguous(), sz, og, threshold=0.5)
+                counts, nruns = ops.rle_counts(masks) if self.rle else (None, None)
+                held.append((scores, masks, counts, nruns))
         if not self.rle:
             return [{"scores": scores, "masks": masks.unsqueeze(1)} for scores, masks, _, _ in held]
         nruns = torch.cat([h[3] for h in held]).cpu().tolist()               # read-back 1: B*N integers

@@ -17,6 +17,10 @@ Two loops of the reference's callers, with the model call and the caller harness
   run ONCE per chunk (clip groups, as above), and each annotator's objects are combined into one uint8 label map per chunk by one
   launch (ops.label_objects: best query, up-sampling, sigmoid, threshold, background plane and arg-max over the objects).
 
+* `run_annotated_frames(...)` -- the A2D-Sentences / JHMDB-Sentences evaluation loop (engine.py:301-319 without the data loader): one
+  annotated frame per clip (`valid_indices`); samples of one clip shape and index go through `model.forward_group` together and
+  through the post-processor's group launch.
+
 A video's chunks share the caption, so with `model.text_cache_size > 0` RoBERTa runs once per expression instead of
 once per chunk (the reference recomputes it inside every forward).  Chunks of one length share a captured hipGraph
 (model._graphs is an LRU over shapes); a last, shorter chunk runs eagerly unless its shape comes back.
@@ -196,3 +200,55 @@ def run_video_objects(model, frames: torch.Tensor, captions, origin_hw, clip_siz
     ops.check_range(dev)
     return [{"labels": r["labels"], "best_query": r["best_query"].t().contiguous(), "pred_logits": torch.cat(r["pred_logits"], 1),
              "pred_boxes": torch.cat(r["pred_boxes"], 1)} for r in res]
+
+
+def plan_single_frame_groups(shapes, indices, lengths, max_group: int = 8, mixed_lengths: bool = False):
+    """The forwards of run_annotated_frames: lists of sample indices, one list per forward_group call.  Samples are bucketed by
+    (clip shape, annotated-frame index, caption token length; mixed_lengths=True: whatever their lengths), buckets in order of first
+    sighting, `max_group` samples at a time; every sample appears exactly once.  Bucketing by index keeps the graph keys few: a
+    captured group graph belongs to one index tuple (model.forward_group)."""
+    if not len(shapes) == len(indices) == len(lengths):
+        raise ValueError(f"plan_single_frame_groups: {len(shapes)} shapes, {len(indices)} indices, {len(lengths)} lengths")
+    mg = max(1, int(max_group))
+    buckets = {}
+    for i, (shp, idx, n) in enumerate(zip(shapes, indices, lengths)):
+        key = (tuple(shp), int(idx)) + (() if mixed_lengths else (int(n),))
+        buckets.setdefault(key, []).append(i)
+    return [members[g0:g0 + mg] for members in buckets.values() for g0 in range(0, len(members), mg)]
+
+
+@torch.no_grad()
+def run_annotated_frames(model, samples, postprocessor=None, max_group: int = 8, mixed_lengths: bool = False):
+    """The A2D-Sentences / JHMDB-Sentences evaluation loop (engine.py:301-319 without the data loader).  samples: a list of dicts
+    with `clip` [T,3,H,W] float32 on the GPU (resized + normalised), `caption` (str or LongTensor [1,L]), `valid_index` (the annotated
+    frame), `orig_size` (the dataset's frame size) and optionally `size` (the model-input size; default the clip's (H, W)).  Returns,
+    in input order, the post-processor's dict per sample (postprocess.A2DSentencesPostProcess; grouped=True serves a group's samples
+    from one launch), or the forward's raw output dict when `postprocessor` is None.
+
+    The clips are UN-PADDED: samples are grouped by exact clip shape (plan_single_frame_groups), which replaces the reference's
+    padding of a batch to its largest clip, so each sample's result is its own B = 1 forward's -- forward([clip], caption,
+    [{'size', 'valid_indices'}]) -- and does not depend on what else the batch holds.  Samples that name the SAME clip tensor
+    (several expressions of one clip) share the backbone inside their group."""
+    if not samples:
+        return []
+    dev = samples[0]["clip"].device
+    ids = [s["caption"] if torch.is_tensor(s["caption"]) else model._tokenise([s["caption"]], dev)[0] for s in samples]
+    sizes = [tuple(int(v) for v in s["size"]) if s.get("size") is not None else (int(s["clip"].shape[-2]), int(s["clip"].shape[-1]))
+             for s in samples]
+    plan = plan_single_frame_groups([tuple(s["clip"].shape) + sz for s, sz in zip(samples, sizes)],
+                                    [int(s["valid_index"]) for s in samples], [int(t.shape[1]) for t in ids], max_group, mixed_lengths)
+    res = [None] * len(samples)
+    for grp in plan:
+        if mixed_lengths:  # right-padded on the host (validated there), lengths derived again on the device
+            from .model import pad_captions
+            tok = pad_captions([ids[i] for i in grp], model._pad_id())[0].to(dev)
+        else:
+            tok = torch.cat([ids[i].to(dev) for i in grp], 0)
+        targets = [{"size": torch.tensor(sizes[i]), "valid_indices": int(samples[i]["valid_index"])} for i in grp]
+        outs = model.forward_group([samples[i]["clip"] for i in grp], tok, targets, **({"ragged": True} if mixed_lengths else {}))
+        if postprocessor is not None:
+            outs = postprocessor(outs, [samples[i]["orig_size"] for i in grp], [sizes[i] for i in grp])
+        for i, o in zip(grp, outs):
+            res[i] = o
+    ops.check_range(dev)
+    return res
