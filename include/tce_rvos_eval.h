@@ -1,5 +1,6 @@
 /* tce_rvos_eval.h -- evaluation-stage entry points of libtce_rvos.so: what the reference's A2D-Sentences / JHMDB-Sentences
- * post-processor (models/postprocessors.py:14-54, called by engine.py:308-319) does with the outputs of one forward.
+ * post-processor (models/postprocessors.py:14-54, called by engine.py:308-319) does with the outputs of one forward
+ * (csrc/eval.hip), and its output stage for a GROUP of samples in one launch (csrc/a2d_group.hip).
  *
  * Same conventions as tce_rvos_video.h: device pointers to contiguous memory, the caller owns all of it, every launching entry
  * takes the hipStream_t to launch on, is asynchronous, allocates nothing, never synchronises (legal inside hipGraph capture),
@@ -45,6 +46,32 @@ int tce_a2d_masks_u8(const float* masks /* [N,h,w] */, uint8_t* out /* [N,H0,W0]
 int64_t tce_rle_ws_bytes(int32_t P, int32_t H, int32_t W); /* < 0: bad extents */
 int tce_rle_counts_u32(const uint8_t* masks /* [P,H,W] */, uint32_t* counts /* [P,H*W+1] */, int32_t* nruns /* [P] */,
                        void* ws, int32_t P, int32_t H, int32_t W, tceStream stream);
+
+/* ---- The output stage for a group of samples: what B calls of tce_a2d_masks_u8 and B sigmoid launches do
+ * (models/postprocessors.py:38-47), in one launch.  The samples of a clip group (model.forward_group with valid_indices) share the
+ * query count and the mask plane; everything else is per sample and travels in a table.  No atomics, every byte of every output
+ * written. */
+#define TCE_A2D_GROUP_MAX 16 /* samples per launch: the table is passed to the kernel by value (896 bytes of kernel arguments) */
+
+/* One sample of the group.  The table is read on the HOST at the call. */
+typedef struct {
+  const float* masks;   /* [N,h,w] mask logits (outputs['pred_masks'][b,0]), contiguous, 4-byte aligned */
+  const float* logits;  /* N class logits, logit_stride floats apart (outputs['pred_logits'][b,0,:,0]) */
+  uint8_t* out;         /* [N,H0,W0] 0/1, ANY address */
+  float* scores;        /* [N] sigmoid(logits), 4-byte aligned */
+  int32_t fh, fw;       /* the un-padded model-input size (targets['size']); fh <= 4h, fw <= 4w */
+  int32_t H0, W0;       /* the dataset's frame size; N*H0*W0 < 2^31 - 4096 */
+  int32_t logit_stride; /* >= 1 */
+  int32_t reserved;     /* 0 */
+} tceA2dGroupSample;
+
+/* For each of the B samples (1 <= B <= TCE_A2D_GROUP_MAX): out = the bytes the per-sample masks entry writes for (masks, N, h, w,
+ * fh, fw, H0, W0, threshold) -- the resampling rule and the byte-quad store of csrc/mask_planes.h, so equal byte for byte at any
+ * output address -- and scores[n] = 1 / (1 + expf(-logits[n * logit_stride])), the bits of the sigmoid entry of include/tce_rvos.h.
+ * One launch: grid (x, B); sample b's workgroups own 1024 output bytes each (a byte quad per thread) and those past its own
+ * N*H0*W0 exit; workgroup 0 of a sample also writes its N scores.  Outputs of different samples must not overlap. */
+int tce_a2d_group_masks_u8(const tceA2dGroupSample* samples, int32_t B, int32_t N, int32_t h, int32_t w, float threshold,
+                           tceStream stream);
 
 #ifdef __cplusplus
 }

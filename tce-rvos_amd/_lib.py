@@ -1,4 +1,4 @@
-"""ctypes binding of libtce_rvos.so (the C ABI declared in include/tce_rvos.h).
+"""ctypes binding of libtce_rvos.so (the C ABI declared in the headers of include/).
 
 The product path has NO fallback: if the shared object is missing or a symbol is absent, importing this
 module's `lib()` raises.  Build it with `python -m tce_rvos_amd.build` / `__graft_entry__.build()`.
@@ -65,7 +65,7 @@ class LabelObj(C.Structure):
     _fields_ = [("logits", c_f), ("masks", c_f)]
 
 
-class A2dGroupSample(C.Structure):  # tceA2dGroupSample (csrc/tce_rvos_a2d_group.h)
+class A2dGroupSample(C.Structure):  # tceA2dGroupSample (include/tce_rvos_eval.h)
     _fields_ = [("masks", c_f), ("logits", c_f), ("out", c_f), ("scores", c_f), ("fh", i32), ("fw", i32), ("H0", i32), ("W0", i32),
                 ("logit_stride", i32), ("reserved", i32)]
 
@@ -189,30 +189,22 @@ VIDEO_SIGNATURES = {
 }
 
 # include/tce_rvos_eval.h: evaluation-stage entry points (the A2D-Sentences / JHMDB-Sentences post-processor)
+A2D_GROUP_MAX = 16  # TCE_A2D_GROUP_MAX
 EVAL_SIGNATURES = {
     # masks [N,h,w], out [N,H0,W0], N, h, w, fh, fw, H0, W0, threshold
     "tce_a2d_masks_u8": (i32, [c_f, c_f, i32, i32, i32, i32, i32, i32, i32, f32, c_f]),
     "tce_rle_ws_bytes": (i64, [i32, i32, i32]),
     # masks [P,H,W] u8, counts [P,H*W+1] u32, nruns [P] i32, ws, P, H, W
     "tce_rle_counts_u32": (i32, [c_f, c_f, c_f, c_f, i32, i32, i32, c_f]),
+    # samples (host table), B, N, h, w, threshold: the masks and scores of up to A2D_GROUP_MAX samples in one launch
+    "tce_a2d_group_masks_u8": (i32, [C.POINTER(A2dGroupSample), i32, i32, i32, i32, f32, c_f]),
 }
 
-# include/tce_rvos_score.h: scoring-stage entry points (the counts behind Ref-DAVIS J&F)
+# include/tce_rvos_score.h: scoring-stage entry points (the counts behind Ref-DAVIS J&F and behind A2D / JHMDB precision, IoU and AP)
 SCORE_SIGNATURES = {
     "tce_jf_ws_bytes": (i64, [i32, i32, i32, i32, i32]),  # T, n, H, W, radius
     # pred [T,H,W] u8, gt [T,H,W] u8, counts [n,T,6] i32, ws, T, n, H, W, radius
     "tce_jf_counts_i32": (i32, [c_f, c_f, c_f, c_f, i32, i32, i32, i32, i32, c_f]),
-}
-
-HEADERS = {"tce_rvos.h": SIGNATURES, "tce_rvos_debug.h": DEBUG_SIGNATURES, "tce_rvos_video.h": VIDEO_SIGNATURES,
-           "tce_rvos_eval.h": EVAL_SIGNATURES, "tce_rvos_score.h": SCORE_SIGNATURES}
-
-# csrc/tce_rvos_a2d_score.h: A2D-Sentences / JHMDB-Sentences scoring-stage entry points, STAGED -- exported by the same library and
-# bound by lib() after the HEADERS tables, but not a header of include/ and not in HEADERS, whose contents existing tests pin (the
-# header's top comment has the reasons and the follow-up).  The hazard checker has no access model for them: hazard._LibProxy
-# refuses each of these names inside a recorded launch program (tests/test_a2d_score_cpu.py holds this table to its header).
-STAGED_HEADER = os.path.join(HERE, "csrc", "tce_rvos_a2d_score.h")
-STAGED_SIGNATURES = {
     "tce_rle_decode_ws_bytes": (i64, [i32, i32, i32, i32]),  # P, H, W, stride
     # counts [P,stride] u32, nruns [P] i32, out [P,H,W] u8, ws, P, H, W, stride
     "tce_rle_decode_u8": (i32, [c_f, c_f, c_f, c_f, i32, i32, i32, i32, c_f]),
@@ -221,34 +213,18 @@ STAGED_SIGNATURES = {
     "tce_mask_overlap_i32": (i32, [c_f, c_f, c_f, c_f, i32, i32, i32, c_f]),
 }
 
-# csrc/tce_rvos_png.h: PNG-writing stage entry points (the zlib stream of every output plane), staged beside the table above for the
-# same reasons and on the same terms: bound by lib() after it, outside HEADERS, no access model, refused by hazard._LibProxy
-# (tests/test_png_cpu.py holds this table to its header).
-PNG_HEADER = os.path.join(HERE, "csrc", "tce_rvos_png.h")
+# include/tce_rvos_png.h: PNG-writing stage entry points (the zlib stream of every output plane, with the fixed Huffman code or with
+# the cheaper of the fixed code and a code of its own per strip)
 PNG_SIGNATURES = {
     "tce_png_stream_bound": (i64, [i32, i32, i32]),  # H, W, rows_per_strip
     "tce_png_ws_bytes": (i64, [i32, i32, i32, i32]),  # P, H, W, rows_per_strip
     # planes [P,H,W] u8, streams [P,bound] u8, nbytes [P] i32, ws, P, H, W, rows_per_strip, nonzero_value
     "tce_png_deflate_u8": (i32, [c_f, c_f, c_f, c_f, i32, i32, i32, i32, i32, c_f]),
-}
-
-# csrc/tce_rvos_png_dyn.h: the PNG stage's second encoding (the cheaper of the fixed code and a code of its own per strip), staged on the
-# same terms in a header and a table of its own, bound by lib() after PNG_SIGNATURES (tests/test_png_dyn_cpu.py holds it to its header).
-PNG_DYN_HEADER = os.path.join(HERE, "csrc", "tce_rvos_png_dyn.h")
-PNG_DYN_SIGNATURES = {
-    # planes [P,H,W] u8, streams [P,bound] u8, nbytes [P] i32, ws, P, H, W, rows_per_strip, nonzero_value
     "tce_png_deflate_dyn_u8": (i32, [c_f, c_f, c_f, c_f, i32, i32, i32, i32, i32, c_f]),
 }
 
-# csrc/tce_rvos_a2d_group.h: the A2D / JHMDB post-processor's output stage for a group of samples (one launch for the masks and
-# scores of up to A2D_GROUP_MAX samples), staged on the same terms in a header and a table of its own, bound by lib() after
-# PNG_DYN_SIGNATURES (tests/test_single_frame_groups_cpu.py holds it to its header).
-A2D_GROUP_HEADER = os.path.join(HERE, "csrc", "tce_rvos_a2d_group.h")
-A2D_GROUP_MAX = 16  # TCE_A2D_GROUP_MAX
-A2D_GROUP_SIGNATURES = {
-    # samples (host table), B, N, h, w, threshold
-    "tce_a2d_group_masks_u8": (i32, [C.POINTER(A2dGroupSample), i32, i32, i32, i32, f32, c_f]),
-}
+HEADERS = {"tce_rvos.h": SIGNATURES, "tce_rvos_debug.h": DEBUG_SIGNATURES, "tce_rvos_video.h": VIDEO_SIGNATURES,
+           "tce_rvos_eval.h": EVAL_SIGNATURES, "tce_rvos_score.h": SCORE_SIGNATURES, "tce_rvos_png.h": PNG_SIGNATURES}
 
 _LIB = None
 
@@ -270,7 +246,7 @@ def lib():
             warnings.warn(f"tce_rvos_amd: GPU_MAX_HW_QUEUES={hwq} is set; the HIP runtime's default (4) is the only value this "
                           f"launch program runs well with (1-3 crash the runtime, 5-16 double the clip time)", RuntimeWarning)
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in [kv for table in list(HEADERS.values()) + [STAGED_SIGNATURES, PNG_SIGNATURES, PNG_DYN_SIGNATURES, A2D_GROUP_SIGNATURES] for kv in table.items()]:
+        for name, (res, args) in [kv for table in HEADERS.values() for kv in table.items()]:
             fn = getattr(l, name)  # AttributeError if the symbol is absent
             fn.restype, fn.argtypes = res, args
         _LIB = l

@@ -2,7 +2,7 @@
 (engine.py:321-353: COCOeval with iouType='segm', useCats=0, and datasets/a2d_eval.py) -- P@0.5 .. P@0.9, overall IoU, mean IoU and
 mask AP -- without pycocotools and without decoding a run-length string on the host.
 
-The pixel work is two library calls per image (csrc/tce_rvos_a2d_score.h): ops.rle_decode turns the ground truth's run lengths
+The pixel work is two library calls per image (include/tce_rvos_score.h): ops.rle_decode turns the ground truth's run lengths
 (and, for saved prediction files, the predictions') into planes, ops.mask_overlap counts per prediction the intersection, its own
 area and the ground truth's.  Three integers per prediction and its score wait in device slabs; state() reads them back, once.
 Everything after the counts is host arithmetic on integers, restated from the reference operation by operation:

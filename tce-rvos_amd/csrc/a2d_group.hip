@@ -3,7 +3,7 @@
 // (eval.hip), whose per-pixel body it repeats on the shared rules of mask_planes.h; what it saves is launches, not bytes.
 #include "common.h"
 #include "mask_planes.h"
-#include "tce_rvos_a2d_group.h"
+#include "../../include/tce_rvos_eval.h"
 
 namespace {
 

@@ -2,7 +2,7 @@
 // counts of N prediction planes against one ground-truth plane.  Byte kernels, bound by memory latency at dataset sizes.
 #include "common.h"
 #include "mask_planes.h"
-#include "tce_rvos_a2d_score.h"
+#include "../../include/tce_rvos_score.h"
 
 namespace {
 

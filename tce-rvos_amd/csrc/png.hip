@@ -2,8 +2,7 @@
 // bytes, RLE-only deflate with the fixed Huffman code or, behind the second entry, with the cheaper of the fixed code and a code of
 // the strip's own, Adler-32 -- in three launches.  Byte and bit kernels: bound by LDS traffic and barriers, not by arithmetic.
 #include "common.h"
-#include "tce_rvos_png.h"
-#include "tce_rvos_png_dyn.h"
+#include "../../include/tce_rvos_png.h"
 
 namespace {
 

@@ -8,8 +8,9 @@ differed from the eager pass).  This module needs no failure to come back: it RE
 checks it statically.
 
   * every C-ABI launch (`lib().tce_*`) is intercepted: the stream it was issued on and -- from the same pointers and sizes
-    the kernel receives -- the exact byte ranges it reads and writes (`MODELS`, one access model per entry point of
-    the headers of include/ (_lib.HEADERS); an entry point without a model is an error, so coverage cannot rot);
+    the kernel receives -- the byte ranges it reads and writes (`MODELS`: one access model for every launching entry point
+    of every header of include/ (_lib.HEADERS), the drivers' output stages included; an entry point that is neither modelled
+    nor listed in `NOT_LAUNCHES` is an error, so coverage cannot rot);
   * every event record / wait (torch's `wait_stream` is `wait_event(record_event())`) and every host synchronisation is
     intercepted and turned into vector clocks: launch A happens-before launch B iff B's clock has seen A's tick;
   * `analyse()` then asserts that any two launches NOT ordered by happens-before touch disjoint memory (write/write and
@@ -362,6 +363,42 @@ def _jf_counts(a):
     return [dense(_p(pred), T * H * W), dense(_p(gt), T * H * W), wsb], [dense(_p(counts), n * T * 6 * 4), wsb]
 
 
+def _rle_decode(a):
+    """counts, nruns, out, ws, P, H, W, stride: how far a row of counts is read is decided by nruns on the device, so every row is
+    read in full here; every byte of out is written; ws is written by the first two launches and read by the later ones"""
+    counts, nruns, out, ws, P, H, W, stride = a[:8]
+    wsb = dense(_p(ws), _lib.lib_raw().tce_rle_decode_ws_bytes(P, H, W, stride))
+    return [dense(_p(counts), P * stride * 4), dense(_p(nruns), P * 4), wsb], [dense(_p(out), P * H * W), wsb]
+
+
+def _mask_overlap(a):
+    """pred, gt, counts, ws, N, H, W: every plane is read in full, every word of counts is written; ws is written by the first
+    launch (the tiles' partial sums) and read by the second"""
+    pred, gt, counts, ws, N, H, W = a[:7]
+    wsb = dense(_p(ws), _lib.lib_raw().tce_mask_overlap_ws_bytes(N, H, W))
+    return [dense(_p(pred), N * H * W), dense(_p(gt), H * W), wsb], [dense(_p(counts), N * 3 * 4), wsb]
+
+
+def _png_deflate(a):
+    """planes, streams, nbytes, ws, P, H, W, rows_per_strip, nonzero_value (both encodings): how much of a row of streams is written
+    is device data (nbytes), so the whole row is named: a superset, which can cost a false conflict and can never hide one"""
+    planes, streams, nbytes, ws, P, H, W, S = a[:8]
+    L = _lib.lib_raw()
+    wsb = dense(_p(ws), L.tce_png_ws_bytes(P, H, W, S))
+    return [dense(_p(planes), P * H * W), wsb], [dense(_p(streams), P * L.tce_png_stream_bound(H, W, S)), dense(_p(nbytes), P * 4), wsb]
+
+
+def _a2d_group_masks(a):
+    """samples (host table), B, N, h, w: per sample what _a2d_masks names, plus its N logits (logit_stride floats apart) and scores"""
+    samples, B, N, h, w = a[:5]
+    rd, wr = [], []
+    for b in range(B):
+        e = samples[b]
+        rd += [dense(_p(e.masks), N * h * w * F), strided(_p(e.logits), F, (N, e.logit_stride * F))]
+        wr += [dense(_p(e.out), N * e.H0 * e.W0), dense(_p(e.scores), N * F)]
+    return rd, wr
+
+
 MODELS = {
     "tce_gemm_f32": lambda a: _gemm(_st(a[0])),
     "tce_gemm_splitk_f32": lambda a: _gemm(_st(a[0]), ws=a[2], splits=a[1]),
@@ -507,6 +544,11 @@ MODELS = {
     "tce_a2d_masks_u8": _a2d_masks,
     "tce_rle_counts_u32": _rle_counts,
     "tce_jf_counts_i32": _jf_counts,
+    "tce_rle_decode_u8": _rle_decode,
+    "tce_mask_overlap_i32": _mask_overlap,
+    "tce_png_deflate_u8": _png_deflate,
+    "tce_png_deflate_dyn_u8": _png_deflate,
+    "tce_a2d_group_masks_u8": _a2d_group_masks,
 }
 
 
@@ -516,7 +558,8 @@ NOT_LAUNCHES = {"tce_abi_version", "tce_last_error", "tce_gemm_select_tile", "tc
                 "tce_ffn_set_wg_cap", "tce_ffn_capped_grid",
                 "tce_rowlin_packed_bytes", "tce_conv3x3_packed_bytes", "tce_conv3x3_split_ws_floats",
                 "tce_conv3x3_split_pieces", "tce_conv3x3_split_kstep", "tce_swin_attn_packed_bytes", "tce_thin_linear_splits", "tce_graph_begin", "tce_graph_end", "tce_graph_launch",
-                "tce_graph_destroy", "tce_graph_group", "tce_rle_ws_bytes", "tce_jf_ws_bytes"} | set(_lib.DEBUG_SIGNATURES)
+                "tce_graph_destroy", "tce_graph_group", "tce_rle_ws_bytes", "tce_jf_ws_bytes", "tce_rle_decode_ws_bytes", "tce_mask_overlap_ws_bytes",
+                "tce_png_stream_bound", "tce_png_ws_bytes"} | set(_lib.DEBUG_SIGNATURES)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -636,11 +679,11 @@ class Report:
 
 
 def _site():
-    """Innermost frame of the launch program (pipeline / text_encoder / model) on the stack: 'file:line function'."""
+    """Innermost frame of the launch program (pipeline / text_encoder / model / a stage driver) on the stack: 'file:line function'."""
     best = "?"
     for fr in traceback.extract_stack(limit=24)[:-3]:
         fn = fr.filename.rsplit("/", 1)[-1]
-        if fn in ("pipeline.py", "text_encoder.py", "model.py", "video.py", "postprocess.py", "score.py"):
+        if fn in ("pipeline.py", "text_encoder.py", "model.py", "video.py", "postprocess.py", "score.py", "a2d_score.py", "png.py"):
             best = f"{fn}:{fr.lineno} {fr.name}"
     return best
 

@@ -1072,12 +1072,12 @@ def a2d_masks(pred_masks, size, orig_size, threshold=0.5, out=None):
     return out
 
 
-A2D_GROUP_MAX = 16  # TCE_A2D_GROUP_MAX (csrc/tce_rvos_a2d_group.h): samples per launch
+A2D_GROUP_MAX = 16  # TCE_A2D_GROUP_MAX (include/tce_rvos_eval.h): samples per launch
 
 
 def a2d_group_masks(pred_masks_list, logits_list, sizes, orig_sizes, threshold=0.5, outs=None):
     """ops.a2d_masks and ops.sigmoid for the B samples of a group in ONE launch per A2D_GROUP_MAX samples
-    (csrc/tce_rvos_a2d_group.h).  pred_masks_list: B tensors [N,h,w] of one shape (each sample's outputs['pred_masks'][b,0]);
+    (include/tce_rvos_eval.h).  pred_masks_list: B tensors [N,h,w] of one shape (each sample's outputs['pred_masks'][b,0]);
     logits_list: B tensors [N] (outputs['pred_logits'][b,0,:,0]: a strided view is taken as it is); sizes / orig_sizes: B pairs
     (the un-padded model-input size, the dataset's frame size) -> (masks: B uint8 [N,H0_b,W0_b] of 0/1, scores: B float32 [N]).
     Every output byte is ops.a2d_masks', every score ops.sigmoid's.  The tensors' addresses go into the launch's table as they are,
@@ -1179,11 +1179,10 @@ def jf_counts(pred, gt, n, radius, counts=None, ws=None):
 
 
 def rle_decode(counts, nruns, hw, out=None, ws=None):
-    """Planes of P run-length masks on the GPU (csrc/tce_rvos_a2d_score.h: cocoapi rleDecode, the inverse of rle_counts):
+    """Planes of P run-length masks on the GPU (include/tce_rvos_score.h: cocoapi rleDecode, the inverse of rle_counts):
     counts int32 [P,stride] (uint32-valued, as rle_counts leaves them; any stride >= 1), nruns int32 [P], hw = (H, W) -> uint8
     [P,H,W] of 0/1.  Three launches, no host read-back: nruns is read on the device.  out: write into this (any address, e.g. a
     slice of a slab) instead of a new tensor."""
-    from ._lib import lib_raw
     for name, t, dims in (("counts", counts, 2), ("nruns", nruns, 1)):
         if not torch.is_tensor(t) or t.dim() != dims:
             raise ValueError(f"rle_decode: {name} must be {'[P,stride]' if dims == 2 else '[P]'}")
@@ -1195,8 +1194,7 @@ def rle_decode(counts, nruns, hw, out=None, ws=None):
         raise ValueError(f"rle_decode: counts {tuple(counts.shape)} on {counts.device} and nruns {tuple(nruns.shape)} on "
                          f"{nruns.device} must agree in P and device")
     H, W = int(hw[0]), int(hw[1])
-    # the *_ws_bytes queries launch nothing: asked of the library itself, so that a recording (hazard.py) meets the launching entry
-    nbytes = lib_raw().tce_rle_decode_ws_bytes(P, H, W, stride) if min(P, H, W, stride) >= 1 and H * W < 2 ** 31 else -1
+    nbytes = lib().tce_rle_decode_ws_bytes(P, H, W, stride) if min(P, H, W, stride) >= 1 and H * W < 2 ** 31 else -1
     if nbytes < 0:
         raise ValueError(f"rle_decode: unsupported extents P = {P} (1 .. 65535), (H, W) = {(H, W)} (below 2^31 - 4096 pixels), "
                          f"stride = {stride}")
@@ -1210,10 +1208,9 @@ def rle_decode(counts, nruns, hw, out=None, ws=None):
 
 def mask_overlap(pred, gt, counts=None, ws=None):
     """Overlap counts of N uint8 prediction planes [N,H,W] against one ground-truth plane [H,W] on the GPU
-    (csrc/tce_rvos_a2d_score.h) -> int32 [N,3]: per prediction (intersection, prediction area, ground-truth area), any nonzero
+    (include/tce_rvos_score.h) -> int32 [N,3]: per prediction (intersection, prediction area, ground-truth area), any nonzero
     byte counting as set.  Two launches, no host read-back.  The views' addresses go to the launch as they are (any address), so
     both must be contiguous.  counts: write into this (e.g. a slice of a slab) instead of a new tensor."""
-    from ._lib import lib_raw
     for name, t, dims in (("pred", pred, 3), ("gt", gt, 2)):
         if not torch.is_tensor(t) or t.dim() != dims:
             raise ValueError(f"mask_overlap: {name} must be {'[N,H,W]' if dims == 3 else '[H,W]'}")
@@ -1224,7 +1221,7 @@ def mask_overlap(pred, gt, counts=None, ws=None):
         raise ValueError(f"mask_overlap: pred {tuple(pred.shape)} on {pred.device} and gt {tuple(gt.shape)} on {gt.device} must "
                          f"have the same plane and device")
     N, H, W = (int(s) for s in pred.shape)
-    nbytes = lib_raw().tce_mask_overlap_ws_bytes(N, H, W) if min(N, H, W) >= 1 and H * W < 2 ** 31 else -1
+    nbytes = lib().tce_mask_overlap_ws_bytes(N, H, W) if min(N, H, W) >= 1 and H * W < 2 ** 31 else -1
     if nbytes < 0:
         raise ValueError(f"mask_overlap: unsupported extents N = {N} (1 .. 65535), (H, W) = {(H, W)} (below 2^31 - 4096 pixels)")
     dev = pred.device
@@ -1236,13 +1233,12 @@ def mask_overlap(pred, gt, counts=None, ws=None):
 
 
 def png_deflate(planes, rows_per_strip=8, nonzero_value=0, streams=None, nbytes=None, ws=None, codes="fixed"):
-    """The zlib stream of every uint8 plane [P,H,W] on the GPU (csrc/tce_rvos_png.h: PNG filter type 0 on every row, RLE-only
+    """The zlib stream of every uint8 plane [P,H,W] on the GPU (include/tce_rvos_png.h: PNG filter type 0 on every row, RLE-only
     deflate with the fixed Huffman code in strips of rows_per_strip rows, Adler-32) -> (streams uint8 [P,bound], nbytes int32 [P]):
     row p holds its nbytes[p] bytes; what lies behind them is not written.  nonzero_value = v in 1..255: every nonzero byte is
     encoded as v (0/1 masks as 0/255); 0: bytes as they are (label maps).  Three launches, no host read-back.  The planes' address
     goes to the launch as it is (any address), so they must be contiguous.  codes = "dynamic": every strip's block with the cheaper
-    of the fixed code and a Huffman code of its own (csrc/tce_rvos_png_dyn.h); the same sizes of streams and ws, never more bytes."""
-    from ._lib import lib_raw
+    of the fixed code and a Huffman code of its own (tce_png_deflate_dyn_u8); the same sizes of streams and ws, never more bytes."""
     if codes not in ("fixed", "dynamic"):
         raise ValueError(f"png_deflate: codes must be 'fixed' or 'dynamic', got {codes!r}")
     entry = "tce_png_deflate_u8" if codes == "fixed" else "tce_png_deflate_dyn_u8"
@@ -1257,9 +1253,8 @@ def png_deflate(planes, rows_per_strip=8, nonzero_value=0, streams=None, nbytes=
     if not 0 <= v <= 255:
         raise ValueError(f"png_deflate: nonzero_value = {v} outside 0 .. 255")
     ok = min(P, H, W, S) >= 1 and H * W < 2 ** 31 and S < 2 ** 31
-    # the two queries launch nothing: asked of the library itself, so that a recording (hazard.py) meets the launching entry
-    bound = lib_raw().tce_png_stream_bound(H, W, S) if ok else -1
-    need = lib_raw().tce_png_ws_bytes(P, H, W, S) if ok else -1
+    bound = lib().tce_png_stream_bound(H, W, S) if ok else -1
+    need = lib().tce_png_ws_bytes(P, H, W, S) if ok else -1
     if bound < 0 or need < 0:
         raise ValueError(f"png_deflate: unsupported extents P = {P} (1 .. 65535), (H, W) = {(H, W)} (below 2^31 pixels, the stream "
                          f"bound below 2^31 bytes), rows_per_strip = {S} (>= 1, at most 2^22 strips)")

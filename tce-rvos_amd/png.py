@@ -3,11 +3,11 @@
     inference_ytvos.py:354-363   Image.fromarray(mask * 255).convert('L').save(...)       -> mask_pngs(run_video(...)["masks"])
     inference_davis.py:300-311   Image.fromarray(labels), putpalette(palette), save(...)  -> label_pngs(run_video_objects(...)[i]["labels"], palette)
 
-The device makes each plane's complete zlib stream (ops.png_deflate, csrc/tce_rvos_png.h: filter bytes, deflate, Adler-32); the host
+The device makes each plane's complete zlib stream (ops.png_deflate, include/tce_rvos_png.h: filter bytes, deflate, Adler-32); the host
 reads back the byte counts and then only the bytes in use -- a few KB per mask instead of the plane -- and adds the chunk framing
 below.  The files decode to the same pixels as the reference's.  With codes="fixed" (the default: the stream as it always was) they
 are several times LARGER than Pillow's (fixed Huffman codes, run-length matches only, a flush per strip of 8 rows).  With
-codes="dynamic" every strip's block takes the cheaper of the fixed code and a Huffman code of its own (csrc/tce_rvos_png_dyn.h) and
+codes="dynamic" every strip's block takes the cheaper of the fixed code and a Huffman code of its own (tce_png_deflate_dyn_u8) and
 the strips are DYNAMIC_ROWS_PER_STRIP rows: files about the size of Pillow's (DESIGN.md section 3.16 has the measured sizes and
 times), never longer than the fixed stream of the same strips.  The framing functions need neither the GPU nor the shared library.
 """

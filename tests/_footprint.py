@@ -12,7 +12,8 @@ call (recorded, not restated):
   R  results do not depend on unmodelled bytes: with everything outside the union of modelled reads filled with zero
      bytes / a quiet NaN / a large negative finite pattern, the modelled output bytes are bit-identical.
 
-Pure torch + numpy: the same code runs on CPU slabs with plain functions standing in for kernels (test_footprint_cpu.py).
+Pure torch + numpy: the same code runs on CPU slabs with plain functions standing in for kernels (test_footprint_cpu.py);
+only `recorder`, which the GPU cases of the stage models share, needs a device.
 """
 import numpy as np
 import torch
@@ -334,6 +335,18 @@ def check_case(slab, build, record, exempt=(), atomic=None, scratch=(), props="W
                                              f"(max diff {float((a - b_).abs().max()):.3e})")
         info["R"] = len(outs)
     return info
+
+
+def recorder(*names):
+    """-> record(fn, dry) for check_case on the GPU: what fn launches goes through hazard.recording(), so the intervals are the
+    model's own for the real call (not restated), and fn must launch exactly the entry points `names`, in this order."""
+    def record(fn, dry):
+        with hazard.recording(dry=dry) as rec:
+            fn()
+        torch.cuda.synchronize()
+        assert [x.name for x in rec.launches] == list(names)
+        return [x.reads for x in rec.launches], [x.writes for x in rec.launches]
+    return record
 
 
 def first_touched_outside(buf, writes, word, window=64 << 20):

@@ -1,4 +1,4 @@
-"""Plain numpy / Python restatement of the device's PNG stream (csrc/tce_rvos_png.h): RLE-only deflate
+"""Plain numpy / Python restatement of the device's PNG stream (include/tce_rvos_png.h): RLE-only deflate
 with the fixed Huffman code of RFC 1951, PNG filter type 0 on every row, strips of rows_per_strip rows that are independent of
 each other, and the Adler-32 of the filtered bytes.  Written from the rule's text, one token at a time into a list of bits; it
 shares nothing with the kernel or with tce_rvos_amd/png.py."""

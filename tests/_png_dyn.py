@@ -1,4 +1,4 @@
-"""Plain Python restatement of the device's PNG stream with codes = "dynamic" (csrc/tce_rvos_png_dyn.h):
+"""Plain Python restatement of the device's PNG stream with codes = "dynamic" (include/tce_rvos_png.h):
 the stream of tests/_png.py in which every strip's block is written either with the fixed Huffman code or with a code of its own
 (BTYPE = 10), whichever takes fewer bits.  Written from the rule's text: the tree is a list of symbol groups that are merged, a
 symbol's code length is the number of merges it took part in.  It shares the token rule, the bit writer and the Adler pair with

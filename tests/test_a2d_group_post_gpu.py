@@ -1,12 +1,15 @@
-"""GPU: the A2D-Sentences / JHMDB-Sentences output stage for a group of samples (csrc/tce_rvos_a2d_group.h, ops.a2d_group_masks,
+"""GPU: the A2D-Sentences / JHMDB-Sentences output stage for a group of samples (include/tce_rvos_eval.h, ops.a2d_group_masks,
 A2DSentencesPostProcess(grouped=True)) against the per-sample launches it replaces: every byte ops.a2d_masks', every score
-ops.sigmoid's, and sample 0 of the first case against the reference class's fixture (tests/golden/a2d_post_cases.npz)."""
+ops.sigmoid's, sample 0 of the first case against the reference class's fixture (tests/golden/a2d_post_cases.npz), and the
+entry's access model against the bytes the launch touches (tests/_footprint.py)."""
 import os
 
 import pytest
 import torch
 
 import _a2d
+import _footprint as fp
+from tce_rvos_amd import _lib, hazard
 
 pytestmark = pytest.mark.gpu
 
@@ -119,6 +122,79 @@ def test_grouped_post_processor_equals_the_per_sample_one(three, rle):
             assert r["rle_masks"] == w["rle_masks"]
     for b, k in ((0, 0), (2, 1), (3, 2)):
         assert torch.equal(got[b]["masks"][:, 0], t["solo_m"][k])
+
+
+# --------------------------------------------------------------------------------------------- the recorder and the footprint
+def test_hazard_recording_lists_the_one_entry(three):
+    from tce_rvos_amd import ops
+    t = three
+    with hazard.recording() as rec:
+        masks, scores = ops.a2d_group_masks(t["pm"], t["lg"], [p[0] for p in t["pairs"]], [p[1] for p in t["pairs"]])
+    torch.cuda.synchronize()
+    assert [x.name for x in rec.launches] == ["tce_a2d_group_masks_u8"] and rec.analyse().clean
+    for b in range(3):
+        assert torch.equal(masks[b], t["masks"][b]) and torch.equal(scores[b], t["scores"][b]), b
+
+
+@pytest.fixture(scope="module")
+def slab():
+    s = fp.Slab(64 << 20, device="cuda")
+    yield s
+    del s
+    torch.cuda.empty_cache()
+
+
+def _group_case(S, N, h, w, samples):
+    """samples: per sample (fh, fw, H0, W0, the bytes `out` starts into its buffer, logit_stride).  Every device buffer of the call in
+    the slab: the mask planes and the scores of all samples in one buffer each, logits and out per sample.  The table is a host
+    array, read by the entry point at the call: it stays outside the slab."""
+    B = len(samples)
+    pm = S.randn("masks", (B, N * h * w), scale=3.0)
+    scores = S.alloc("scores", (B, N))
+    table = (_lib.A2dGroupSample * B)()
+    lg, raws = [], []
+    for b, (fh, fw, H0, W0, shift, stride) in enumerate(samples):
+        lg.append(S.randn(f"logits{b}", (N * stride,), scale=2.0))
+        raws.append(S.alloc(f"out{b}", (shift + N * H0 * W0 + 3,), dtype=torch.uint8))
+        e = table[b]
+        e.masks, e.logits, e.out, e.scores = pm[b].data_ptr(), lg[b].data_ptr(), raws[b].data_ptr() + shift, scores[b].data_ptr()
+        e.fh, e.fw, e.H0, e.W0, e.logit_stride = fh, fw, H0, W0, stride
+
+    def fn():
+        _lib.check(_lib.lib().tce_a2d_group_masks_u8(table, B, N, h, w, 0.5, torch.cuda.current_stream().cuda_stream),
+                   "tce_a2d_group_masks_u8")
+    fn.check = lambda: (pm, lg, raws, scores)
+    return fn
+
+
+GROUP_FOOTPRINT = [
+    # the second sample's planes of 20 x 30 x 3 = 1800 bytes take more than one 1024-byte workgroup; its logits are 2 floats apart
+    ("two_samples_3x4x6_to_9x11_and_20x30_addresses_1_and_2", dict(N=3, h=4, w=6, samples=[(13, 20, 9, 11, 1, 1), (16, 24, 20, 30, 2, 2)])),
+    ("a_full_table_of_16_samples_1x2x2_to_3x5", dict(N=1, h=2, w=2, samples=[(7, 8, 3, 5, b % 4, 1) for b in range(16)])),
+]
+
+
+@pytest.mark.parametrize("tag,kw", GROUP_FOOTPRINT, ids=[c[0] for c in GROUP_FOOTPRINT])
+def test_a2d_group_masks_footprint(slab, tag, kw):
+    """W, O and R of tests/_footprint.py, no exemptions: nothing outside the samples' out and scores is written (the bytes around the
+    oddly placed planes included), every output byte and every score is written, and the result depends on no byte outside the
+    samples' mask planes and the N logits of each -- the floats between strided logits included."""
+    from tce_rvos_amd import ops
+    info = fp.check_case(slab, lambda S: _group_case(S, **kw), fp.recorder("tce_a2d_group_masks_u8"), props="WOR",
+                         sync=torch.cuda.synchronize, label=tag)
+    print(f"{tag}: read {info['read_bytes']} written {info['written_bytes']} guard {info['guard_bytes']} untouched-in-buffers {info['pad_bytes']}")
+    assert (info["W"], info["O"], info["R"]) == (2, 2, 3) and info["exempt"] == []
+    N, h, w, samples = kw["N"], kw["h"], kw["w"], kw["samples"]
+    assert info["read_bytes"] == len(samples) * (N * h * w + N) * 4
+    assert info["written_bytes"] == sum(N * s[2] * s[3] + N * 4 for s in samples)
+    slab.begin(0)
+    fn = _group_case(slab, **kw)
+    fn()
+    pm, lg, raws, scores = fn.check()
+    for b, (fh, fw, H0, W0, shift, stride) in enumerate(samples):
+        want = ops.a2d_masks(pm[b].reshape(N, h, w).clone(), (fh, fw), (H0, W0))
+        assert torch.equal(raws[b][shift:shift + N * H0 * W0], want.reshape(-1)), b
+        assert torch.equal(scores[b], ops.sigmoid(lg[b][::stride].clone())), b
 
 
 def test_rejections():

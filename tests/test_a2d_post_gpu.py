@@ -190,17 +190,6 @@ def slab():
     torch.cuda.empty_cache()
 
 
-def _recorder(name):
-    def record(fn, dry):
-        """The model's own intervals for the real call: what fn launches goes through hazard.recording() (as test_footprint_gpu does)."""
-        with hazard.recording(dry=dry) as rec:
-            fn()
-        torch.cuda.synchronize()
-        assert [x.name for x in rec.launches] == [name]
-        return [x.reads for x in rec.launches], [x.writes for x in rec.launches]
-    return record
-
-
 def _masks_case(S, N, h, w, fh, fw, H0, W0, shift):
     pm = S.randn("masks", (N, h * w), scale=3.0)
     total = N * H0 * W0
@@ -226,7 +215,7 @@ def test_a2d_masks_footprint(slab, tag, kw):
     """W, O and R of tests/_footprint.py, no exemptions: nothing outside `out` is written (the bytes around an oddly placed plane
     included), every output byte is written, and the result depends on no byte outside the N mask planes."""
     from tce_rvos_amd import ops
-    info = fp.check_case(slab, lambda S: _masks_case(S, **kw), _recorder("tce_a2d_masks_u8"), props="WOR", sync=torch.cuda.synchronize, label=tag)
+    info = fp.check_case(slab, lambda S: _masks_case(S, **kw), fp.recorder("tce_a2d_masks_u8"), props="WOR", sync=torch.cuda.synchronize, label=tag)
     print(f"{tag}: read {info['read_bytes']} written {info['written_bytes']} guard {info['guard_bytes']} untouched-in-buffers {info['pad_bytes']}")
     assert (info["W"], info["O"], info["R"]) == (2, 2, 3) and info["exempt"] == []
     assert info["read_bytes"] == kw["N"] * kw["h"] * kw["w"] * 4
@@ -265,7 +254,7 @@ def test_rle_counts_footprint(slab, tag, kw):
     """W, O and R with no exemption: every word of counts is written (the counts, then zeros), so the whole of counts and nruns is
     held to O and compared under R; ws is scratch (R fills it before the run: the second launch must not consume a record the
     first did not write)."""
-    info = fp.check_case(slab, lambda S: _rle_case(S, **kw), _recorder("tce_rle_counts_u32"), scratch=("ws",), props="WOR",
+    info = fp.check_case(slab, lambda S: _rle_case(S, **kw), fp.recorder("tce_rle_counts_u32"), scratch=("ws",), props="WOR",
                          sync=torch.cuda.synchronize, label=tag)
     print(f"{tag}: read {info['read_bytes']} written {info['written_bytes']} guard {info['guard_bytes']}")
     assert (info["W"], info["O"], info["R"]) == (2, 2, 3) and info["exempt"] == []

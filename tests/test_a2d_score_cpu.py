@@ -1,8 +1,7 @@
-"""CPU: the staged A2D scoring entries against their header (what test_host_cpu.py does for the headers of include/), the
-run-length string reader, and the host scoring functions on integer counts -- against the reference's own function through the
+"""CPU: the A2D scoring entries' access models on hand-made blocks (their header against its binding table, the exported symbols
+and the checker's tables: tests/test_host_cpu.py, with every other header), the run-length string reader, and the host scoring functions on integer counts -- against the reference's own function through the
 fixture (tests/golden/a2d_score_cases.npz), the plain-loop restatement of COCOeval (tests/_a2d_score.py) and cases derived by
 hand.  No AP number here was compared with pycocotools' own output (it is on no machine this project can use)."""
-import ctypes
 import os
 import pickle
 import re
@@ -32,41 +31,50 @@ def cases():
     return S.load_cases(FIXTURE)
 
 
-# ---------------------------------------------------------------------------------------------------------- the staged table
-def test_staged_symbols_declared_bound_exported_and_outside_the_pinned_tables(built_lib):
-    from tce_rvos_amd import _lib, hazard
-    from tce_rvos_amd import build as b
-    header = os.path.join(ROOT, "tce-rvos_amd", "csrc", "tce_rvos_a2d_score.h")
-    assert os.path.realpath(header) == os.path.realpath(_lib.STAGED_HEADER)
-    declared = set(re.findall(r"\b(tce_[a-z0-9_]+)\s*\(", open(header).read()))
-    assert declared == set(_lib.STAGED_SIGNATURES) == set(LAUNCHING) | set(QUERIES), declared ^ set(_lib.STAGED_SIGNATURES)
-    l, bound = ctypes.CDLL(built_lib), _lib.lib()  # lib() applies the table after those of HEADERS
-    for name, (res, args) in _lib.STAGED_SIGNATURES.items():
-        assert hasattr(l, name), name
-        fn = getattr(bound, name)
-        assert fn.restype is res and list(fn.argtypes) == args, name
-        assert all(name not in table for table in _lib.HEADERS.values()), name
-        assert name not in hazard.MODELS and name not in hazard.NOT_LAUNCHES, name
-    assert _lib.STAGED_SIGNATURES not in list(_lib.HEADERS.values())
-    assert "tce_rvos_a2d_score.h" not in os.listdir(os.path.join(ROOT, "include"))
-    assert bound.tce_abi_version() == 5
-    assert "a2d_score.hip" in b.SOURCES
-    assert os.path.realpath(header) in {os.path.realpath(d) for d in b.dependencies()}  # every object is rebuilt when it changes
-    text = open(header).read()
-    for q in QUERIES:  # the header says which entries launch nothing
+# ------------------------------------------------------------------------------------------- the header and the access models
+# (symbols, binding table, exports, argtypes, models / launch-free names of include/tce_rvos_score.h: tests/test_host_cpu.py)
+def test_the_header_says_which_entries_launch_nothing():
+    text = open(os.path.join(ROOT, "include", "tce_rvos_score.h")).read()
+    for q in QUERIES:
         assert re.search(rf"{q}\([^;]*;\s*/\*[^*]*launches nothing", text), q
 
 
-@pytest.mark.parametrize("name", LAUNCHING + QUERIES)
-def test_hazard_proxy_refuses_every_staged_entry(built_lib, name):
-    """The choice: the two launch-free *_ws_bytes queries keep their tce_ spelling and are refused inside a recorded launch program
-    like the launching entries (there is no access model and no NOT_LAUNCHES line for them); ops.py asks them of the library
-    itself (_lib.lib_raw), so a recording trips over the launching entry."""
+def test_access_models_on_hand_made_blocks(built_lib):
     from tce_rvos_amd import _lib, hazard
-    proxy = hazard._LibProxy(_lib.lib(), hazard.Recorder())
-    with pytest.raises(RuntimeError, match=f"no access model for {name}"):
-        getattr(proxy, name)
-    assert callable(getattr(_lib.lib_raw(), name))
+    l = _lib.lib()
+    # P = 3, H = 5, W = 7, stride = 36: 35-byte planes from an odd address; every e_i and one segment sum per row in ws
+    assert l.tce_rle_decode_ws_bytes(3, 5, 7, 36) == 448
+    rd, wr = hazard.MODELS["tce_rle_decode_u8"]((0x100000, 0x200000, 0x300001, 0x400000, 3, 5, 7, 36, 0))
+    assert hazard.union(*rd).tolist() == [[0x100000, 0x1001B0], [0x200000, 0x20000C], [0x400000, 0x4001C0]]
+    assert hazard.union(*wr).tolist() == [[0x300001, 0x30006A], [0x400000, 0x4001C0]]
+    # N = 3, H = 5, W = 7: pred and gt on odd addresses, one tile
+    assert l.tce_mask_overlap_ws_bytes(3, 5, 7) == 32
+    rd, wr = hazard.MODELS["tce_mask_overlap_i32"]((0x500001, 0x600003, 0x700000, 0x800000, 3, 5, 7, 0))
+    assert hazard.union(*rd).tolist() == [[0x500001, 0x50006A], [0x600003, 0x600026], [0x800000, 0x800020]]
+    assert hazard.union(*wr).tolist() == [[0x700000, 0x700024], [0x800000, 0x800020]]
+
+
+class _StandIn:
+    """Stands where the CDLL stands under a dry hazard._LibProxy: every entry answers with its own name."""
+
+    def __getattr__(self, name):
+        return lambda *a: name
+
+
+def test_recording_proxy_records_the_launching_entries_and_passes_the_queries_through(built_lib):
+    from tce_rvos_amd import hazard
+    rec = hazard.Recorder()
+    proxy = hazard._LibProxy(_StandIn(), rec, dry=True)
+    assert proxy.tce_rle_decode_u8(0x100000, 0x200000, 0x300001, 0x400000, 3, 5, 7, 36, 0) == 0
+    assert proxy.tce_mask_overlap_i32(0x500001, 0x600003, 0x700000, 0x800000, 3, 5, 7, 0) == 0
+    assert [x.name for x in rec.launches] == list(LAUNCHING)
+    assert rec.launches[0].reads.tolist() == [[0x100000, 0x1001B0], [0x200000, 0x20000C], [0x400000, 0x4001C0]]
+    assert rec.launches[0].writes.tolist() == [[0x300001, 0x30006A], [0x400000, 0x4001C0]]
+    assert rec.launches[1].reads.tolist() == [[0x500001, 0x50006A], [0x600003, 0x600026], [0x800000, 0x800020]]
+    assert rec.launches[1].writes.tolist() == [[0x700000, 0x700024], [0x800000, 0x800020]]
+    for q in QUERIES:  # passed through, not recorded
+        assert getattr(proxy, q)(3, 5, 7, 36) == q
+    assert len(rec.launches) == 2
 
 
 def test_extents_are_rejected_before_anything_is_launched(built_lib):

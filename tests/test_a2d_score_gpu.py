@@ -1,6 +1,6 @@
-"""A2D-Sentences / JHMDB-Sentences scoring on the GPU: tce_rle_decode_u8 and tce_mask_overlap_i32 (csrc/tce_rvos_a2d_score.h)
+"""A2D-Sentences / JHMDB-Sentences scoring on the GPU: tce_rle_decode_u8 and tce_mask_overlap_i32 (include/tce_rvos_score.h)
 against numpy (tests/_a2d.py: rle_decode is the yardstick; the contract's own formula for counts that are no mask's run lengths),
-and a2d_score.A2DScorer end to end against the fixture of the reference's own function (tests/golden/a2d_score_cases.npz) and the
+their access models against the bytes the launches touch (tests/_footprint.py), and a2d_score.A2DScorer end to end against the fixture of the reference's own function (tests/golden/a2d_score_cases.npz) and the
 plain-loop restatement of COCOeval (tests/_a2d_score.py; not pycocotools)."""
 import os
 
@@ -10,6 +10,8 @@ import torch
 
 import _a2d
 import _a2d_score as S
+import _footprint as fp
+from tce_rvos_amd import _lib, hazard
 
 pytestmark = pytest.mark.gpu
 
@@ -286,6 +288,142 @@ def test_overlap_rejections():
         ops.mask_overlap(p, g, counts=torch.zeros(2, 3, dtype=torch.int64, device="cuda"))
     with pytest.raises(ValueError, match="counts"):
         ops.mask_overlap(p, g, counts=torch.zeros(2, 6, dtype=torch.int32, device="cuda")[:, ::2])
+
+
+# --------------------------------------------------------------------------------------------- the recorder and the footprint
+def test_hazard_recording_lists_the_one_entry_of_each_wrapper():
+    from tce_rvos_amd import ops
+    H, W = 37, 53
+    masks = _blob_masks(H, W, 12)
+    counts, nruns = _pack([_a2d.rle_counts(m) for m in masks], H * W + 1)
+    pred, gt = _at_odd_addresses(*_planes(5, H, W, 43))
+    want = ops.rle_decode(counts, nruns, (H, W)), ops.mask_overlap(pred, gt)
+    with hazard.recording() as rec:
+        planes = ops.rle_decode(counts, nruns, (H, W))
+    with hazard.recording() as rec2:
+        overlap = ops.mask_overlap(pred, gt)
+    torch.cuda.synchronize()
+    assert [x.name for x in rec.launches] == ["tce_rle_decode_u8"] and [x.name for x in rec2.launches] == ["tce_mask_overlap_i32"]
+    assert rec.analyse().clean and rec2.analyse().clean
+    assert torch.equal(planes, want[0]) and torch.equal(overlap, want[1]) and np.array_equal(planes.cpu().numpy(), masks)
+
+
+@pytest.fixture(scope="module")
+def slab():
+    s = fp.Slab(64 << 20, device="cuda")
+    yield s
+    del s
+    torch.cuda.empty_cache()
+
+
+def _stream():
+    return torch.cuda.current_stream().cuda_stream
+
+
+def _decode_case(S_, masks, nruns, stride, shift):
+    """Every buffer of the call in the slab; out starts `shift` bytes into its buffer.  nruns: None (the rows' own lengths) or the
+    values to pass instead."""
+    P, H, W = masks.shape
+    rows = [_a2d.rle_counts(m) for m in masks]
+    buf = np.zeros((P, stride), dtype=np.uint32)
+    for p, r in enumerate(rows):
+        buf[p, :len(r)] = r
+    counts = S_.put("counts", buf.view(np.int32))
+    nr = S_.put("nruns", [len(r) for r in rows] if nruns is None else nruns, dtype=torch.int32)
+    raw = S_.alloc("out", (shift + P * H * W + 3,), dtype=torch.uint8)
+    ws = S_.alloc("ws", (_lib.lib_raw().tce_rle_decode_ws_bytes(P, H, W, stride) // 8,), dtype=torch.int64)
+    out = raw.data_ptr() + shift
+
+    def fn():
+        _lib.check(_lib.lib().tce_rle_decode_u8(counts.data_ptr(), nr.data_ptr(), out, ws.data_ptr(), P, H, W, stride, _stream()),
+                   "tce_rle_decode_u8")
+    fn.check = lambda: raw[shift:shift + P * H * W].view(P, H, W)
+    return fn
+
+
+def _decode_footprint_cases():
+    rng = np.random.default_rng(51)
+    small = (rng.random((3, 5, 7)) < 0.5).astype(np.uint8)
+    H, W = 33, 65
+    board = np.ascontiguousarray(((np.arange(H * W) + 1) & 1).astype(np.uint8).reshape(W, H).T)[None]  # starts with a 1: H*W + 1 runs
+    return [
+        # 35-byte planes, so planes 2 and 3 start on odd addresses; the row of plane 1 is not in use at all
+        ("three_5x7_planes_stride_36_one_row_unused_address_1", dict(masks=small, nruns="second row 0", stride=36, shift=1)),
+        # 2146 runs: more than two segments of 1024 counts
+        ("checkerboard_33x65_of_2146_runs_address_3", dict(masks=board, nruns=None, stride=H * W + 1, shift=3)),
+    ]
+
+
+DECODE_FOOTPRINT = _decode_footprint_cases()
+
+
+@pytest.mark.parametrize("tag,kw", DECODE_FOOTPRINT, ids=[c[0] for c in DECODE_FOOTPRINT])
+def test_rle_decode_footprint(slab, tag, kw):
+    """W, O and R of tests/_footprint.py: nothing outside out and ws is written (the bytes around the oddly placed planes included),
+    every byte of out is written, and the result depends on no byte outside counts and nruns, nor on what ws held (scratch: R fills
+    it before the run).  ws is exempt from O: the e_i behind a row's last run in use and the pad to 8 bytes are never written."""
+    masks, stride = kw["masks"], kw["stride"]
+    P, H, W = masks.shape
+    lens = [len(_a2d.rle_counts(m)) for m in masks]
+    nruns = None if kw["nruns"] is None else [lens[0], 0] + lens[2:]
+    assert max(lens) <= stride and (kw["nruns"] is None or masks[1].any())
+    info = fp.check_case(slab, lambda S_: _decode_case(S_, masks, nruns, stride, kw["shift"]), fp.recorder("tce_rle_decode_u8"),
+                         exempt=("ws",), scratch=("ws",), props="WOR", sync=torch.cuda.synchronize, label=tag)
+    print(f"{tag}: read {info['read_bytes']} written {info['written_bytes']} guard {info['guard_bytes']} untouched-in-buffers {info['pad_bytes']}")
+    assert (info["W"], info["O"], info["R"]) == (2, 2, 3) and info["exempt"] == ["ws"]
+    wsb = (P * stride + P * -(-stride // 1024)) * 4 + 7 & ~7
+    assert info["read_bytes"] == P * stride * 4 + P * 4 + wsb and info["written_bytes"] == P * H * W + wsb
+    slab.begin(0)
+    fn = _decode_case(slab, masks, nruns, stride, kw["shift"])
+    fn()
+    torch.cuda.synchronize()
+    want = masks.copy()
+    if nruns is not None:
+        want[1] = 0  # a row with no run in use decodes to zeros
+    assert np.array_equal(fn.check().cpu().numpy(), want)
+
+
+def _overlap_case(S_, N, H, W, shift_p, shift_g, seed):
+    pred, gt = _planes(N, H, W, seed)
+    hp, hg = np.zeros(shift_p + pred.size + 3, np.uint8), np.zeros(shift_g + gt.size + 3, np.uint8)
+    hp[shift_p:shift_p + pred.size], hg[shift_g:shift_g + gt.size] = pred.reshape(-1), gt.reshape(-1)
+    rp, rg = S_.put("pred", hp), S_.put("gt", hg)
+    counts = S_.alloc("counts", (N * 3,), dtype=torch.int32)
+    ws = S_.alloc("ws", (_lib.lib_raw().tce_mask_overlap_ws_bytes(N, H, W) // 8,), dtype=torch.int64)
+    p, g = rp.data_ptr() + shift_p, rg.data_ptr() + shift_g
+
+    def fn():
+        _lib.check(_lib.lib().tce_mask_overlap_i32(p, g, counts.data_ptr(), ws.data_ptr(), N, H, W, _stream()), "tce_mask_overlap_i32")
+    fn.check = lambda: (counts.view(N, 3), S.overlap_counts(pred, gt))
+    return fn
+
+
+OVERLAP_FOOTPRINT = [
+    ("three_5x7_planes_one_tile_addresses_1_and_3", dict(N=3, H=5, W=7, shift_p=1, shift_g=3, seed=52)),
+    # 2145 bytes: two full tiles of 1024 and a partial one
+    ("two_33x65_planes_three_tiles_addresses_2_and_1", dict(N=2, H=33, W=65, shift_p=2, shift_g=1, seed=53)),
+]
+
+
+@pytest.mark.parametrize("tag,kw", OVERLAP_FOOTPRINT, ids=[c[0] for c in OVERLAP_FOOTPRINT])
+def test_mask_overlap_footprint(slab, tag, kw):
+    """W, O and R: nothing outside counts and ws is written, every word of counts is written, and the result depends on no byte
+    outside pred and gt -- the bytes around the oddly placed planes included -- nor on what ws held.  ws is exempt from O for its
+    pad alone: both cases have an odd number of partial sums, so the last 4 of its bytes (the pad to 8) are never written."""
+    info = fp.check_case(slab, lambda S_: _overlap_case(S_, **kw), fp.recorder("tce_mask_overlap_i32"), exempt=("ws",), scratch=("ws",),
+                         props="WOR", sync=torch.cuda.synchronize, label=tag)
+    print(f"{tag}: read {info['read_bytes']} written {info['written_bytes']} guard {info['guard_bytes']} untouched-in-buffers {info['pad_bytes']}")
+    assert (info["W"], info["O"], info["R"]) == (2, 2, 3) and info["exempt"] == ["ws"]
+    N, HW = kw["N"], kw["H"] * kw["W"]
+    tiles = -(-HW // 1024)
+    wsb = (N * tiles * 2 + tiles) * 4 + 4
+    assert info["read_bytes"] == N * HW + HW + wsb and info["written_bytes"] == N * 12 + wsb
+    slab.begin(0)
+    fn = _overlap_case(slab, **kw)
+    fn()
+    torch.cuda.synchronize()
+    got, want = fn.check()
+    assert np.array_equal(got.cpu().numpy(), want)
 
 
 # ------------------------------------------------------------------------------------------------------------ the scorer

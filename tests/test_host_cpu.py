@@ -23,13 +23,18 @@ def _declared(header):
 
 
 # header, its symbols spelled out (None: its table is the record), those of them that launch nothing (None: not spelled out; "all":
-# every one), its translation unit (None: several)
+# every one), its translation units (None: several)
 HEADER_CASES = [
     ("tce_rvos.h", None, None, None),
     ("tce_rvos_debug.h", None, "all", None),
-    ("tce_rvos_video.h", {"tce_label_objects_u8"}, set(), "label.hip"),
-    ("tce_rvos_eval.h", {"tce_a2d_masks_u8", "tce_rle_ws_bytes", "tce_rle_counts_u32"}, {"tce_rle_ws_bytes"}, "eval.hip"),
-    ("tce_rvos_score.h", {"tce_jf_ws_bytes", "tce_jf_counts_i32"}, {"tce_jf_ws_bytes"}, "score.hip"),
+    ("tce_rvos_video.h", {"tce_label_objects_u8"}, set(), ("label.hip",)),
+    ("tce_rvos_eval.h", {"tce_a2d_masks_u8", "tce_rle_ws_bytes", "tce_rle_counts_u32", "tce_a2d_group_masks_u8"}, {"tce_rle_ws_bytes"},
+     ("eval.hip", "a2d_group.hip")),
+    ("tce_rvos_score.h", {"tce_jf_ws_bytes", "tce_jf_counts_i32", "tce_rle_decode_ws_bytes", "tce_rle_decode_u8",
+                          "tce_mask_overlap_ws_bytes", "tce_mask_overlap_i32"},
+     {"tce_jf_ws_bytes", "tce_rle_decode_ws_bytes", "tce_mask_overlap_ws_bytes"}, ("score.hip", "a2d_score.hip")),
+    ("tce_rvos_png.h", {"tce_png_stream_bound", "tce_png_ws_bytes", "tce_png_deflate_u8", "tce_png_deflate_dyn_u8"},
+     {"tce_png_stream_bound", "tce_png_ws_bytes"}, ("png.hip",)),
 ]
 
 
@@ -59,7 +64,7 @@ def test_header_symbols_bound_exported_and_modelled(built_lib, header, symbols, 
     assert set(hazard.MODELS) <= every and hazard.NOT_LAUNCHES <= every
     # every object is rebuilt when the header changes, and the stage's translation unit is built
     assert os.path.realpath(os.path.join(ROOT, "include", header)) in {os.path.realpath(d) for d in b.dependencies()}
-    assert source is None or source in b.SOURCES
+    assert source is None or all(src in b.SOURCES for src in source)
 
 
 def test_bad_arguments_are_rejected_with_a_message(built_lib):

@@ -201,15 +201,6 @@ def slab():
     torch.cuda.empty_cache()
 
 
-def _record(fn, dry):
-    """The model's own intervals for the real call: what fn launches goes through hazard.recording() (as test_footprint_gpu does)."""
-    with hazard.recording(dry=dry) as rec:
-        fn()
-    torch.cuda.synchronize()
-    assert [x.name for x in rec.launches] == ["tce_jf_counts_i32"]
-    return [x.reads for x in rec.launches], [x.writes for x in rec.launches]
-
-
 def _jf_case(S, T, n, H, W, radius, shift_p, shift_g):
     """Every buffer of the call in the slab; the label planes start `shift` bytes into their buffers (odd base addresses), labels
     0 .. n+1 so that some pixels carry a label above n."""
@@ -243,7 +234,7 @@ def test_jf_counts_footprint(slab, tag, kw):
     """W, O and R of tests/_footprint.py, no exemptions: nothing outside counts and ws is written, every word of counts (and of ws)
     is written, and the result depends on no byte outside pred, gt -- the bytes around the oddly placed planes included -- and on
     nothing ws held before the call (ws is scratch: R fills it before the run)."""
-    info = fp.check_case(slab, lambda S: _jf_case(S, **kw), _record, scratch=("ws",), props="WOR", sync=torch.cuda.synchronize, label=tag)
+    info = fp.check_case(slab, lambda S: _jf_case(S, **kw), fp.recorder("tce_jf_counts_i32"), scratch=("ws",), props="WOR", sync=torch.cuda.synchronize, label=tag)
     print(f"{tag}: read {info['read_bytes']} written {info['written_bytes']} guard {info['guard_bytes']} untouched-in-buffers {info['pad_bytes']}")
     assert (info["W"], info["O"], info["R"]) == (2, 2, 3) and info["exempt"] == []
     T, n, H, W = kw["T"], kw["n"], kw["H"], kw["W"]

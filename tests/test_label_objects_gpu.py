@@ -11,7 +11,7 @@ import torch
 import _davis
 import _footprint as fp
 from _util import synth_frames
-from tce_rvos_amd import _lib, hazard
+from tce_rvos_amd import _lib
 
 pytestmark = pytest.mark.gpu
 
@@ -97,15 +97,6 @@ def slab():
     torch.cuda.empty_cache()
 
 
-def _record(fn, dry):
-    """The model's own intervals for the real call: what fn launches goes through hazard.recording() (as test_footprint_gpu does)."""
-    with hazard.recording(dry=dry) as rec:
-        fn()
-    torch.cuda.synchronize()
-    assert [x.name for x in rec.launches] == ["tce_label_objects_u8"]
-    return [x.reads for x in rec.launches], [x.writes for x in rec.launches]
-
-
 def _label_case(S, n, T, Q, K, h, w, H0, W0, order, shift):
     """Every device buffer of the call in the slab, objects allocated in index order and listed in `order`; labels start `shift`
     bytes into their buffer.  The table is a host array, read by the entry point at launch time: it stays outside the slab."""
@@ -138,7 +129,7 @@ def test_label_objects_footprint(slab, tag, kw):
     oddly placed label map included), every label byte and every best_query word is written, and the result depends on no byte
     outside the n logits and n masks blocks."""
     from tce_rvos_amd import ops
-    info = fp.check_case(slab, lambda S: _label_case(S, **kw), _record, props="WOR", sync=torch.cuda.synchronize, label=tag)
+    info = fp.check_case(slab, lambda S: _label_case(S, **kw), fp.recorder("tce_label_objects_u8"), props="WOR", sync=torch.cuda.synchronize, label=tag)
     print(f"{tag}: read {info['read_bytes']} written {info['written_bytes']} guard {info['guard_bytes']} untouched-in-buffers {info['pad_bytes']}")
     assert (info["W"], info["O"], info["R"]) == (2, 2, 3) and info["exempt"] == []
     n, T = kw["n"], kw["T"]

@@ -1,8 +1,7 @@
 """CPU: the PNG stage without a GPU -- the restatement of the stream (tests/_png.py) against zlib and Pillow, the host framing of
 tce_rvos_amd/png.py against Pillow and against the reference's own save lines (inference_ytvos.py:354-363,
-inference_davis.py:308-311, run through Pillow on the same arrays), the staged table against its header, the two queries against
+inference_davis.py:308-311, run through Pillow on the same arrays), the access model on a hand-made block, the two queries against
 the bound's formula, and the extents the entries reject before anything is launched."""
-import ctypes
 import io
 import os
 import re
@@ -133,38 +132,48 @@ def test_frame_layout_and_errors(tmp_path):
     assert open(paths[1], "rb").read() == blob
 
 
-# ------------------------------------------------------------------------------------------------------------ the staged table
-def test_png_symbols_declared_bound_exported_and_outside_the_pinned_tables(built_lib):
-    from tce_rvos_amd import _lib, hazard
+# -------------------------------------------------------------------------------------------- the header and the access model
+# (symbols, binding table, exports, argtypes, models / launch-free names of include/tce_rvos_png.h: tests/test_host_cpu.py)
+def test_the_header_says_which_entries_launch_nothing_and_png_is_the_last_source():
     from tce_rvos_amd import build as b
-    header = os.path.join(ROOT, "tce-rvos_amd", "csrc", "tce_rvos_png.h")
-    assert os.path.realpath(header) == os.path.realpath(_lib.PNG_HEADER)
-    text = open(header).read()
-    declared = set(re.findall(r"\b(tce_[a-z0-9_]+)\s*\(", text))
-    assert declared == set(_lib.PNG_SIGNATURES) == set(LAUNCHING) | set(QUERIES), declared ^ set(_lib.PNG_SIGNATURES)
-    l, bound = ctypes.CDLL(built_lib), _lib.lib()
-    for name, (res, args) in _lib.PNG_SIGNATURES.items():
-        assert hasattr(l, name), name
-        fn = getattr(bound, name)
-        assert fn.restype is res and list(fn.argtypes) == args, name
-        assert all(name not in table for table in _lib.HEADERS.values()) and name not in _lib.STAGED_SIGNATURES, name
-        assert name not in hazard.MODELS and name not in hazard.NOT_LAUNCHES, name
-    assert _lib.PNG_SIGNATURES not in list(_lib.HEADERS.values())
-    assert "tce_rvos_png.h" not in os.listdir(os.path.join(ROOT, "include"))
-    assert bound.tce_abi_version() == 5
-    assert b.SOURCES[-1] == "png.hip"
-    assert os.path.realpath(header) in {os.path.realpath(d) for d in b.dependencies()}
+    text = open(os.path.join(ROOT, "include", "tce_rvos_png.h")).read()
     for q in QUERIES:
         assert re.search(rf"{q}\([^;]*;\s*/\*[^*]*launches nothing", text), q
+    assert b.SOURCES[-1] == "png.hip"
 
 
-@pytest.mark.parametrize("name", LAUNCHING + QUERIES)
-def test_hazard_proxy_refuses_every_png_entry(built_lib, name):
+# P = 2, H = 5, W = 7, S = 2: three strips a plane (16, 16 and 8 filtered bytes: at most 24, 24 and 15 stream bytes), planes and
+# streams on odd addresses; every row of streams is named in full
+BLOCK = (0x100001, 0x200003, 0x300000, 0x400000, 2, 5, 7, 2, 255, 0)
+BLOCK_READS = [[0x100001, 0x100047], [0x400000, 0x4000D8]]
+BLOCK_WRITES = [[0x200003, 0x200091], [0x300000, 0x300008], [0x400000, 0x4000D8]]
+
+
+def test_access_model_on_a_hand_made_block(built_lib):
     from tce_rvos_amd import _lib, hazard
-    proxy = hazard._LibProxy(_lib.lib(), hazard.Recorder())
-    with pytest.raises(RuntimeError, match=f"no access model for {name}"):
-        getattr(proxy, name)
-    assert callable(getattr(_lib.lib_raw(), name))
+    l = _lib.lib()
+    assert l.tce_png_stream_bound(5, 7, 2) == 71 and l.tce_png_ws_bytes(2, 5, 7, 2) == 216
+    rd, wr = hazard.MODELS["tce_png_deflate_u8"](BLOCK)
+    assert hazard.union(*rd).tolist() == BLOCK_READS and hazard.union(*wr).tolist() == BLOCK_WRITES
+
+
+class _StandIn:
+    """Stands where the CDLL stands under a dry hazard._LibProxy: every entry answers with its own name."""
+
+    def __getattr__(self, name):
+        return lambda *a: name
+
+
+def test_recording_proxy_records_the_launching_entry_and_passes_the_queries_through(built_lib):
+    from tce_rvos_amd import hazard
+    rec = hazard.Recorder()
+    proxy = hazard._LibProxy(_StandIn(), rec, dry=True)
+    assert proxy.tce_png_deflate_u8(*BLOCK) == 0
+    assert [x.name for x in rec.launches] == list(LAUNCHING)
+    assert rec.launches[0].reads.tolist() == BLOCK_READS and rec.launches[0].writes.tolist() == BLOCK_WRITES
+    for q in QUERIES:  # passed through, not recorded
+        assert getattr(proxy, q)(5, 7, 2) == q
+    assert len(rec.launches) == 1
 
 
 # ----------------------------------------------------------------------------------------------------------------- the queries

@@ -1,11 +1,9 @@
 """CPU: the PNG stage's dynamic encoding without a GPU -- the restatement of the stream (tests/_png_dyn.py) against zlib, Pillow and
 the fixed stream's length and bound; the codes it builds (complete, within 15 / 7 bits); inputs that take the hard paths of the
 rule, each asserted to take them and to end in a dynamic block; the sizes at the two shapes of DESIGN.md section 3.16 beside
-Pillow's; the staged table against its header; what the new entry and ops.png_deflate reject before anything is launched."""
-import ctypes
+Pillow's; the entry's signature and its access model on a hand-made block; what the new entry and ops.png_deflate reject before anything is launched."""
 import io
 import os
-import re
 import zlib
 from fractions import Fraction
 
@@ -167,29 +165,38 @@ def test_the_default_strip_height_makes_smaller_files_than_the_fixed_default(H, 
               f"dynamic / Pillow = {a / c:.2f}")
 
 
-# ------------------------------------------------------------------------------------------------------------ the staged table
-def test_the_dynamic_entry_is_declared_bound_exported_and_outside_every_other_table(built_lib):
-    from tce_rvos_amd import _lib, hazard
+# -------------------------------------------------------------------------------------------- the entry and its access model
+# (symbols, binding table, exports, argtypes, models / launch-free names of include/tce_rvos_png.h: tests/test_host_cpu.py)
+def test_the_dynamic_entry_has_the_fixed_entrys_signature_and_png_is_the_last_source(built_lib):
+    from tce_rvos_amd import _lib
     from tce_rvos_amd import build as b
-    header = os.path.join(ROOT, "tce-rvos_amd", "csrc", "tce_rvos_png_dyn.h")
-    assert os.path.realpath(header) == os.path.realpath(_lib.PNG_DYN_HEADER)
-    declared = set(re.findall(r"\b(tce_[a-z0-9_]+)\s*\(", open(header).read()))
-    assert declared == set(_lib.PNG_DYN_SIGNATURES) == {ENTRY}, declared
-    l, bound = ctypes.CDLL(built_lib), _lib.lib()
-    res, args = _lib.PNG_DYN_SIGNATURES[ENTRY]
-    fn = getattr(bound, ENTRY)
-    assert hasattr(l, ENTRY) and fn.restype is res and list(fn.argtypes) == args
-    assert (res, args) == _lib.PNG_SIGNATURES["tce_png_deflate_u8"]                 # the same arguments as the fixed entry
-    others = list(_lib.HEADERS.values()) + [_lib.STAGED_SIGNATURES, _lib.PNG_SIGNATURES]
-    assert all(ENTRY not in table for table in others) and _lib.PNG_DYN_SIGNATURES not in list(_lib.HEADERS.values())
-    assert ENTRY not in hazard.MODELS and ENTRY not in hazard.NOT_LAUNCHES
-    assert "tce_rvos_png_dyn.h" not in os.listdir(os.path.join(ROOT, "include"))
-    assert bound.tce_abi_version() == 5 and b.SOURCES[-1] == "png.hip"
-    assert os.path.realpath(header) in {os.path.realpath(d) for d in b.dependencies()}
-    proxy = hazard._LibProxy(_lib.lib(), hazard.Recorder())
-    with pytest.raises(RuntimeError, match=f"no access model for {ENTRY}"):
-        getattr(proxy, ENTRY)
-    assert callable(getattr(_lib.lib_raw(), ENTRY))
+    assert _lib.PNG_SIGNATURES[ENTRY] == _lib.PNG_SIGNATURES["tce_png_deflate_u8"]
+    fn, fixed = getattr(_lib.lib(), ENTRY), _lib.lib().tce_png_deflate_u8
+    assert fn.restype is fixed.restype and list(fn.argtypes) == list(fixed.argtypes)
+    assert b.SOURCES[-1] == "png.hip"
+
+
+def test_access_model_on_a_hand_made_block_and_under_the_recording_proxy(built_lib):
+    """P = 1, H = 3, W = 1500, S = 2: strips of 3002 and 1501 filtered bytes (at most 3383 and 1695 stream bytes), the plane and the
+    stream row on odd addresses; the row is named in full, as for the fixed entry."""
+    from tce_rvos_amd import _lib, hazard
+    l = _lib.lib()
+    assert l.tce_png_stream_bound(3, 1500, 2) == 5086 and l.tce_png_ws_bytes(1, 3, 1500, 2) == 6792
+    block = (0x100003, 0x200001, 0x300000, 0x400000, 1, 3, 1500, 2, 0, 0)
+    reads = [[0x100003, 0x100003 + 4500], [0x400000, 0x400000 + 6792]]
+    writes = [[0x200001, 0x200001 + 5086], [0x300000, 0x300004], [0x400000, 0x400000 + 6792]]
+    rd, wr = hazard.MODELS[ENTRY](block)
+    assert hazard.union(*rd).tolist() == reads and hazard.union(*wr).tolist() == writes
+
+    class StandIn:
+        def __getattr__(self, name):
+            return lambda *a: name
+    rec = hazard.Recorder()
+    proxy = hazard._LibProxy(StandIn(), rec, dry=True)
+    assert getattr(proxy, ENTRY)(*block) == 0
+    assert [x.name for x in rec.launches] == [ENTRY]
+    assert rec.launches[0].reads.tolist() == reads and rec.launches[0].writes.tolist() == writes
+    assert proxy.tce_png_ws_bytes(1, 3, 1500, 2) == "tce_png_ws_bytes" and len(rec.launches) == 1  # a query: passed through
 
 
 def test_bad_calls_are_rejected_before_anything_is_launched(built_lib):

@@ -1,8 +1,9 @@
-"""PNG stage with codes="dynamic" on the GPU: tce_png_deflate_dyn_u8 (csrc/tce_rvos_png_dyn.h) byte for byte against the
+"""PNG stage with codes="dynamic" on the GPU: tce_png_deflate_dyn_u8 (include/tce_rvos_png.h) byte for byte against the
 restatement of the stream (tests/_png_dyn.py), every stream through zlib, never longer than the fixed stream; the hard paths of the
 code build (both depth limits, every length symbol, HLIT at its maximum, the three run-length symbols of the header, strips longer
 than a pass and than a sub-pass of matches, planes whose strips choose differently), each with the block kind the restatement
-reports asserted; planes and streams off every alignment; png.mask_pngs / png.label_pngs against their codes="fixed" files."""
+reports asserted; planes and streams off every alignment; png.mask_pngs / png.label_pngs against their codes="fixed" files; the access
+model against the bytes the launches touch (the cases of test_png_gpu.py through this entry)."""
 import io
 import zlib
 
@@ -13,6 +14,7 @@ from PIL import Image
 
 import _png as R
 import _png_dyn as D
+from test_png_gpu import FOOTPRINT_CASES, check_footprint, recorded_equals_unrecorded, slab  # noqa: F401  (slab: the fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -192,3 +194,13 @@ def test_the_fixed_encoding_is_what_it_was():
         assert explicit[p] == want and streams[p, :int(nbytes[p])].cpu().numpy().tobytes() == want, p
     with pytest.raises(ValueError):
         ops.png_deflate(t, codes="huffman")
+
+
+# --------------------------------------------------------------------------------------------- the recorder and the footprint
+def test_hazard_recording_lists_the_one_entry():
+    recorded_equals_unrecorded("dynamic")
+
+
+@pytest.mark.parametrize("tag,kw", FOOTPRINT_CASES, ids=[c[0] for c in FOOTPRINT_CASES])
+def test_png_deflate_dyn_footprint(slab, tag, kw):
+    check_footprint(slab, "tce_png_deflate_dyn_u8", tag, kw, lambda plane, S, v: D.stream(plane, S, v)[0])

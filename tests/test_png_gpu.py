@@ -1,6 +1,6 @@
-"""PNG stage on the GPU: tce_png_deflate_u8 (csrc/tce_rvos_png.h) byte for byte against the restatement of the stream
+"""PNG stage on the GPU: tce_png_deflate_u8 (include/tce_rvos_png.h) byte for byte against the restatement of the stream
 (tests/_png.py), every stream through zlib and every framed file through Pillow back to the value-mapped input; png.mask_pngs and
-png.label_pngs on synthetic device tensors.  Small shapes: each puts the kernel on another path (the branches of the run rule
+png.label_pngs on synthetic device tensors; the access model against the bytes the launches touch (tests/_footprint.py).  Small shapes: each puts the kernel on another path (the branches of the run rule
 through all-zero strips of S * (W + 1) bytes, runs across passes of 2048 bytes, more boundaries than threads, a shorter last
 strip, planes and streams off every alignment)."""
 import io
@@ -11,7 +11,9 @@ import pytest
 import torch
 from PIL import Image
 
+import _footprint as fp
 import _png as R
+from tce_rvos_amd import _lib, hazard
 
 pytestmark = pytest.mark.gpu
 
@@ -149,6 +151,106 @@ def test_workspace_content_is_irrelevant_and_calls_repeat():
     again, _, _ = _deflate(t, S, 255, ws=ws)
     third, _, _ = _deflate(t, S, 255, ws=ws)                                         # the workspace as the call before left it
     assert first == again == third
+
+
+# --------------------------------------------------------------------------------------------- the recorder and the footprint
+def recorded_equals_unrecorded(codes):
+    """ops.png_deflate under hazard.recording(): its one entry, no conflict, the bytes of the unrecorded call"""
+    from tce_rvos_amd import ops
+    t = torch.from_numpy(_planes(9, 260, 5)).cuda()
+    want_s, want_n = ops.png_deflate(t, rows_per_strip=4, nonzero_value=255, codes=codes)
+    with hazard.recording() as rec:
+        got_s, got_n = ops.png_deflate(t, rows_per_strip=4, nonzero_value=255, codes=codes)
+    torch.cuda.synchronize()
+    assert [x.name for x in rec.launches] == ["tce_png_deflate_u8" if codes == "fixed" else "tce_png_deflate_dyn_u8"]
+    assert rec.analyse().clean and torch.equal(got_n, want_n)
+    for p, n in enumerate(want_n.tolist()):
+        assert n > 0 and torch.equal(got_s[p, :n], want_s[p, :n]), p
+
+
+def test_hazard_recording_lists_the_one_entry():
+    recorded_equals_unrecorded("fixed")
+
+
+@pytest.fixture(scope="module")
+def slab():
+    s = fp.Slab(64 << 20, device="cuda")
+    yield s
+    del s
+    torch.cuda.empty_cache()
+
+
+TAIL = 0xEE  # what the cases write behind nbytes[p]
+
+
+def footprint_planes(tag):
+    if tag.startswith("masks"):
+        return (np.random.default_rng(61).random((2, 5, 7)) < 0.5).astype(np.uint8)
+    return ((np.arange(1500)[None] // 37 + np.arange(3)[:, None]) % 4).astype(np.uint8)[None]  # labels 0 .. 3 in runs of 37
+
+
+# both entries take these (test_png_dyn_gpu.py runs them through the dynamic one)
+FOOTPRINT_CASES = [
+    # three strips a plane, the last one of a single row; 0/1 masks written as 0/255
+    ("masks_2x5x7_strips_of_2_rows_value_255_addresses_1_and_3", dict(S=2, v=255, shift_p=1, shift_s=3)),
+    # a strip of 3002 filtered bytes: more than one pass of 2048
+    ("labels_1x3x1500_strips_of_2_rows_value_0_addresses_3_and_1", dict(S=2, v=0, shift_p=3, shift_s=1)),
+]
+
+
+def footprint_case(slab_, entry, planes, S, v, shift_p, shift_s):
+    """Every buffer of the call in the slab, planes and streams `shift` bytes into their buffers.  By contract the bytes of a row of
+    streams behind nbytes[p] are not written, while the model names whole rows (how much is written is device data): the case
+    follows the launch with a fill of each row's tail, made on the device from nbytes on the same stream, so bytes [0, nbytes[p])
+    are held to the canary and compared under R as they are, and no row needs an exemption."""
+    P, H, W = planes.shape
+    total, bound = P * H * W, R.stream_bound(H, W, S)
+    host = np.zeros(shift_p + total + 3, np.uint8)
+    host[shift_p:shift_p + total] = planes.reshape(-1)
+    raw_p = slab_.put("planes", host)
+    raw_s = slab_.alloc("streams", (shift_s + P * bound + 3,), dtype=torch.uint8)
+    nbytes = slab_.alloc("nbytes", (P,), dtype=torch.int32)
+    ws = slab_.alloc("ws", (_lib.lib_raw().tce_png_ws_bytes(P, H, W, S) // 8,), dtype=torch.int64)
+    rows = raw_s[shift_s:shift_s + P * bound].view(P, bound)
+    col = torch.arange(bound, dtype=torch.int32, device=slab_.device)[None]
+    src, dst = raw_p.data_ptr() + shift_p, raw_s.data_ptr() + shift_s
+
+    def fn():
+        _lib.check(getattr(_lib.lib(), entry)(src, dst, nbytes.data_ptr(), ws.data_ptr(), P, H, W, S, v,
+                                              torch.cuda.current_stream().cuda_stream), entry)
+        rows.masked_fill_(col >= nbytes[:, None], TAIL)
+    fn.check = lambda: (rows, nbytes)
+    return fn
+
+
+def check_footprint(slab_, entry, tag, kw, restatement):
+    """W, O and R of tests/_footprint.py: nothing outside streams, nbytes and ws is written, every byte of a stream and every word
+    of nbytes is written, and the result depends on no byte outside the planes -- the bytes around them included -- nor on what ws
+    held (scratch: R fills it before the run).  ws is exempt from O: a strip's slot is written as far as its bits go."""
+    planes = footprint_planes(tag)
+    P, H, W = planes.shape
+    build = lambda s: footprint_case(s, entry, planes, **kw)  # noqa: E731
+    info = fp.check_case(slab_, build, fp.recorder(entry), exempt=("ws",), scratch=("ws",), props="WOR", sync=torch.cuda.synchronize,
+                         label=f"{entry} {tag}")
+    print(f"{entry} {tag}: read {info['read_bytes']} written {info['written_bytes']} guard {info['guard_bytes']} "
+          f"untouched-in-buffers {info['pad_bytes']}")
+    assert (info["W"], info["O"], info["R"]) == (2, 2, 3) and info["exempt"] == ["ws"]
+    wsb = _lib.lib_raw().tce_png_ws_bytes(P, H, W, kw["S"])
+    assert info["read_bytes"] == P * H * W + wsb and info["written_bytes"] == P * R.stream_bound(H, W, kw["S"]) + 4 * P + wsb
+    slab_.begin(0)
+    fn = build(slab_)
+    fn()
+    torch.cuda.synchronize()
+    rows, nbytes = fn.check()
+    rows, n = rows.cpu().numpy(), nbytes.cpu().tolist()
+    for p in range(P):
+        want = restatement(planes[p], kw["S"], kw["v"])
+        assert rows[p, :n[p]].tobytes() == want and (rows[p, n[p]:] == TAIL).all(), p
+
+
+@pytest.mark.parametrize("tag,kw", FOOTPRINT_CASES, ids=[c[0] for c in FOOTPRINT_CASES])
+def test_png_deflate_footprint(slab, tag, kw):
+    check_footprint(slab, "tce_png_deflate_u8", tag, kw, R.stream)
 
 
 def test_mask_pngs_and_label_pngs_on_device_tensors(tmp_path):

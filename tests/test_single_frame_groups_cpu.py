@@ -1,5 +1,6 @@
 """CPU: the host side of A2D-Sentences / JHMDB-Sentences clip groups -- the planner of video.run_annotated_frames, the copy table of a
-group's single-frame selection (pipeline.pick_segments), and the staged table of the group output stage (csrc/tce_rvos_a2d_group.h)."""
+group's single-frame selection (pipeline.pick_segments), and the group output stage's cap, host structure
+and access model (include/tce_rvos_eval.h)."""
 import ctypes
 import os
 import re
@@ -114,33 +115,43 @@ def test_pick_segments_rejects_bad_indices():
         pick_segments(2, 3, (0,), sizes, chs)
 
 
-# --------------------------------------------------------------------------------------------------------- the staged table
-def test_the_group_entry_is_declared_bound_exported_and_outside_every_other_table(built_lib):
-    from tce_rvos_amd import _lib, hazard, ops
-    from tce_rvos_amd import build as b
-    header = os.path.join(ROOT, "tce-rvos_amd", "csrc", "tce_rvos_a2d_group.h")
-    assert os.path.realpath(header) == os.path.realpath(_lib.A2D_GROUP_HEADER)
-    text = open(header).read()
-    declared = set(re.findall(r"\b(tce_[a-z0-9_]+)\s*\(", text))
-    assert declared == set(_lib.A2D_GROUP_SIGNATURES) == {ENTRY}, declared
-    l, bound = ctypes.CDLL(built_lib), _lib.lib()
-    res, args = _lib.A2D_GROUP_SIGNATURES[ENTRY]
-    fn = getattr(bound, ENTRY)
-    assert hasattr(l, ENTRY) and fn.restype is res and list(fn.argtypes) == args
-    others = list(_lib.HEADERS.values()) + [_lib.STAGED_SIGNATURES, _lib.PNG_SIGNATURES, _lib.PNG_DYN_SIGNATURES]
-    assert all(ENTRY not in table for table in others) and _lib.A2D_GROUP_SIGNATURES not in list(_lib.HEADERS.values())
-    assert ENTRY not in hazard.MODELS and ENTRY not in hazard.NOT_LAUNCHES
-    assert "tce_rvos_a2d_group.h" not in os.listdir(os.path.join(ROOT, "include"))
-    assert bound.tce_abi_version() == 5 and "a2d_group.hip" in b.SOURCES
-    assert os.path.realpath(header) in {os.path.realpath(d) for d in b.dependencies()}
-    proxy = hazard._LibProxy(_lib.lib(), hazard.Recorder())
-    with pytest.raises(RuntimeError, match=f"no access model for {ENTRY}"):
-        getattr(proxy, ENTRY)
-    assert callable(getattr(_lib.lib_raw(), ENTRY))
-    # the table's cap and the host structure are the header's
+# ---------------------------------------------------------------------------------------------- the group entry and its model
+# (symbols, binding table, exports, argtypes, models / launch-free names of include/tce_rvos_eval.h: tests/test_host_cpu.py)
+def test_the_group_cap_and_the_host_structure_are_the_headers():
+    from tce_rvos_amd import _lib, ops
+    text = open(os.path.join(ROOT, "include", "tce_rvos_eval.h")).read()
     cap = int(re.search(r"#define\s+TCE_A2D_GROUP_MAX\s+(\d+)", text).group(1))
     assert cap == _lib.A2D_GROUP_MAX == ops.A2D_GROUP_MAX
     assert ctypes.sizeof(_lib.A2dGroupSample) == 56 and cap * 56 == 896
+
+
+def test_access_model_on_a_hand_made_table_and_under_the_recording_proxy():
+    """Two samples of N = 3 queries and 4 x 6 mask planes with different frame sizes; the second's logits are 2 floats apart, so
+    they show up as three separate 4-byte intervals; the outputs start on odd and on even-but-unaligned addresses."""
+    from tce_rvos_amd import _lib, hazard
+    table = (_lib.A2dGroupSample * 2)()
+    a, b = table
+    a.masks, a.logits, a.out, a.scores = 0x100000, 0x200000, 0x300001, 0x400000
+    a.fh, a.fw, a.H0, a.W0, a.logit_stride = 13, 20, 9, 11, 1
+    b.masks, b.logits, b.out, b.scores = 0x110000, 0x210004, 0x310002, 0x410000
+    b.fh, b.fw, b.H0, b.W0, b.logit_stride = 16, 24, 20, 30, 2
+    reads = [[0x100000, 0x100120], [0x110000, 0x110120], [0x200000, 0x20000C],
+             [0x210004, 0x210008], [0x21000C, 0x210010], [0x210014, 0x210018]]
+    writes = [[0x300001, 0x30012A], [0x310002, 0x31070A], [0x400000, 0x40000C], [0x410000, 0x41000C]]
+    rd, wr = hazard.MODELS[ENTRY]((table, 2, 3, 4, 6, 0.5, 0))
+    assert hazard.union(*rd).tolist() == reads and hazard.union(*wr).tolist() == writes
+    rd, wr = hazard.MODELS[ENTRY]((table, 1, 3, 4, 6, 0.5, 0))  # B decides how much of the table counts
+    assert hazard.union(*rd).tolist() == [reads[0], reads[2]] and hazard.union(*wr).tolist() == [writes[0], writes[2]]
+
+    class StandIn:
+        def __getattr__(self, name):
+            return lambda *a: name
+    rec = hazard.Recorder()
+    proxy = hazard._LibProxy(StandIn(), rec, dry=True)
+    assert getattr(proxy, ENTRY)(table, 2, 3, 4, 6, 0.5, 0) == 0
+    assert [x.name for x in rec.launches] == [ENTRY]
+    assert rec.launches[0].reads.tolist() == reads and rec.launches[0].writes.tolist() == writes
+    assert proxy.tce_rle_ws_bytes(3, 9, 11) == "tce_rle_ws_bytes" and len(rec.launches) == 1  # a query: passed through
 
 
 def test_bad_calls_are_rejected_before_anything_is_launched(built_lib):
