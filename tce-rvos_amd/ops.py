@@ -968,19 +968,52 @@ def splitk_reduce(ws, splits, M, N, out, bias=None, act=ACT_NONE, res=None, ldre
     return out
 
 
-def select_masks(pred_logits, pred_masks, out_hw, threshold=0.5):
+def select_masks(pred_logits, pred_masks, out_hw, threshold=0.5, out=None, best_out=None):
     """Caller harness H (inference_ytvos.py:238-250) on the GPU: pred_logits [T,Q,K], pred_masks [T,Q,h,w]
-    -> (uint8 masks [T,H0,W0], best-query index tensor [1] int32)."""
+    -> (uint8 masks [T,H0,W0], best-query index tensor [1] int32).
+    out / best_out: write into these (e.g. a chunk's slice of a video's masks, at any address) instead of new tensors."""
     _chk(pred_logits, "pred_logits")
     _chk(pred_masks, "pred_masks")
     T, Q, K = pred_logits.shape
     _, _, h, w = pred_masks.shape
     H0, W0 = int(out_hw[0]), int(out_hw[1])
-    out = torch.empty(T, H0, W0, dtype=torch.uint8, device=pred_masks.device)
-    best = torch.empty(1, dtype=torch.int32, device=pred_masks.device)
+    out = _out_tensor(out, "select_masks: out [T,H0,W0]", torch.uint8, (T, H0, W0), pred_masks.device)
+    best = _out_tensor(best_out, "select_masks: best_out [1]", torch.int32, (1,), pred_masks.device)
     check(lib().tce_select_masks_u8(pred_logits.contiguous().data_ptr(), pred_masks.contiguous().data_ptr(),
                                     out.data_ptr(), best.data_ptr(), T, Q, K, h, w, H0, W0, float(threshold), _stream()),
           "tce_select_masks_u8")
+    return out, best
+
+
+def select_window_masks(pred_logits, pred_masks, out_hw, first, count, threshold=0.5, out=None, best_out=None):
+    """The harness H of one context-frame window (inference_ytvos.py:238-264 under keep_fps): pred_logits [T,Q,K] and pred_masks
+    [T,Q,h,w] of the WIDENED clip -> (uint8 masks [count,H0,W0] of clip positions first .. first+count-1, best-query index [1] int32).
+    The best query is chosen over all T frames; only the kept positions are resampled, so a context frame costs no output plane.
+    Three launches that exist, no read-back in between: tce_select_masks_u8 at a 1x1 output writes the index (and T scratch
+    bytes); index_select gathers the kept planes of that query on the device; tce_select_masks_u8 on those [count,1,h,w] planes
+    (Q = K = 1: its own index is 0, not stored) renders them -- the operations of the whole-window launch on the same planes,
+    hence its bits (tests/test_output_stage_gpu.py holds the Q = 1 form to that).  out / best_out as in select_masks."""
+    _chk(pred_logits, "pred_logits")
+    _chk(pred_masks, "pred_masks")
+    if pred_logits.dim() != 3 or pred_masks.dim() != 4 or pred_masks.shape[:2] != pred_logits.shape[:2]:
+        raise ValueError("select_window_masks: pred_logits must be [T,Q,K] and pred_masks [T,Q,h,w]")
+    T, Q, K = (int(v) for v in pred_logits.shape)
+    h, w = int(pred_masks.shape[2]), int(pred_masks.shape[3])
+    H0, W0 = int(out_hw[0]), int(out_hw[1])
+    first, count = int(first), int(count)
+    if first < 0 or count < 1 or first + count > T:
+        raise ValueError(f"select_window_masks: positions {first} .. {first + count - 1} are not inside a window of {T} frames")
+    dev = pred_masks.device
+    out = _out_tensor(out, "select_window_masks: out [count,H0,W0]", torch.uint8, (count, H0, W0), dev)
+    best = _out_tensor(best_out, "select_window_masks: best_out [1]", torch.int32, (1,), dev)
+    lg, pm = pred_logits.contiguous(), pred_masks.contiguous()
+    scratch = torch.empty(T, dtype=torch.uint8, device=dev)  # the 1x1 "masks" of the index launch: written, never read
+    check(lib().tce_select_masks_u8(lg.data_ptr(), pm.data_ptr(), scratch.data_ptr(), best.data_ptr(), T, Q, K, h, w, 1, 1,
+                                    float(threshold), _stream()), "tce_select_masks_u8")
+    planes = pm[first:first + count].index_select(1, best.long())  # [count,1,h,w], the index stays on the device
+    # the render launch scores its one query from `count` floats of lg (T*Q*K >= count of them) and stores no index
+    check(lib().tce_select_masks_u8(lg.data_ptr(), planes.data_ptr(), out.data_ptr(), None, count, 1, 1, h, w, H0, W0,
+                                    float(threshold), _stream()), "tce_select_masks_u8")
     return out, best
 
 

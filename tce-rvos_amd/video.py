@@ -6,7 +6,7 @@ Two loops of the reference's callers, with the model call and the caller harness
   frames (the last one shorter), each chunk is one B=1 forward, the best query is chosen PER CHUNK from that chunk's
   mean class score, its masks are resized to the original size, and the per-chunk results are concatenated.
 * `run_video(..., clip_size=None)` -- inference_ytvos.py:278-321 (the non-`keep_fps` branch): the whole video is one
-  clip, whatever its length.
+  clip, whatever its length.  (The `keep_fps` branch is run_video_windows, below.)
 
 * `run_video_expressions(...)` -- the loop AROUND those two in the reference's drivers (inference_ytvos.py:96-113,
   inference_davis.py:150-208: every expression of a video is run over the same frames): expressions whose captions tokenise to
@@ -20,6 +20,13 @@ Two loops of the reference's callers, with the model call and the caller harness
 * `run_annotated_frames(...)` -- the A2D-Sentences / JHMDB-Sentences evaluation loop (engine.py:301-319 without the data loader): one
   annotated frame per clip (`valid_indices`); samples of one clip shape and index go through `model.forward_group` together and
   through the post-processor's group launch.
+
+* `run_video_windows(...)` -- the `keep_fps` branch of the Ref-YouTube-VOS driver (inference_ytvos.py:194-277; forced on when
+  `args.f_extra != 0`, :136-137) and the live part of the MeViS driver (inference_mevis.py:196-214, `last="shifted"`): the video is
+  cut into windows of `num_frames` frames, each widened by `f_extra` context frames on both sides (clamped at the video's ends), the
+  best query is chosen over the WIDENED window and only the window's own frames get a mask (ops.select_window_masks: a context
+  frame costs no output plane).  `plan_windows` is the rule, `plan_window_forwards` the forwards: the expressions of a video share
+  the backbone per window, a lone expression runs several windows per forward.
 
 A video's chunks share the caption, so with `model.text_cache_size > 0` RoBERTa runs once per expression instead of
 once per chunk (the reference recomputes it inside every forward).  Chunks of one length share a captured hipGraph
@@ -252,3 +259,144 @@ def run_annotated_frames(model, samples, postprocessor=None, max_group: int = 8,
             res[i] = o
     ops.check_range(dev)
     return res
+
+
+def window_args(args):
+    """dict(num_frames, f_extra) of the reference's argparse namespace, for plan_windows / run_video_windows.  The reference's
+    drivers take the window loop when `args.keep_fps` is set and force it on when `args.f_extra != 0` (inference_ytvos.py:136-137):
+    a caller that follows them runs run_video_windows in exactly those cases and run_video(clip_size=None) otherwise.  `f_extra` is
+    an attribute some of the reference's own entry points forget to define: missing means 0.  num_frames defaults to 5 (opts.py)."""
+    return {"num_frames": int(getattr(args, "num_frames", 5)), "f_extra": int(getattr(args, "f_extra", 0) or 0)}
+
+
+def plan_windows(n_frames: int, num_frames: int, f_extra: int = 0, last: str = "short", take: str = "leading"):
+    """The windows of run_video_windows, in order: a list of (ids, first, count, lo).  ids: the clip's frame indices (a tuple);
+    the masks of clip positions first .. first+count-1 are written to video frames lo .. lo+count-1.  Every video frame is written
+    exactly once, in increasing order.  Pure host arithmetic.
+
+    Window w has the core frames [s, min(s + num_frames, N)), s = w * num_frames; its clip is the core with f_extra frames put in
+    front (each max(0, first - 1)) and f_extra appended (each min(N - 1, last + 1)): frames repeat at the video's ends
+    (inference_ytvos.py:198-212).  last="shifted" (inference_mevis.py:206-207): a window with s + num_frames > N starts at
+    N - num_frames instead; the frames it shares with the window before keep their FIRST entry, so it writes only the frames from
+    `covered` on (N < num_frames has negative indices in the reference: ValueError here).
+    take="leading" is what the reference stores: core frame s + j gets the mask of clip position j (:243, range(m) of the
+    widened clip), which with f_extra > 0 is frame clamp(s - f_extra + j).  take="centre" is the aligned variant: position
+    f_extra + j, the frame itself."""
+    N, n, e = int(n_frames), int(num_frames), int(f_extra)
+    if N < 1:
+        raise ValueError("plan_windows: empty video")
+    if n < 1:
+        raise ValueError(f"plan_windows: num_frames must be >= 1, got {n}")
+    if e < 0:
+        raise ValueError(f"plan_windows: f_extra must be >= 0, got {e}")
+    if last not in ("short", "shifted"):
+        raise ValueError(f"plan_windows: last must be 'short' or 'shifted', got {last!r}")
+    if take not in ("leading", "centre"):
+        raise ValueError(f"plan_windows: take must be 'leading' or 'centre', got {take!r}")
+    if last == "shifted" and N < n:
+        raise ValueError(f"plan_windows: last='shifted' needs a video of at least num_frames = {n} frames, got {N}")
+    plan, covered = [], 0
+    for s in range(0, N, n):
+        if last == "shifted" and s + n > N:
+            s = N - n
+        hi = min(s + n, N)
+        ids = [max(0, s - k) for k in range(e, 0, -1)] + list(range(s, hi)) + [min(N - 1, hi - 1 + k) for k in range(1, e + 1)]
+        first = covered - s + (e if take == "centre" else 0)
+        plan.append((tuple(ids), first, hi - covered, covered))
+        covered = hi
+    return plan
+
+
+def plan_window_forwards(lengths, windows, max_group: int = 4, windows_per_forward: int = 4, mixed_lengths: bool = False):
+    """The forwards of run_video_windows, in order: a list of (captions, windows), both lists of indices; every (caption, window)
+    pair appears exactly once.  model.forward_group shares the backbone only when ALL clips of a group are one tensor, so there are
+    two kinds of forward: an expression bucket (plan_expression_groups) of two or more captions runs one SHARED group per window
+    ([i, j, ...], [w]); a bucket of one caption runs its windows `windows_per_forward` at a time as distinct clips ([i], [w, ...]).
+    Only consecutive windows of one clip length go together, so a short last window goes alone.  `windows`: plan_windows' list."""
+    wpf = max(1, int(windows_per_forward))
+    runs = []  # consecutive windows of one clip length, at most wpf of them
+    for w, win in enumerate(windows):
+        if runs and len(runs[-1]) < wpf and len(windows[runs[-1][0]][0]) == len(win[0]):
+            runs[-1].append(w)
+        else:
+            runs.append([w])
+    out = []
+    for grp in plan_expression_groups(lengths, max_group, mixed_lengths):
+        if len(grp) >= 2:
+            out += [(list(grp), [w]) for w in range(len(windows))]
+        else:
+            out += [(list(grp), list(r)) for r in runs]
+    return out
+
+
+@torch.no_grad()
+def run_video_windows(model, frames: torch.Tensor, captions, origin_hw, num_frames: int = 5, f_extra: int = 0, last: str = "short",
+                      take: str = "leading", threshold: float = 0.5, max_group: int = 4, windows_per_forward: int = 4,
+                      mixed_lengths: bool = False):
+    """The context-frame window loop over ONE video (see plan_windows for the rule and the module docstring for the citations).
+    frames and origin_hw as in run_video; captions: a str, a LongTensor [1,L], or a list of either (a list returns a list).
+    Returns per caption dict(masks uint8 [N,H0,W0], best_query int32 [n_windows], pred_logits [N,K], pred_boxes [N,4],
+    reference_points [N,2] -- the best query's rows at the KEPT clip positions, as the reference indexes them --, windows: the plan).
+
+    Each window's clip is frames.index_select(0, ids) on the device (the indices of all windows go up in one copy before the loop);
+    `masks` is allocated once and every window's output stage writes its own slice of it.  Nothing inside the loop waits for the GPU.
+    With take="leading" (the default: what the reference's published numbers were made with) and f_extra > 0 a frame's mask comes
+    from a frame up to f_extra earlier; take="centre" aligns them."""
+    if frames.dim() != 4 or frames.shape[1] != 3 or frames.shape[0] == 0:
+        raise ValueError("run_video_windows: frames must be a non-empty [N,3,H,W]")
+    single = isinstance(captions, str) or torch.is_tensor(captions)
+    caps = [captions] if single else list(captions)
+    if not caps:
+        return []
+    n = int(frames.shape[0])
+    H, W = int(frames.shape[-2]), int(frames.shape[-1])
+    H0, W0 = int(origin_hw[0]), int(origin_hw[1])
+    dev = frames.device
+    target = [{"size": torch.tensor([H, W])}]
+    plan = plan_windows(n, num_frames, f_extra, last, take)
+    ids = [c if torch.is_tensor(c) else model._tokenise([c], dev)[0] for c in caps]
+    forwards = plan_window_forwards([int(t.shape[1]) for t in ids], plan, max_group, windows_per_forward, mixed_lengths)
+    flat = torch.tensor([i for win in plan for i in win[0]], dtype=torch.int64).to(dev)  # every window's indices: one copy
+    offs = [0]
+    for win in plan:
+        offs.append(offs[-1] + len(win[0]))
+    toks = {}
+    for grp, wins in forwards:
+        key = (tuple(grp), len(wins) if len(grp) == 1 else 1)
+        if key in toks:
+            continue
+        if len(grp) == 1:  # one caption, len(wins) distinct clips (one window: the host ids, as run_video passes them)
+            toks[key] = ids[grp[0]] if len(wins) == 1 else ids[grp[0]].to(dev).expand(len(wins), -1).contiguous()
+        elif mixed_lengths:  # right-padded on the host (validated there), lengths derived again on the device
+            from .model import pad_captions
+            toks[key] = pad_captions([ids[i] for i in grp], model._pad_id())[0].to(dev)
+        else:
+            toks[key] = torch.cat([ids[i].to(dev) for i in grp], 0)
+    res = [{"masks": torch.empty(n, H0, W0, dtype=torch.uint8, device=dev),
+            "best_query": torch.empty(len(plan), dtype=torch.int32, device=dev),
+            "pred_logits": [None] * len(plan), "pred_boxes": [None] * len(plan), "reference_points": [None] * len(plan)} for _ in caps]
+    for grp, wins in forwards:
+        clips = [frames.index_select(0, flat[offs[w]:offs[w + 1]]) for w in wins]
+        if len(grp) == 1:
+            outs = model.forward_group(clips, toks[(tuple(grp), len(wins))], target)
+            pairs = [(grp[0], w) for w in wins]
+        else:  # one tensor, len(grp) captions: shared backbone
+            outs = model.forward_group(clips * len(grp), toks[(tuple(grp), 1)], target, **({"ragged": True} if mixed_lengths else {}))
+            pairs = [(i, wins[0]) for i in grp]
+        for (i, w), out in zip(pairs, outs):
+            _, first, count, lo = plan[w]
+            r = res[i]
+            pl = out["pred_logits"][0]
+            # harness H of a window: the query over the widened clip, the kept planes straight into the video's masks
+            _, b = ops.select_window_masks(pl, out["pred_masks"][0], (H0, W0), first, count, threshold,
+                                           out=r["masks"][lo:lo + count], best_out=r["best_query"][w:w + 1])
+            idx = b.long().expand(count)
+            ar = torch.arange(first, first + count, device=dev)
+            r["pred_logits"][w] = pl[ar, idx]
+            r["pred_boxes"][w] = out["pred_boxes"][0][ar, idx]
+            r["reference_points"][w] = out["reference_points"][0][ar, idx]
+    ops.check_range(dev)
+    ret = [{"masks": r["masks"], "best_query": r["best_query"], "pred_logits": torch.cat(r["pred_logits"], 0),
+            "pred_boxes": torch.cat(r["pred_boxes"], 0), "reference_points": torch.cat(r["reference_points"], 0), "windows": plan}
+           for r in res]
+    return ret[0] if single else ret
