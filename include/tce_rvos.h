@@ -341,7 +341,7 @@ int tce_mha_small64_lens_f32(const float* qkv_planes, int32_t splits, const floa
 int tce_caption_lens_f32(const int64_t* ids, int32_t nseq, int32_t Lmax, int32_t pad_id, int32_t D, int32_t* lens, uint8_t* kmask,
                          float* pos, tceStream stream);
 
-/* Fused FFN / MLP, the hidden tensor kept on chip (csrc/chain.hip):
+/* Fused FFN / MLP, the hidden tensor kept on chip (csrc/ffn.hip):
  *     out[M,C] = LN_out?( x + W2 act( W1 LN_in?(x) + b1 ) + b2 )        act 1 ReLU | 2 GELU(erf)
  * One launch replaces linear1 -> ReLU -> linear2 -> +residual -> LayerNorm of the transformer / VisionLanguageBlock
  * FFNs (tce_deformable_transformer.py:489-491,548-552; segmentation.py:374-376) and norm2 -> fc1 -> GELU -> fc2 ->
@@ -362,7 +362,7 @@ int tce_ffn_fused_f32(const float* x, int64_t ldx, const void* packed, const flo
 /* The same launch with the hidden extent of a row block cut once and the two pieces on different workgroups (round 5): a workgroup
  * owns 128 rows and a launch of 24100 rows is 189 of them -- 0.74 rounds of 256 CUs that cost a full one.  With p blocks handed to
  * p + 1 workgroups a round is ~p/(p+1) as long.  tce_ffn_split_ws_floats > 0 says that a split is planned for the shape (C = 256,
- * ReLU, where the launcher's model says it pays -- csrc/chain.hip ffn_split_plan, calibrated on measurements) and how many floats of workspace it needs; tce_ffn_split_counters how many int32
+ * ReLU, where the launcher's model says it pays -- csrc/ffn.hip ffn_split_plan, calibrated on measurements) and how many floats of workspace it needs; tce_ffn_split_counters how many int32
  * counters.  The counters must be ZERO at the launch and are zero again when it ends (a block's second arriver adds the two partial
  * sums -- the same bits whichever piece arrives last -- runs the epilogue and resets the counter): give each call site that can run
  * concurrently with another its own.  Results differ from tce_ffn_fused_f32's by fp32 round-off (one more addition per element). */
@@ -382,7 +382,7 @@ int tce_ffn_fused_split_f32(const float* x, int64_t ldx, const void* packed, con
                             int32_t C, int32_t Hd, int32_t act, float* ws, int64_t ws_floats, int32_t* counters, int32_t n_counters,
                             tceStream stream);
 
-/* Token-stationary linear layer (csrc/chain.hip), for K in {96,128,192,256,384,512} and many rows:
+/* Token-stationary linear layer (csrc/rowlin.hip), for K in {96,128,192,256,384,512} and many rows:
  *     out[M,N] = LN_out?( epi( LN_in?(x + a2) W^T + bias ) )      epi: act 0 none | 1 ReLU | 2 GELU(erf), then
  *                                                                 res_mode 0 none | 1 "+ res" | 2 "* res"
  * x stays in registers for the whole launch (read once, in full 128-byte lines), W is streamed from a packed copy
@@ -413,7 +413,7 @@ int tce_rowlin_f32(const tceRowLinArgs* args, tceStream stream);
 
 /* 3x3 convolution, stride 1, zero padding 1, 256 -> 256 channels on channels-last maps [T*H*W, 256]: the pixel
  * decoder's output convolutions (CrossModalFPNDecoder, segmentation.py:186-204,253-283; nn.Conv2d(256, 256, 3,
- * padding=1)) as a pixel-stationary kernel (csrc/chain.hip) -- each wave owns 32 pixels and all 256 output channels,
+ * padding=1)) as a pixel-stationary kernel (csrc/conv3x3.hip) -- each wave owns 32 pixels and all 256 output channels,
  * the activations go from global memory straight into the MFMA operand registers, only the weights pass through LDS.
  * w [256, 9*256] with k = (ky*3+kx)*256 + c (the layout tce_gemm_f32's implicit-GEMM mode takes); packed streams carry
  * the rounding of the GEMM mode they were packed in (modes 1 and 2; mode 0 has no such kernel: use tce_gemm_f32). */
@@ -432,7 +432,7 @@ int32_t tce_conv3x3_split_kstep(int32_t pieces, int32_t s);
 int tce_conv3x3_split_f32(const float* x, int64_t ldx, const void* packed, const float* bias, float* out, int64_t ldo, int32_t T,
                           int32_t H, int32_t W, int32_t Cin, int32_t N, float* ws, int64_t ws_floats, tceStream stream);
 
-/* Cross-attention of a token tensor against a SHORT key sequence as ONE token-stationary launch (csrc/chain.hip):
+/* Cross-attention of a token tensor against a SHORT key sequence as ONE token-stationary launch (csrc/ffn.hip):
  *     out = LN?( res (+|*) ( MHA(q = x + a2, k, v) W_o^T + b_o ) )          8 heads x 32 channels, `group` key slots
  * group 32: the L <= 32 text keys (VisionLanguageBlock / fusion module); group 8: the f_token = 8 frame tokens of
  * FrameTokenLayer's pixel <- token attention (tce_deformable_transformer.py:480-484), keys / values per frame (batch).

@@ -18,6 +18,10 @@ int* tce_range_flag();
 int tce_gemm_single_pass();
 bool tce_patch_embed_mfma(const float* frames, const float* w, const float* b, const float* gamma, const float* beta,
                           float* out, int H, int W, int C, float eps, long long ntok, int Hp, int Wp, hipStream_t s);
+// Diagnostic stamps, one exported setter and two device copies: ffn_fused_kernel (ffn.hip) and rowlin_kernel (rowlin.hip) each
+// read a `static __device__` pointer of their own translation unit (no relocatable device code, so they cannot share one).
+// tce_debug_ffn_set_stamp_buffer (ffn.hip) sets its unit's copy and calls this, which sets rowlin.hip's; 0 on success.
+int tce_rowlin_set_stamps(long long* dev_buf);
 
 #define TCE_CHECK_ARG(cond, ...)            \
   do {                                      \

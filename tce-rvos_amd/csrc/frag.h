@@ -1,4 +1,4 @@
-// Fragment-level helpers shared by the token-stationary kernels (chain.hip, swinattn.hip): fp16 hi/lo operand splitting,
+// Fragment-level helpers shared by the token-stationary kernels (tiles.h and its users, swinattn.hip): fp16 hi/lo operand splitting,
 // the 1 KiB "piece" = one wave-wide 16-byte-per-lane LDS-DMA / ds_read_b128, and the per-wave LDS staging tile.
 #pragma once
 #include "common.h"
@@ -51,7 +51,7 @@ __device__ __forceinline__ HL split8(const float* v, const int single = 0) {
   return r;
 }
 
-// Per-wave staging tile in LDS: 32 rows x 32 floats, 144-byte pitch (see chain.hip)
+// Per-wave staging tile in LDS: 32 rows x 32 floats, 144-byte pitch (see tiles.h)
 constexpr int WT_PITCH = 36;                 // floats
 constexpr int WT_BYTES = 32 * WT_PITCH * 4;  // 4608 bytes per wave
 

@@ -77,7 +77,7 @@ static __device__ int g_epi_lds = 1;  // tuning aid: 1 = LDS-staged coalesced ep
 // loop is branch-free, so the compiler emits exact counted vmcnt waits): a K step no longer pays a full memory
 // round trip, which is what bounds the small / short-K problems of this path.
 // SINGLE (tce_set_gemm_mode(2): one MFMA per product) is a compile-time parameter: as a run-time flag it put a uniform branch
-// in front of every tile's two lo-term MFMAs and around every hi / lo split (see ffn_fused_kernel in chain.hip).
+// in front of every tile's two lo-term MFMAs and around every hi / lo split (see ffn_fused_kernel in ffn.hip).
 template <int BM, int BN, int WAVES_M, bool CONV, bool HAS_A2, int DEPTH, bool SINGLE>
 __global__ void __launch_bounds__(128 * WAVES_M, WAVES_M == 2 ? 2 : 1)
     gemm_f16x3_kernel(const tceGemmArgs p, const int tiles_m, const int tiles_n, int* const range_flag) {

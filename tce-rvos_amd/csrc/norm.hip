@@ -585,7 +585,7 @@ extern "C" int tce_patch_embed_f32(const float* frames, const float* w, const fl
   TCE_CHECK_ARG(T > 0 && H > 0 && W > 0 && C > 0 && C <= 256, "tce_patch_embed_f32: need 0 < C <= 256 (C=%d)", C);
   const int Hp = (H + 3) / 4, Wp = (W + 3) / 4;
   const long long ntok = (long long)T * Hp * Wp;
-  // split-fp16 / fp16 GEMM modes: the taps go through the matrix cores (csrc/chain.hip); exact-fp32 mode keeps the
+  // split-fp16 / fp16 GEMM modes: the taps go through the matrix cores (csrc/patch_embed.hip); exact-fp32 mode keeps the
   // fp32 vector kernels below
   if (tce_get_gemm_mode() != 0 &&
       tce_patch_embed_mfma(frames, w, b, gamma, beta, out, H, W, C, eps, ntok, Hp, Wp, (hipStream_t)stream)) {

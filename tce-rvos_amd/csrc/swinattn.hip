@@ -30,6 +30,7 @@
 #include "common.h"
 #include "gemm_epilogue.h"
 #include "frag.h"
+#include "tiles.h"
 #include "../../include/tce_rvos.h"
 
 namespace {
@@ -61,15 +62,8 @@ struct SwinArgs {
 
 __device__ __forceinline__ int crow_(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
 
-// compile-time loop: f(integral_constant<int, I>) for I = 0 .. N-1 (a `#pragma unroll` over the head's 24..64 steps is not
-// honoured by the optimiser; every per-step decision below must be a compile-time one: register arrays, ring offsets)
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    static_for<I + 1, N>(f);
-  }
-}
+// The head's steps run under static_for (tiles.h): a `#pragma unroll` over the head's 24..64 steps is not honoured by the
+// optimiser, and every per-step decision below must be a compile-time one: register arrays, ring offsets.
 
 // D += A B in the library's arithmetic: three MFMAs on the hi/lo split (cross terms first), one in single mode
 __device__ __forceinline__ void mma3(f32x16& d, const h16x8 ah, const h16x8 al, const h16x8 bh, const h16x8 bl, const int single) {

@@ -30,7 +30,7 @@ struct ThinArgs {
 
 __device__ __forceinline__ int crow_t(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
 
-template <bool PRO, bool SINGLE>  // SINGLE: the arithmetic mode as a compile-time parameter (see ffn_fused_kernel, chain.hip)
+template <bool PRO, bool SINGLE>  // SINGLE: the arithmetic mode as a compile-time parameter (see ffn_fused_kernel, ffn.hip)
 __global__ void __launch_bounds__(256) thin_partials_kernel(const ThinArgs p) {
   // per wave: one staging tile for W and one for x (32 rows x 32 floats, 144-byte pitch: conflict-free for the row-of-8-lanes
   // writes and the row-per-lane fragment reads alike, see frag.h); the tiles are reused by the wave's two 32-wide K chunks

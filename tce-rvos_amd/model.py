@@ -432,7 +432,7 @@ class ReferFormer(nn.Module):
                         w[pre + "q.wT:x"] = ops.xattn_static(W[:d], B[:d])
                 if v_is_conv(sd[k]) and sd[k].shape[-1] == 3:
                     w[k + ":cl"] = sd[k].detach().permute(0, 2, 3, 1).reshape(sd[k].shape[0], -1).contiguous()
-            # fused FFN / Swin MLP streams (csrc/chain.hip): fp16 hi/lo planes in MFMA-fragment order
+            # fused FFN / Swin MLP streams (csrc/ffn.hip): fp16 hi/lo planes in MFMA-fragment order
             for k in list(sd):
                 for l1, l2, tag in ((".linear1.weight", ".linear2.weight", ".ffn:pk"),
                                     (".mlp.fc1.weight", ".mlp.fc2.weight", ".mlp.ffn:pk")):
@@ -459,14 +459,14 @@ class ReferFormer(nn.Module):
                         pre = k[:-len("attn.qkv.weight")]
                         with ops.arith(mode):
                             w[pre + "attn:pk:" + mode] = ops.swin_attn_pack(sd[k].detach(), sd[pre + "attn.proj.weight"].detach())
-            # token-stationary linear kernel (csrc/chain.hip): packed copies of every eligible weight in THIS model's routes
+            # token-stationary linear kernel (csrc/rowlin.hip): packed copies of every eligible weight in THIS model's routes
             # (keyed by address + arithmetic) so ops.gemm_ex can route the shapes where it wins
             for k in list(w):
                 t = w[k]
                 if torch.is_tensor(t) and t.dtype == torch.float32 and t.dim() == 2 and (k.endswith("weight") or k.endswith(".w")):
                     with self.arith(arith_group_of(k)):
                         ops.rowlin_register(t, routes)
-            # pixel-stationary 3x3 convolution (csrc/chain.hip): the pixel decoder's 256 -> 256 output convolutions
+            # pixel-stationary 3x3 convolution (csrc/conv3x3.hip): the pixel decoder's 256 -> 256 output convolutions
             for k in list(w):
                 if k.startswith("pixel_decoder.") and k.endswith(".weight:cl") and w[k].shape[1] % 9 == 0:
                     with self.arith("pixel.conv"):

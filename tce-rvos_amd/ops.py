@@ -135,7 +135,7 @@ class arith:
 
 class ffn_wg_cap:
     """`with ops.ffn_wg_cap(n):` -- the fused-FFN / folded cross-attention launches inside occupy at most n workgroups (one per CU:
-    the persistent form of csrc/chain.hip, tce_ffn_set_wg_cap); 0 or None = no cap.  Same bits as the uncapped launches.  Like the
+    the persistent form of csrc/ffn.hip, tce_ffn_set_wg_cap); 0 or None = no cap.  Same bits as the uncapped launches.  Like the
     arithmetic mode the cap is per THREAD and read when a launch is issued: a captured graph keeps it per node."""
 
     def __init__(self, n):
@@ -1300,7 +1300,7 @@ def png_deflate(planes, rows_per_strip=8, nonzero_value=0, streams=None, nbytes=
 
 
 def ffn_pack(w1, b1, w2, out=None):
-    """Packs nn.Linear weights W1 [Hd,C], b1 [Hd], W2 [C,Hd] into the fused-FFN stream (csrc/chain.hip): fp16 hi/lo
+    """Packs nn.Linear weights W1 [Hd,C], b1 [Hd], W2 [C,Hd] into the fused-FFN stream (csrc/ffn.hip): fp16 hi/lo
     planes in MFMA-fragment order.  Done once per load_state_dict (static weights) or once per clip into an arena
     buffer `out` (the text cross-attention's folded weights)."""
     _chk(w1, "w1")
@@ -1369,7 +1369,7 @@ def ffn_fused(x, packed, b2, Hd, act, ln_in=None, ln_out=None, eps_in=1e-5, eps_
 
 
 # ---------------------------------------------------------------------------------------------------------------
-# Token-stationary linear layers (csrc/chain.hip: tce_rowlin_f32) and the pixel-stationary 3x3 convolution.  Weights
+# Token-stationary linear layers (csrc/rowlin.hip: tce_rowlin_f32) and the pixel-stationary 3x3 convolution.  Weights
 # are packed once; a MODEL owns the packed copies of its weights in a Routes object (keyed by address + shape + the
 # arithmetic they were packed in) and activates it for the duration of its launch program (`with ops.routes(r):`,
 # pipeline.run_clip); gemm_ex / conv2d_cl route eligible launches through the ACTIVE table only.  Nothing is shared
@@ -1480,7 +1480,7 @@ def rowlin(x, pk, out, M, N, K, ldx, ldo, bias=None, a2=None, lda2=0, a2_rows=0,
 
 
 # ---------------------------------------------------------------------------------------------------------------
-# 3x3 / stride 1 / pad 1 convolution 256 -> 256 as a pixel-stationary launch (csrc/chain.hip: tce_conv3x3_f32)
+# 3x3 / stride 1 / pad 1 convolution 256 -> 256 as a pixel-stationary launch (csrc/conv3x3.hip: tce_conv3x3_f32)
 # ---------------------------------------------------------------------------------------------------------------
 CONV3_MIN_PIXELS = int(os.environ.get("TCE_CONV3_MIN_PIXELS", 12000))
 # A launch that fills less than one round of workgroups is split over the K walk (tce_conv3x3_split_f32) when the call site gives an
@@ -1546,7 +1546,7 @@ def conv3x3(x, pk, T, H, W, Cin, N, bias=None, out=None, alloc=None):
 
 
 # ---------------------------------------------------------------------------------------------------------------
-# Text cross-attention as one token-stationary launch (csrc/chain.hip: tce_xattn_prepare_f32 / tce_xattn_fused_f32):
+# Text cross-attention as one token-stationary launch (csrc/ffn.hip: tce_xattn_prepare_f32 / tce_xattn_fused_f32):
 # with <= 32 keys the per-head scores are linear in the query rows, so q-projection -> attention -> out-projection ->
 # residual -> LayerNorm is the fused FFN kernel with a grouped softmax as its activation.
 # ---------------------------------------------------------------------------------------------------------------

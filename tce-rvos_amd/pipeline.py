@@ -23,7 +23,7 @@ SWIN_FUSED_MIN_TOKENS = int(os.environ.get("TCE_SWIN_FUSED_MIN_TOKENS", 2000))
 
 
 def _proj_res_ln(x, wt, bias, resid, M, norm_w, norm_b):
-    """resid <- LayerNorm(resid + x W^T + bias)  (N = K = 256).  Many rows: one token-stationary launch (csrc/chain.hip, ROW
+    """resid <- LayerNorm(resid + x W^T + bias)  (N = K = 256).  Many rows: one token-stationary launch (csrc/rowlin.hip, ROW
     mode) instead of GEMM + LayerNorm; otherwise the two launches."""
     pk = ops.rowlin_lookup(wt, D, D) if M >= FFN_FUSED_MIN_ROWS else None
     if pk is not None:
@@ -221,7 +221,7 @@ def _run_clip(model, frames, text, img_h, img_w, ar, side_arena=None, side_strea
 
     # ------------------------------------------------------------------ text stage (tce_rvos.py:406-424, FeatureResizer
     # :616-635) and everything that depends on the text alone: the projected keys / values of the five text
-    # cross-attention sites and their folded weight streams (csrc/chain.hip, tce_xattn_fused_f32).  With a side stream it
+    # cross-attention sites and their folded weight streams (csrc/ffn.hip, tce_xattn_fused_f32).  With a side stream it
     # is a parallel graph branch beside the backbone; its buffers live in the side arena until the end of the clip.
     tA = (side_arena if side_arena is not None else ar).alloc
     # The text branch needs nothing the backbone produces.  TCE_TEXT_EARLY_EDGE=1 gives it a graph edge back to the START of
@@ -319,7 +319,7 @@ def _run_clip(model, frames, text, img_h, img_w, ar, side_arena=None, side_strea
 
     def _ffn(x, M, pre, l1, l2, ar, norm):
         """x <- LN_norm?(x + W2 relu(W1 x)) (in place).  Large M: one fused launch, the [M, 2048] hidden stays on chip
-        (csrc/chain.hip); small M (a workgroup walks the whole hidden extent alone): two GEMMs + LayerNorm."""
+        (csrc/ffn.hip); small M (a workgroup walks the whole hidden extent alone): two GEMMs + LayerNorm."""
         pk = w.get(pre + "ffn:pk:" + ops.get_gemm_mode()) if fused_ok else None
         if pk is not None and M >= FFN_FUSED_MIN_ROWS:
             nws, ncnt = ops.ffn_split_need(M, D, ff, ACT_RELU)
@@ -339,7 +339,7 @@ def _run_clip(model, frames, text, img_h, img_w, ar, side_arena=None, side_strea
                 ln=(w[norm + ".weight"], w[norm + ".bias"]) if norm else None)  # the norm rides in the split-K reduction
         ar.release(m1)
 
-    def chain_ffn(pre, group, M, norm, A, sMid):
+    def chained_ffn(pre, group, M, norm, A, sMid):
         """The FFN stage of a cross-attention -> FFN chain launch (ops.xattn_fused(ffn=...)), or None where the two run as two
         launches: the chain needs the chain-ordered W1 stream (model._pack: both site groups in one arithmetic) and the row count
         of the fused FFN route.  `mid` (the attention stage's rows, the FFN's residual) is scratch of the caller's arena."""
@@ -350,7 +350,7 @@ def _run_clip(model, frames, text, img_h, img_w, ar, side_arena=None, side_strea
             return None
         return (pkc, w[pre + "linear2.bias"], ff, (w[norm + ".weight"], w[norm + ".bias"]), A(M, D), sMid)
 
-    ffn.chain = chain_ffn  # travels with `ffn` into the pixel decoder's branches
+    ffn.chain = chained_ffn  # travels with `ffn` into the pixel decoder's branches
 
     # input_proj + early fusion of a level (:258-307) needs that level's backbone map and the text only: with the extra
     # branches of fork3 the two large levels start as soon as their Swin stage is done, beside the later stages (which
@@ -713,7 +713,7 @@ def _run_clip(model, frames, text, img_h, img_w, ar, side_arena=None, side_strea
                     # q-proj -> attention over the frame's 8 tokens -> out-proj -> + src -> norm3 in one token-stationary
                     # launch (the keys / values differ per frame: one folded weight stream per frame)
                     pk = ops.xattn_pack(k, v, w[pre + "q.wT:x"], w[pre + "out_proj.weight"], Fk, A, group=8, batch=T)
-                    chained = chain_ffn(fp, "encoder.ffn", T * S, fp + "norm4", A, S * D)
+                    chained = chained_ffn(fp, "encoder.ffn", T * S, fp + "norm4", A, S * D)
                     ops.xattn_fused(src, pk, w[pre + "out_proj.bias"], S, src, a2=lvl_pos,
                                     ln_out=(w[fp + "norm3.weight"], w[fp + "norm3.bias"]), batch=T, sX=S * D, sOut=S * D,
                                     group=8, per_batch_weights=True, ffn=chained)
@@ -1164,7 +1164,7 @@ def _lateral(model, sc, feats, memory, vl_sites, T, L, ffn, ln_, stage, arx, G=1
         chained = None
         if pk is not None:
             # q-proj -> attention over the text keys -> out-proj -> + tgt -> norm2 in one token-stationary launch (one batch entry
-            # and one folded weight stream per clip); with the FFN + norm3 behind it in the same launch where chain_ffn allows
+            # and one folded weight stream per clip); with the FFN + norm3 behind it in the same launch where chained_ffn allows
             chained = ffn.chain(bp, "pixel.ffn", T * hw, bp + "norm3", A, Mc * D)
             ops.xattn_fused(tgt, pk, w[pre + "out_proj.bias"], Mc, tgt, a2=pos, a2_rows=hw,
                             ln_out=(w[bp + "norm2.weight"], w[bp + "norm2.bias"]), batch=G, sX=Mc * D, sOut=Mc * D,

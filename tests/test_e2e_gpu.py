@@ -324,7 +324,7 @@ def test_flag_combinations_match_oracle(flags):
 @pytest.mark.parametrize("L", [33, 70])
 def test_captions_longer_than_32_tokens_match_oracle(models, L):
     """More than 32 text tokens: the five text cross-attention sites leave the folded one-launch form (built for <= 32 keys,
-    csrc/chain.hip) for q-projection + attention over L keys + output projection (segmentation.py:366-371, tce_rvos.py:283-291);
+    csrc/ffn.hip) for q-projection + attention over L keys + output projection (segmentation.py:366-371, tce_rvos.py:283-291);
     eager launches and graph replays of that form against the oracle."""
     model = models("swin_t_p4w7", 31)
     T, H, W = 3, 80, 120

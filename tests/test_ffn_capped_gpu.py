@@ -1,4 +1,4 @@
-"""Capped (persistent) launches of the fused FFN / folded cross-attention (csrc/chain.hip PERSIST, tce_ffn_set_wg_cap, ops.ffn_wg_cap,
+"""Capped (persistent) launches of the fused FFN / folded cross-attention (csrc/ffn.hip PERSIST, tce_ffn_set_wg_cap, ops.ffn_wg_cap,
 TCE_LAT1_CUS / TCE_LAT1_AT): a capped launch runs the same blocks on fewer workgroups, so every check here is BIT identity against
 the uncapped launch -- no tolerance.  Rows: 5 * 128 + 37 = six 128-row blocks, the last ragged."""
 import ctypes

@@ -743,7 +743,7 @@ def _conv3_pack(S, Cin=256, N=256):
 @case("tce_conv3x3_split_f32", "5x90x160_mixed_rest_split", T=5, H=90, W=160, split=True, mixed=True, pieces=True)
 def _conv3(S, T, H, W, split=False, bias=True, Cin=256, N=256, waves=0, mixed=False, pieces=False):
     """waves: the workgroup form pinned (tce_debug_conv3x3_set_waves: 4 = 128-pixel, 8 = 256-pixel workgroups).  mixed: the
-    launcher's own choice must be one full round of 256-pixel workgroups + the rest as 128-pixel ones (csrc/chain.hip
+    launcher's own choice must be one full round of 256-pixel workgroups + the rest as 128-pixel ones (csrc/conv3x3.hip
     conv3x3_plan), read off the exported plan: the split workspace then covers exactly the pixels after that round.
     pieces: the split entry must really split (more than one piece)."""
     raw = _lib.lib_raw()

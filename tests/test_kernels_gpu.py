@@ -1129,6 +1129,49 @@ def test_rowlin(ops, M, N, K, batch, variant):
         close(out[0], F.linear(x[0] + pos[:rows][torch.arange(M) % rows], w, b), 2e-4, 2e-4)
 
 
+def test_ffn_stamp_buffer_reaches_ffn_and_rowlin(ops):
+    """tce_debug_ffn_set_stamp_buffer is ONE exported setter for TWO device pointers: ffn_fused_kernel (csrc/ffn.hip) and
+    rowlin_kernel (csrc/rowlin.hip) each read a copy of their own translation unit.  A launch of either writes its workgroups'
+    stamps (slot 0 = s_memtime at entry, slot 3 = at exit) while a buffer is set, and nothing once it is unset."""
+    from tce_rvos_amd._lib import lib
+    g = torch.Generator().manual_seed(5)
+    M, C, Hd, N = 128, 96, 32, 32   # one workgroup, one hidden chunk / one output tile
+    x = dev(torch.randn(M, C, generator=g))
+    fpk = ops.ffn_pack(dev(torch.randn(Hd, C, generator=g) / math.sqrt(C)), dev(torch.zeros(Hd)),
+                       dev(torch.randn(C, Hd, generator=g) / math.sqrt(Hd)))
+    b2 = dev(torch.zeros(C))
+    rpk = ops.rowlin_pack(dev(torch.randn(N, C, generator=g) / math.sqrt(C)))
+    fout, rout = torch.empty_like(x), torch.empty(M, N, device="cuda")
+
+    def run_ffn():
+        ops.ffn_fused(x, fpk, b2, Hd, ops.ACT_RELU, out=fout)
+
+    def run_rowlin():
+        ops.rowlin(x, rpk, rout, M, N, C, C, N)
+
+    buf = torch.zeros(1024, 8, dtype=torch.int64, device="cuda")
+    torch.cuda.synchronize()
+    try:
+        assert lib().tce_debug_ffn_set_stamp_buffer(buf.data_ptr()) == 0
+        for run in (run_ffn, run_rowlin):
+            buf.zero_()
+            run()
+            torch.cuda.synchronize()
+            row = buf[0].cpu()
+            entry, leave = int(row[0]), int(row[3])
+            assert entry != 0 and leave != 0 and leave >= entry, f"{run.__name__}: stamps of workgroup 0 {row.tolist()}"
+        buf.zero_()
+        torch.cuda.synchronize()
+        assert lib().tce_debug_ffn_set_stamp_buffer(None) == 0
+        run_ffn()
+        run_rowlin()
+        torch.cuda.synchronize()
+        assert not buf.any().item(), "a launch wrote stamps after the buffer was unset"
+    finally:
+        torch.cuda.synchronize()
+        lib().tce_debug_ffn_set_stamp_buffer(None)
+
+
 def test_msda_fused_lds_staged_is_bit_identical(ops):
     """Encoder-sized call (thousands of queries per frame): the LDS-staged kernel (coarse levels of a (frame, head) slice
     in LDS) against the L2-gather kernel it replaces -- same arithmetic, same order: bit-identical -- and against the

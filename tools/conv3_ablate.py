@@ -1,4 +1,4 @@
-"""Ablation of the pixel-stationary 3x3 convolution kernel (csrc/chain.hip).
+"""Ablation of the pixel-stationary 3x3 convolution kernel (csrc/conv3x3.hip).
 
     python tools/conv3_ablate.py --build    (CPU side: compiles the -DCONV_ABL=n variants into tce-rvos_amd/lib/abl/)
     python tools/conv3_ablate.py            (GPU side: times every variant)
@@ -29,7 +29,7 @@ if a.build:
     for n in VARIANTS:
         out = os.path.join(ABL, f"libconv_abl{n}.so")
         cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-shared", f"-DCONV_ABL={n}",
-               os.path.join(CSRC, "chain.hip"), os.path.join(CSRC, "capi.hip"), stub, "-o", out]
+               os.path.join(CSRC, "conv3x3.hip"), os.path.join(CSRC, "capi.hip"), stub, "-o", out]
         procs.append(subprocess.Popen(cmd))
     for n, p in zip(VARIANTS, procs):
         assert p.wait() == 0, f"variant {n} failed to build"

@@ -1,4 +1,4 @@
-"""Ablation + in-kernel stamps of the fused FFN kernel (csrc/chain.hip).
+"""Ablation + in-kernel stamps of the fused FFN kernel (csrc/ffn.hip).
 
     python tools/ffn_ablate.py --build      (CPU side: compiles the -DFFN_ABL=n variants into tce-rvos_amd/lib/abl/)
     python tools/ffn_ablate.py              (GPU side: times every variant on one shape, prints the stamp breakdown)
@@ -28,7 +28,8 @@ if a.build:
     for n in VARIANTS:
         out = os.path.join(ABL, f"libffn_abl{n}.so")
         cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-shared", f"-DFFN_ABL={n}",
-               os.path.join(CSRC, "chain.hip"), os.path.join(CSRC, "capi.hip"), stub, "-o", out]
+               os.path.join(CSRC, "ffn.hip"), os.path.join(CSRC, "rowlin.hip"),  # the stamp setter sets rowlin.hip's pointer too
+               os.path.join(CSRC, "capi.hip"), stub, "-o", out]
         procs.append(subprocess.Popen(cmd))
     for p in procs:
         assert p.wait() == 0

@@ -1,4 +1,4 @@
-"""Fused FFN kernel (csrc/chain.hip) vs the two-GEMM + LayerNorm path it replaces: parity vs torch fp64 and time."""
+"""Fused FFN kernel (csrc/ffn.hip) vs the two-GEMM + LayerNorm path it replaces: parity vs torch fp64 and time."""
 import sys, os, argparse
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

@@ -1,4 +1,4 @@
-"""Token-stationary linear kernel (csrc/chain.hip) vs the tiled split-fp16 GEMM on the K <= 256 shapes of config 2."""
+"""Token-stationary linear kernel (csrc/rowlin.hip) vs the tiled split-fp16 GEMM on the K <= 256 shapes of config 2."""
 import sys, os, argparse
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
