@@ -600,10 +600,18 @@ class ReferFormer(nn.Module):
         tok0 = T * ((H0 + 3) // 4) * ((W0 + 3) // 4)
         return self.arena_bytes or int(tok0 * 4 * (2048 * 2.2 + 256 * 24) + (256 << 20) + self._conv3_ws_bytes(T, H0, W0, (4, 8)))
 
-    def _get_arena(self, T, H0, W0, device, slot=0):
+    def _gather_bytes(self, rows, H0, W0):
+        """Bytes of the four dense maps of `rows` frames that an indexed group gathers from the backbone's maps (one per stage)."""
+        h, w, out = (H0 + 3) // 4, (W0 + 3) // 4, []
+        for c in self.cfg.num_channels:
+            out.append(int(rows) * h * w * int(c) * 4 + 256)
+            h, w = (h + 1) // 2, (w + 1) // 2
+        return out
+
+    def _get_arena(self, T, H0, W0, device, slot=0, extra=0):
         """The eager path's arena of `slot` (captured graphs own a private one each: their addresses are baked in).
         One arena per slot: forwards kept in flight on different streams must not share activations."""
-        need = self._arena_bytes(T, H0, W0)
+        need = self._arena_bytes(T, H0, W0) + int(extra)
         ar = self._arenas.get(slot)
         if ar is None or ar.buf.numel() < need or ar.device != torch.device(device):
             ar = self._arenas[slot] = ops.Arena(device, need)
@@ -808,6 +816,127 @@ class ReferFormer(nn.Module):
         ops.range_snapshot_async(clips[0].device)
         return self._split_group(out, G, Tc if sel is None else 1)
 
+    def _pool_plan(self, index, F):
+        """(index as a tuple of G int tuples, the pool frames the backbone runs over in its row order) of an indexed group over a
+        pool of F frames (pipeline.pool_segments: distinct frames for the 2-D backbones, distinct clips for Video-Swin)."""
+        from .pipeline import pool_segments
+        idx = tuple(tuple(int(v) for v in t) for t in index)
+        if not idx or not idx[0] or any(len(t) != len(idx[0]) for t in idx):
+            raise ValueError("indexed groups: G >= 1 index tuples of one length Tc >= 1")
+        if len(idx) > 64:
+            raise ValueError("indexed groups: G <= 64")
+        if any(not 0 <= v < F for t in idx for v in t):
+            raise ValueError(f"indexed groups: an index lies outside the pool's {F} frames")
+        return idx, pool_segments(idx, [(1, 1)], [1], "clip" if self.cfg.video else "frame")[0]
+
+    @torch.no_grad()
+    def forward_indexed(self, pool, index, captions, targets, ragged=False, slot=0):
+        """A clip group whose clips are index tuples into a pool of frames (an extension, like forward_group): one backbone pass per
+        DISTINCT frame, whatever number of (clip, caption) slots read it -- the windows of a video that overlap by their context
+        frames, each under several captions (video.run_video_windows(share="frames")).
+
+        pool: [F,3,H,W] un-padded frames on the GPU; index: G tuples of Tc ints in [0, F), clip g = pool[list(index[g])] -- a frame may
+        serve several clips and several positions of one clip; captions (one per slot; a caption may repeat), targets, ragged, slot
+        as in forward_group.  Returns G output dicts: result g is what forward([pool[list(index[g])]], captions[g], targets) returns
+        (same keys / shapes, values to the round-off forward_group documents).
+
+        The 2-D backbones (swin_*, resnet*) are frame-independent: the backbone runs over the distinct frames of `index`, U rows in
+        increasing pool order.  Video-Swin's 3-D windows span a clip, so its unit is the clip: the backbone runs over the distinct
+        index tuples in order of first appearance, one window launch per distinct clip.  After every backbone stage the rows of each
+        slot's frames are gathered into the dense map of the group program (pipeline.pool_segments, tce_copy_segments, issued where
+        the map's consumer runs); an identity gather launches nothing.  The text stage sees G captions: repeated captions are not
+        de-duplicated.  The gather's source addresses are arguments of the captured copy launches, so the index tuple is part of the
+        graph key (as valid_indices is): callers that want few graphs keep their indices relative to the pool.  G = 1 goes to
+        `forward`.  ValueError: 'valid_indices' in a target, an index outside the pool, tuples of different lengths, G > 64,
+        G != len(captions); NotImplementedError: padded input (a NestedTensor)."""
+        if hasattr(pool, "tensors") and hasattr(pool, "mask"):
+            raise NotImplementedError("indexed groups: un-padded frames only (a [F,3,H,W] tensor, not a NestedTensor)")
+        if not torch.is_tensor(pool) or pool.dim() != 4 or pool.shape[1] != 3:
+            raise ValueError("indexed groups: the pool is one tensor [F,3,H,W]")
+        if any("valid_indices" in t for t in targets):
+            raise ValueError("indexed groups: 'valid_indices' is not supported over a pool")
+        index, need = self._pool_plan(index, int(pool.shape[0]))
+        G, Tc = len(index), len(index[0])
+        if (len(captions) if isinstance(captions, (list, tuple)) else int(captions.shape[0])) != G:
+            raise ValueError(f"indexed groups: {G} index tuples but "
+                             f"{len(captions) if isinstance(captions, (list, tuple)) else int(captions.shape[0])} captions")
+        if not pool.is_cuda:
+            raise RuntimeError("inputs must be on the GPU: this path has no CPU implementation")
+        dev = pool.device
+        if ragged:
+            pad_id = self._pad_id()
+            if isinstance(captions, (list, tuple)):
+                captions, _ = pad_captions([self._tokenise([c], dev)[0] for c in captions], pad_id)
+            elif not captions.is_cuda:
+                caption_lengths(captions, pad_id)  # validation only: the device derives the lengths itself
+        if G == 1:
+            cap = captions[:1] if torch.is_tensor(captions) else [captions[0]]
+            if ragged and torch.is_tensor(cap):
+                cap = cap[:, :caption_lengths(cap.cpu(), self._pad_id())[0]]
+            return [self.forward([pool[list(index[0])]], cap, targets[:1], slot=slot)]
+        if isinstance(captions, (list, tuple)):
+            rows = [self._tokenise([c], dev)[0] for c in captions]
+            if len({int(r.shape[1]) for r in rows}) != 1:
+                raise ValueError("indexed groups: the captions must tokenise to one length (or ragged=True)")
+            ids = torch.cat(rows, 0)
+        else:
+            ids = captions
+        if ids.dim() != 2:
+            raise ValueError("indexed groups: token ids [G, L]")
+        size = targets[0]["size"]
+        img_h, img_w = float(size[0]), float(size[1])
+        if any((float(t["size"][0]), float(t["size"][1])) != (img_h, img_w) for t in targets[1:]):
+            raise ValueError("indexed groups: the clips of a group share one target size")
+        self._ensure_packed()
+        ops.range_poll(dev)
+        ids = ids.to(dev)
+        if ragged:
+            ids = ids.to(torch.int64).contiguous()
+        shp = tuple(pool.shape)
+        key = ("indexed", G, shp, tuple(ids.shape), img_h, img_w, self.training, int(slot), self._stamp) + \
+            (("ragged",) if ragged else ()) + (("index", index),)
+        # the backbone's frames as runs of consecutive pool frames: [first pool frame, frames]
+        runs = []
+        for f in need:
+            if runs and runs[-1][0] + runs[-1][1] == f:
+                runs[-1][1] += 1
+            else:
+                runs.append([f, 1])
+        whole = len(runs) == 1 and runs[0][1] == shp[0]  # the backbone sees the pool as it is
+
+        def frames_now():
+            if whole:
+                return pool.to(torch.float32).contiguous()
+            return torch.cat([pool[a:a + n].to(torch.float32) for a, n in runs], 0)
+
+        def eager():
+            return self._run(frames_now(), self._group_text(ids, ragged), img_h, img_w, None, slot, groups=G, index=index)
+
+        if not ragged and key[:-1] not in self._group_checked:  # padded captions in an un-ragged group: see forward_group
+            self._group_checked.add(key[:-1])
+            pad_id = self._pad_id()
+            if bool((ids == pad_id).any()):
+                raise ValueError(f"indexed groups: token ids contain the pad id ({pad_id}): padded captions need ragged=True")
+        if not self._want_graph(key):
+            out = eager()
+        else:
+            ent = self._graphs.get(key)
+            if ent is None:
+                st = (frames_now().clone() if whole else frames_now(), ids.clone())
+                text_fn = self._group_text(st[1], ragged)
+                like = types.SimpleNamespace(shape=(G * Tc,) + shp[1:], device=dev, gather=True)
+                ent = self._capture(key, st, lambda res: self._run(st[0], text_fn, img_h, img_w, res, groups=G, index=index), like, slot)
+            if ent is None:
+                out = eager()
+            else:  # the pool's runs go straight into their rows of the graph's static frame buffer (one copy launch)
+                at, statics = 0, []
+                for _, n in runs:
+                    statics.append(ent[1][0][at:at + n])
+                    at += n
+                out = self._replay(key, (ent[0], statics + [ent[1][1]]) + tuple(ent[2:]), [pool[a:a + n] for a, n in runs] + [ids])
+        ops.range_snapshot_async(dev)
+        return self._split_group(out, G, Tc)
+
     def _split_group(self, out, G, Tc):
         """The output dict of a whole group -> one dict per clip (Tc output frames each)."""
         def part(v, g):  # clip g's slice of an output of the whole group
@@ -953,29 +1082,36 @@ class ReferFormer(nn.Module):
         enc = self.text_encoder(input_ids=ids, attention_mask=att)
         return enc.last_hidden_state.float(), enc.pooler_output.float()
 
-    def _run(self, frames, text, img_h, img_w, res, slot=0, valid=None, groups=1, shared=False, select=None):
+    def _run(self, frames, text, img_h, img_w, res, slot=0, valid=None, groups=1, shared=False, select=None, index=None):
         from .pipeline import run_clip
         T, _, H0, W0 = frames.shape
         if res is None:  # eager: the slot's arena, single stream
-            return run_clip(self, frames, text, img_h, img_w, self._get_arena(T * (groups if shared else 1), H0, W0, frames.device, slot),
-                            valid=valid, groups=groups, shared=shared, select=select)
+            if index is not None:  # the group's G*Tc frames, and the gathered maps beside the backbone's
+                rows = len(index) * len(index[0])
+                ar = self._get_arena(rows, H0, W0, frames.device, slot, extra=sum(self._gather_bytes(rows, H0, W0)))
+            else:
+                ar = self._get_arena(T * (groups if shared else 1), H0, W0, frames.device, slot)
+            return run_clip(self, frames, text, img_h, img_w, ar, valid=valid, groups=groups, shared=shared, select=select, index=index)
         arena, side_arena, side_stream, arena2, stream2, arena3, stream3, arena4, stream4 = res
         return run_clip(self, frames, text, img_h, img_w, arena, side_arena, side_stream, clone_outputs=False, valid=valid,
-                        groups=groups, shared=shared, select=select,
+                        groups=groups, shared=shared, select=select, index=index,
                         fork2=(arena2, stream2) if os.environ.get("TCE_FORK2", "1") != "0" else None,
                         fork3=((arena3, stream3), (arena4, stream4)) if os.environ.get("TCE_FORK3", "1") != "0" else None)
 
     def _branch_resources(self, like, slot=0):
         """(arena, side arena, side stream, arena2, stream2, arena3, stream3, arena4, stream4) of one capture: the main arena
-        and one arena per parallel branch that allocates; the side streams are the (device, slot)'s shared set."""
+        and one arena per parallel branch that allocates; the side streams are the (device, slot)'s shared set.  like.gather (an
+        indexed group): T frames' maps are gathered from the backbone's -- room for each in the arena of the branch that consumes it
+        (stage 0: the stride-4 lateral branch, stages 1 / 2: the early input projections) and for all of them in the main arena."""
         T, _, H0, W0 = like.shape
         tok0 = T * ((H0 + 3) // 4) * ((W0 + 3) // 4)
         st = _side_streams(like.device, slot)
-        return (ops.Arena(like.device, self._arena_bytes(T, H0, W0)),
+        gb = self._gather_bytes(T, H0, W0) if getattr(like, "gather", False) else [0, 0, 0, 0]
+        return (ops.Arena(like.device, self._arena_bytes(T, H0, W0) + sum(gb)),
                 ops.Arena(like.device, T * self._tokens_per_frame(H0, W0) * 256 * 4 * 4 + (32 << 20)),
                 st[0],
                 # third branch: the pixel decoder's stride-4 lateral path (tgt + its self-attention / FFN temporaries)
-                ops.Arena(like.device, int(tok0 * 4 * (2048 * 1.1 + 256 * 4)) + (64 << 20)),
+                ops.Arena(like.device, int(tok0 * 4 * (2048 * 1.1 + 256 * 4)) + (64 << 20) + gb[0]),
                 st[1],
                 # fourth / fifth branch: the stride-32 lateral path + the merge chain down to stride 16 (tokens/64 and
                 # tokens/16 maps, two-GEMM FFN hidden [tokens/16 ... , 2048]); the stride-16 lateral path.  With the early
@@ -983,33 +1119,43 @@ class ReferFormer(nn.Module):
                 # (projection, GroupNorm output, q, attention output + workspaces: 5 maps of [tokens/4, 256]) -- the form
                 # exact-fp32 mode and captions longer than 32 tokens take
                 ops.Arena(like.device, max(int(tok0 / 64 * 4 * (2048 + 256 * 12)) + int(tok0 / 16 * 4 * 256 * 8),
-                                           int(tok0 / 4 * 4 * 256 * 5)) + (64 << 20) + self._conv3_ws_bytes(T, H0, W0, (16, 32))),
+                                           int(tok0 / 4 * 4 * 256 * 5)) + (64 << 20) + self._conv3_ws_bytes(T, H0, W0, (16, 32)) + gb[1]),
                 st[2],
-                ops.Arena(like.device, int(tok0 / 16 * 4 * (2048 * 1.1 + 256 * 12)) + (64 << 20)),
+                ops.Arena(like.device, int(tok0 / 16 * 4 * (2048 * 1.1 + 256 * 12)) + (64 << 20) + gb[2]),
                 st[3])
 
     @torch.no_grad()
     def hazard_check(self, frames, ids, img_hw=None, valid=None, slot=0, dry=False, groups=1, shared=False, ragged=False, observe=None,
-                     select=None):
+                     select=None, index=None):
         """Records ONE pass of the clip's launch program on the capture topology (the same arenas, side streams, forks and
         joins a captured graph is built from) and checks it for races: any two launches not ordered by a fork / join edge
         must touch disjoint memory (tce_rvos_amd/hazard.py).  frames [T,3,H,W] and token ids [1,L] on the GPU.
         dry=True: the recorded pass launches nothing (negative controls).  ragged=True: the ragged clip-group program
         (forward_group(..., ragged=True); ids [groups, Lmax] right-padded).  select: the single-frame path -- one index (groups = 1)
-        or one per clip of the group (with groups= / shared=: forward_group's valid_indices program).  Returns a hazard.Report (`.clean`, `str()`);
+        or one per clip of the group (with groups= / shared=: forward_group's valid_indices program).  index: forward_indexed's
+        program -- `frames` is then the pool [F,3,H,W], `index` the group's tuples of pool indices and ids [len(index), L] (groups is
+        taken from it).  Returns a hazard.Report (`.clean`, `str()`);
         results of the pass are discarded.  observe (tests): called as observe("before", resources, None) after the warm-up pass
         and observe("after", resources, recorder) after the recorded one, everything synchronised; it only looks on."""
         from . import hazard
         frames = frames.to(torch.float32).contiguous()
+        if index is not None:  # an indexed group: `frames` is the pool, the program runs on the frames its backbone needs
+            index, need = self._pool_plan(index, int(frames.shape[0]))
+            groups = len(index)
+            frames = frames[need].contiguous()
         T, _, H0, W0 = frames.shape
         img_h, img_w = (float(H0), float(W0)) if img_hw is None else (float(img_hw[0]), float(img_hw[1]))
         self._ensure_packed()
-        res = self._branch_resources(types.SimpleNamespace(shape=(T * (groups if shared else 1), 3, H0, W0), device=frames.device), slot)
+        if index is not None:
+            like = types.SimpleNamespace(shape=(groups * len(index[0]), 3, H0, W0), device=frames.device, gather=True)
+        else:
+            like = types.SimpleNamespace(shape=(T * (groups if shared else 1), 3, H0, W0), device=frames.device)
+        res = self._branch_resources(like, slot)
         st = (frames.clone(), ids.to(frames.device).clone())
         if select is not None:
             select = int(select) if groups == 1 and not isinstance(select, (tuple, list)) else tuple(int(v) for v in select)
         run = lambda: self._run(st[0], self._group_text(st[1], ragged), img_h, img_w, res, valid=valid, shared=shared,  # noqa: E731
-                                groups=groups, select=select)
+                                groups=groups, select=select, index=index)
         main = torch.cuda.Stream(device=frames.device)  # like a capture: never the legacy default stream (it syncs with all)
         main.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(main):

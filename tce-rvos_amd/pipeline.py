@@ -142,18 +142,60 @@ def pick_segments(G, Tc, indices, sizes, channels, shared=False):
     return table
 
 
+def pool_segments(index, sizes, channels, unit="frame"):
+    """The backbone's frame list and the copy table of a clip group over a frame pool (model.forward_indexed): clip g of the group is
+    pool[list(index[g])], G tuples of Tc pool indices each; a frame may serve several clips and several positions of one clip.
+    unit="frame" (2-D backbones: a frame's map depends on that frame alone): the backbone sees the distinct frames of `index` in
+    increasing pool order.  unit="clip" (Video-Swin: the 3-D windows span a clip): it sees the distinct index tuples back to back, in
+    order of first appearance.  Returns (frames, table): `frames` the pool indices the backbone runs over, in its row order; `table`
+    per level the segments (source row offset, rows, row words) that, applied in order, fill the dense [G*Tc*hw_i, C_i] map of the
+    group program from the backbone's [len(frames)*hw_i, C_i] map -- slot-major, consecutive source rows merged into one segment.
+    An identity gather (every slot frame distinct and in backbone order) has NO segments: the backbone's map is the group's map.
+    Pure host arithmetic."""
+    idx = [tuple(int(v) for v in t) for t in index]
+    if not idx or not idx[0] or any(len(t) != len(idx[0]) for t in idx):
+        raise ValueError("pool_segments: G >= 1 index tuples of one length Tc >= 1")
+    if any(v < 0 for t in idx for v in t):
+        raise ValueError("pool_segments: pool indices are >= 0")
+    Tc = len(idx[0])
+    if unit == "frame":
+        frames = sorted({v for t in idx for v in t})
+        at = {f: k for k, f in enumerate(frames)}
+        src = [at[v] for t in idx for v in t]  # the backbone row (in frames) of every slot frame
+    elif unit == "clip":
+        clips = list(dict.fromkeys(idx))
+        frames = [v for t in clips for v in t]
+        at = {t: k for k, t in enumerate(clips)}
+        src = [at[t] * Tc + j for t in idx for j in range(Tc)]
+    else:
+        raise ValueError(f"pool_segments: unit must be 'frame' or 'clip', got {unit!r}")
+    runs = []  # [first backbone frame, frames] of consecutive source frames
+    for s in src:
+        if runs and runs[-1][0] + runs[-1][1] == s:
+            runs[-1][1] += 1
+        else:
+            runs.append([s, 1])
+    identity = len(runs) == 1 and runs[0][0] == 0 and runs[0][1] == len(frames)
+    table = []
+    for (h, w), c in zip(sizes, channels):
+        hw = int(h) * int(w)
+        table.append([] if identity else [(a * hw, n * hw, int(c)) for a, n in runs])
+    return frames, table
+
+
 def run_clip(model, frames, text, img_h, img_w, ar, side_arena=None, side_stream=None, clone_outputs=True, fork2=None,
-             fork3=None, valid=None, groups=1, shared=False, select=None):
+             fork3=None, valid=None, groups=1, shared=False, select=None, index=None):
     """The clip's launch program with the model's own packed-weight routes active (ops.Routes).  valid = (rows, columns) of
     the frames that are not padding (None: un-padded clip).  select = targets[0]['valid_indices'] (tce_rvos.py:233-243); for a clip
-    group a sequence of `groups` indices, one per clip (pick_segments)."""
+    group a sequence of `groups` indices, one per clip (pick_segments).  index: a clip group over a frame pool -- `groups` tuples of
+    pool indices; `frames` then holds the backbone's frames, pool_segments(index, ...)[0], in that order."""
     with ops.routes(model._routes):
         return _run_clip(model, frames, text, img_h, img_w, ar, side_arena, side_stream, clone_outputs, fork2, fork3, valid, groups,
-                         shared, select)
+                         shared, select, index)
 
 
 def _run_clip(model, frames, text, img_h, img_w, ar, side_arena=None, side_stream=None, clone_outputs=True, fork2=None,
-              fork3=None, valid=None, groups=1, shared=False, select=None):
+              fork3=None, valid=None, groups=1, shared=False, select=None, index=None):
     """text: (last_hidden_state [L,768], pooler_output [768]) or a callable(alloc) returning them (the RoBERTa
     forward, run as a parallel branch beside the backbone when a side stream is given).
     side_arena / side_stream: the decoder (~100 latency-bound launches on 25 rows) runs as a parallel branch
@@ -175,7 +217,7 @@ def _run_clip(model, frames, text, img_h, img_w, ar, side_arena=None, side_strea
     G = int(groups)
     Tb, _, H0, W0 = frames.shape  # frames the backbone sees
     T = Tb * G if shared else Tb
-    if T % G:
+    if T % G and index is None:
         raise ValueError("clip group: frames must hold `groups` clips of equal length")
     # select (the A2D / JHMDB single-frame path, tce_rvos.py:233-243): the backbone sees the clip's Tb frames (Video-Swin's
     # windows span them), every stage after it only frame `select` -- the reference index_selects the features, their masks and
@@ -183,9 +225,29 @@ def _run_clip(model, frames, text, img_h, img_w, ar, side_arena=None, side_strea
     # A group with a selection (select = one index per clip): the backbone sees every frame of the G clips (shared: the one clip's
     # frames, once); after every stage the rows of frame g*Tc + select[g] of each clip are gathered into a dense [G*hw_i, C_i] map
     # (tce_copy_segments, one segment per clip and level: pick_segments) and the rest is the group program at T = G, Tc = 1.
+    # index (a group over a frame pool, model.forward_indexed): `frames` holds what the backbone must see -- the distinct frames of
+    # the index tuples (Video-Swin: the distinct tuples' frames) -- and after every stage the rows of each slot's frames are gathered
+    # into the dense [G*Tc*hw_i, C_i] map of the group program, with the selection's mechanism: one table per level
+    # (pool_segments), the copy issued in the arena and on the stream of the map's consumer.
     sel_many = isinstance(select, (tuple, list)) and G > 1
     seg_table = None
-    if sel_many:
+    gather = index is not None
+    if gather:
+        if select is not None or shared or valid is not None or G < 2:
+            raise ValueError("index: a group of two or more un-padded clips, without valid_indices")
+        index = tuple(tuple(int(v) for v in t) for t in index)
+        if len(index) != G:
+            raise ValueError(f"index: {G} clips but {len(index)} index tuples")
+        bb_frames, seg_table = pool_segments(index, [(1, 1)] * 4, cfg.num_channels, "clip" if cfg.video else "frame")
+        if len(bb_frames) != Tb:
+            raise ValueError(f"index: the backbone needs {len(bb_frames)} frames, `frames` holds {Tb}")
+        T = G * len(index[0])
+        Tcb = len(index[0])  # frames per clip in front of the backbone (Video-Swin's windows)
+        if not seg_table[0]:  # every slot frame distinct and in order: the backbone's maps ARE the group's maps
+            gather, seg_table = False, None
+    if gather:
+        pass  # T and Tcb are the index's
+    elif sel_many:
         select = tuple(int(v) for v in select)
         Tcb = Tb if shared else Tb // G  # frames per clip in front of the backbone
         if len(select) != G or any(not 0 <= v < Tcb for v in select):
@@ -358,6 +420,9 @@ def _run_clip(model, frames, text, img_h, img_w, ar, side_arena=None, side_strea
     chs = cfg.num_channels
     if sel_many:
         seg_table = pick_segments(G, Tcb, select, sizes, chs, shared)
+    elif gather:
+        seg_table = pool_segments(index, sizes, chs, "clip" if cfg.video else "frame")[1]
+    many = sel_many or gather  # the maps of the group are gathered from the backbone's
     early = (fork3 is not None and not cfg.is_resnet and fork3[0][1] is not None and fork3[1][1] is not None and
              side_stream is not None and EARLY_PROJ)
     src = A(T * S, D) if early else None  # [T, S, 256]: the encoder sequence
@@ -406,12 +471,12 @@ def _run_clip(model, frames, text, img_h, img_w, ar, side_arena=None, side_strea
     def pick(feat, i, alloc=None):
         """the selected frame's rows of stage i's map (valid_indices), else the map.  A group's selection is a gather: allocated
         from `alloc` (default: the main arena) and issued on the current stream -- where the map's consumer runs."""
-        if select is None:
+        if select is None and not gather:
             return feat
         hw_i = sizes[i][0] * sizes[i][1]
-        if not sel_many:
+        if not many:
             return feat[select * hw_i:(select + 1) * hw_i]
-        picked[i] = ops.copy_row_segments(feat, seg_table[i], (alloc or A)(G * hw_i, chs[i]))
+        picked[i] = ops.copy_row_segments(feat, seg_table[i], (alloc or A)(T * hw_i, chs[i]))
         return picked[i]
 
     lat1_cap = LAT1_CUS
@@ -426,7 +491,7 @@ def _run_clip(model, frames, text, img_h, img_w, ar, side_arena=None, side_strea
         with lat1_fork:
             while pending_norm0:
                 pending_norm0.pop()()  # Swin stage 0's output norm, here where its only consumer runs
-            if sel_many and picked[0] is None:  # a group's selection: stage 0's gather, in its consumer's arena and stream
+            if many and picked[0] is None:  # a group's selection: stage 0's gather, in its consumer's arena and stream
                 if feat0 is None:
                     feats[0] = pick(feats[0], 0, ar2.alloc)
                 else:
@@ -442,7 +507,7 @@ def _run_clip(model, frames, text, img_h, img_w, ar, side_arena=None, side_strea
             text_stage()
         if i == 0 and finish is not None:
             pending_norm0.append(finish)
-        if not sel_many:
+        if not many:
             feat = pick(feat, i)
         if i == 0 and LAT1_AT == "text" and ar2 is not None and stream2 is not None:
             lat1 = start_lat1(feat, wait_text=True)  # TCE_LAT1_AT=text: from the text join on, beside Swin stages 1-3
@@ -453,7 +518,7 @@ def _run_clip(model, frames, text, img_h, img_w, ar, side_arena=None, side_strea
                     with fk_:
                         if finish is not None:
                             finish()  # the stage's output norm, in this branch
-                        if sel_many:
+                        if many:
                             feat = pick(feat, i, arx.alloc)  # this level's gather, in its consumer's arena and stream
                         text_fork.join()  # this level's stream waits for the text branch (keys / values of the fusion)
                         input_level(i - 1, feat, arx.alloc)
@@ -461,13 +526,14 @@ def _run_clip(model, frames, text, img_h, img_w, ar, side_arena=None, side_strea
     if DEFER_OUT_NORM:
         # stage 0's map is read by the stride-4 lateral branch only (started later, on its own stream); stages 1 / 2 by their
         # level's early input projection (forked right here); stage 3 by the main stream itself
-        on_stage.defers = lambda i: select is None and ((i == 0 and ar2 is not None and stream2 is not None) or (i in (1, 2) and early))
+        on_stage.defers = lambda i: select is None and not gather and ((i == 0 and ar2 is not None and stream2 is not None) or (i in (1, 2) and early))
     if cfg.is_resnet:
         with model.arith("backbone.merge"):  # a ResNet is convolutions only: one site group
             feats = _resnet_backbone(model, frames, ar, sizes, rep=G if shared and not sel_many else 1)
     else:
-        feats = _swin_backbone(model, frames, ar, sizes, on_stage, 1 if shared else G, rep=G if shared and not sel_many else 1)
-    if sel_many:
+        feats = _swin_backbone(model, frames, ar, sizes, on_stage, Tb // Tcb if gather else (1 if shared else G),
+                               rep=G if shared and not sel_many else 1)
+    if many:
         # stages whose consumer's branch has gathered them keep that map; stage 0 waits for the stride-4 lateral branch (start_lat1)
         # where that branch exists; the others are read by the main stream's own work
         later0 = ar2 is not None and stream2 is not None
@@ -884,7 +950,7 @@ def _run_clip(model, frames, text, img_h, img_w, ar, side_arena=None, side_strea
     # ------------------------------------------------------------------ pixel decoder (segmentation.py:175-296)
     while pending_norm0:  # (the stride-4 lateral branch was never started: its input's norm runs here, before the decoder reads it)
         pending_norm0.pop()()
-    if sel_many and picked[0] is None:  # (and a group's selection of stage 0 with it)
+    if many and picked[0] is None:  # (and a group's selection of stage 0 with it)
         feats[0] = pick(feats[0], 0)
     mask_feats = _pixel_decoder(model, ar, sc, feats, memory, vl_sites, T, L, ffn, ln_, lat1=lat1, par=fork3, G=G)
     dec_fork.join()

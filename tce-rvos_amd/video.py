@@ -26,7 +26,8 @@ Two loops of the reference's callers, with the model call and the caller harness
   cut into windows of `num_frames` frames, each widened by `f_extra` context frames on both sides (clamped at the video's ends), the
   best query is chosen over the WIDENED window and only the window's own frames get a mask (ops.select_window_masks: a context
   frame costs no output plane).  `plan_windows` is the rule, `plan_window_forwards` the forwards: the expressions of a video share
-  the backbone per window, a lone expression runs several windows per forward.
+  the backbone per window, a lone expression runs several windows per forward.  `share="frames"` (opt-in) mixes
+  captions and windows in one forward over a pool of the windows' distinct frames (model.forward_indexed).
 
 A video's chunks share the caption, so with `model.text_cache_size > 0` RoBERTa runs once per expression instead of
 once per chunk (the reference recomputes it inside every forward).  Chunks of one length share a captured hipGraph
@@ -307,20 +308,47 @@ def plan_windows(n_frames: int, num_frames: int, f_extra: int = 0, last: str = "
     return plan
 
 
-def plan_window_forwards(lengths, windows, max_group: int = 4, windows_per_forward: int = 4, mixed_lengths: bool = False):
-    """The forwards of run_video_windows, in order: a list of (captions, windows), both lists of indices; every (caption, window)
-    pair appears exactly once.  model.forward_group shares the backbone only when ALL clips of a group are one tensor, so there are
-    two kinds of forward: an expression bucket (plan_expression_groups) of two or more captions runs one SHARED group per window
-    ([i, j, ...], [w]); a bucket of one caption runs its windows `windows_per_forward` at a time as distinct clips ([i], [w, ...]).
-    Only consecutive windows of one clip length go together, so a short last window goes alone.  `windows`: plan_windows' list."""
-    wpf = max(1, int(windows_per_forward))
-    runs = []  # consecutive windows of one clip length, at most wpf of them
+def _window_runs(windows, wpf):
+    """consecutive windows of one clip length, at most wpf of them"""
+    runs = []
     for w, win in enumerate(windows):
         if runs and len(runs[-1]) < wpf and len(windows[runs[-1][0]][0]) == len(win[0]):
             runs[-1].append(w)
         else:
             runs.append([w])
+    return runs
+
+
+def plan_window_forwards(lengths, windows, max_group: int = 4, windows_per_forward: int = 4, mixed_lengths: bool = False,
+                         share: str = "clips", max_pairs: int = 8):
+    """The forwards of run_video_windows, in order: a list of (captions, windows), both lists of indices; every (caption, window)
+    pair appears exactly once.  `windows`: plan_windows' list.
+
+    share="clips" (the default): model.forward_group shares the backbone only when ALL clips of a group are one tensor, so there
+    are two kinds of forward: an expression bucket (plan_expression_groups) of two or more captions runs one SHARED group per window
+    ([i, j, ...], [w]); a bucket of one caption runs its windows `windows_per_forward` at a time as distinct clips ([i], [w, ...]).
+    Only consecutive windows of one clip length go together, so a short last window goes alone.  (max_pairs is not read.)
+
+    share="frames" (opt-in; model.forward_indexed): a forward mixes captions and windows -- every bucket of c captions takes
+    max(1, max_pairs // c) consecutive windows of one clip length per forward, a lone caption included (windows_per_forward is not
+    read), so a forward has at most max_pairs (caption, window) slots unless the bucket alone is larger.  Its frames are a pool, the
+    sorted distinct frames of its windows (window_pool): each runs through the backbone once, however many slots read it.
+
+    Graph shapes per video with share="frames": the index tuples are relative to the forward's pool, so all interior forwards of a
+    bucket are ONE shape; the first forward (f_extra > 0: frame 0 repeated), the last one (the last frame repeated, or fewer
+    windows) and a short last window differ -- at most 4 shapes per bucket, 1 at f_extra = 0 when the windows divide evenly.  The
+    graph cache holds 6 entries and 96 GB by default (model.max_graphs, model.max_graph_bytes; a graph owns arenas for all its
+    slots' frames): a video of three buckets with f_extra > 0 asks for 8 shapes at max_pairs=4, and then evicts inside every video,
+    which was measured at HALF the default plan's rate -- use share="frames" where a video's shapes fit the cache."""
+    if share not in ("clips", "frames"):
+        raise ValueError(f"plan_window_forwards: share must be 'clips' or 'frames', got {share!r}")
     out = []
+    if share == "frames":
+        mp = max(1, int(max_pairs))
+        for grp in plan_expression_groups(lengths, max_group, mixed_lengths):
+            out += [(list(grp), list(r)) for r in _window_runs(windows, max(1, mp // len(grp)))]
+        return out
+    runs = _window_runs(windows, max(1, int(windows_per_forward)))
     for grp in plan_expression_groups(lengths, max_group, mixed_lengths):
         if len(grp) >= 2:
             out += [(list(grp), [w]) for w in range(len(windows))]
@@ -329,10 +357,20 @@ def plan_window_forwards(lengths, windows, max_group: int = 4, windows_per_forwa
     return out
 
 
+def window_pool(windows, wins, n_captions: int = 1):
+    """The frame pool of one share="frames" forward: (pool, index).  pool: the sorted distinct video frames of windows `wins` of
+    plan_windows' list; index: n_captions * len(wins) tuples of positions in `pool`, caption-major (slot c * len(wins) + k is window
+    wins[k] under the forward's c-th caption), so that [pool[p] for p in index[slot]] are that window's frame ids."""
+    pool = sorted({f for w in wins for f in windows[w][0]})
+    at = {f: k for k, f in enumerate(pool)}
+    rel = [tuple(at[f] for f in windows[w][0]) for w in wins]
+    return pool, [t for _ in range(int(n_captions)) for t in rel]
+
+
 @torch.no_grad()
 def run_video_windows(model, frames: torch.Tensor, captions, origin_hw, num_frames: int = 5, f_extra: int = 0, last: str = "short",
                       take: str = "leading", threshold: float = 0.5, max_group: int = 4, windows_per_forward: int = 4,
-                      mixed_lengths: bool = False):
+                      mixed_lengths: bool = False, share: str = "clips", max_pairs: int = 8):
     """The context-frame window loop over ONE video (see plan_windows for the rule and the module docstring for the citations).
     frames and origin_hw as in run_video; captions: a str, a LongTensor [1,L], or a list of either (a list returns a list).
     Returns per caption dict(masks uint8 [N,H0,W0], best_query int32 [n_windows], pred_logits [N,K], pred_boxes [N,4],
@@ -341,7 +379,13 @@ def run_video_windows(model, frames: torch.Tensor, captions, origin_hw, num_fram
     Each window's clip is frames.index_select(0, ids) on the device (the indices of all windows go up in one copy before the loop);
     `masks` is allocated once and every window's output stage writes its own slice of it.  Nothing inside the loop waits for the GPU.
     With take="leading" (the default: what the reference's published numbers were made with) and f_extra > 0 a frame's mask comes
-    from a frame up to f_extra earlier; take="centre" aligns them."""
+    from a frame up to f_extra earlier; take="centre" aligns them.
+
+    share="frames" (opt-in; plan_window_forwards has the rule): a forward holds up to max_pairs (caption, window) slots over a pool
+    of its windows' distinct frames (model.forward_indexed), so the context frames that neighbouring windows repeat, the frames
+    clamped at the video's ends and the windows that several captions read each pass the backbone once per forward.  The pool is one
+    index_select into the video (the pool indices of all forwards go up in one copy before the loop); outputs are as above, to the
+    round-off between one group shape and another."""
     if frames.dim() != 4 or frames.shape[1] != 3 or frames.shape[0] == 0:
         raise ValueError("run_video_windows: frames must be a non-empty [N,3,H,W]")
     single = isinstance(captions, str) or torch.is_tensor(captions)
@@ -355,7 +399,10 @@ def run_video_windows(model, frames: torch.Tensor, captions, origin_hw, num_fram
     target = [{"size": torch.tensor([H, W])}]
     plan = plan_windows(n, num_frames, f_extra, last, take)
     ids = [c if torch.is_tensor(c) else model._tokenise([c], dev)[0] for c in caps]
-    forwards = plan_window_forwards([int(t.shape[1]) for t in ids], plan, max_group, windows_per_forward, mixed_lengths)
+    forwards = plan_window_forwards([int(t.shape[1]) for t in ids], plan, max_group, windows_per_forward, mixed_lengths, share,
+                                    max_pairs)
+    if share == "frames":
+        return _run_window_pools(model, frames, caps, ids, plan, forwards, (H0, W0), target, threshold, mixed_lengths, single)
     flat = torch.tensor([i for win in plan for i in win[0]], dtype=torch.int64).to(dev)  # every window's indices: one copy
     offs = [0]
     for win in plan:
@@ -383,20 +430,61 @@ def run_video_windows(model, frames: torch.Tensor, captions, origin_hw, num_fram
         else:  # one tensor, len(grp) captions: shared backbone
             outs = model.forward_group(clips * len(grp), toks[(tuple(grp), 1)], target, **({"ragged": True} if mixed_lengths else {}))
             pairs = [(i, wins[0]) for i in grp]
-        for (i, w), out in zip(pairs, outs):
-            _, first, count, lo = plan[w]
-            r = res[i]
-            pl = out["pred_logits"][0]
-            # harness H of a window: the query over the widened clip, the kept planes straight into the video's masks
-            _, b = ops.select_window_masks(pl, out["pred_masks"][0], (H0, W0), first, count, threshold,
-                                           out=r["masks"][lo:lo + count], best_out=r["best_query"][w:w + 1])
-            idx = b.long().expand(count)
-            ar = torch.arange(first, first + count, device=dev)
-            r["pred_logits"][w] = pl[ar, idx]
-            r["pred_boxes"][w] = out["pred_boxes"][0][ar, idx]
-            r["reference_points"][w] = out["reference_points"][0][ar, idx]
+        _store_windows(res, plan, pairs, outs, (H0, W0), threshold, dev)
+    return _window_results(res, plan, single, dev)
+
+
+def _store_windows(res, plan, pairs, outs, origin_hw, threshold, dev):
+    """harness H of every (caption, window) pair of one forward: the query over the widened clip, the kept planes straight into the
+    video's masks"""
+    for (i, w), out in zip(pairs, outs):
+        _, first, count, lo = plan[w]
+        r = res[i]
+        pl = out["pred_logits"][0]
+        _, b = ops.select_window_masks(pl, out["pred_masks"][0], origin_hw, first, count, threshold,
+                                       out=r["masks"][lo:lo + count], best_out=r["best_query"][w:w + 1])
+        idx = b.long().expand(count)
+        ar = torch.arange(first, first + count, device=dev)
+        r["pred_logits"][w] = pl[ar, idx]
+        r["pred_boxes"][w] = out["pred_boxes"][0][ar, idx]
+        r["reference_points"][w] = out["reference_points"][0][ar, idx]
+
+
+def _window_results(res, plan, single, dev):
     ops.check_range(dev)
     ret = [{"masks": r["masks"], "best_query": r["best_query"], "pred_logits": torch.cat(r["pred_logits"], 0),
             "pred_boxes": torch.cat(r["pred_boxes"], 0), "reference_points": torch.cat(r["reference_points"], 0), "windows": plan}
            for r in res]
     return ret[0] if single else ret
+
+
+def _run_window_pools(model, frames, caps, ids, plan, forwards, origin_hw, target, threshold, mixed_lengths, single):
+    """run_video_windows(share="frames"): every planned forward is one model.forward_indexed over the pool of its windows' frames."""
+    n, dev = int(frames.shape[0]), frames.device
+    pools = [window_pool(plan, wins, len(grp)) for grp, wins in forwards]
+    flat = torch.tensor([f for pool, _ in pools for f in pool], dtype=torch.int64).to(dev)  # every forward's pool: one copy
+    offs = [0]
+    for pool, _ in pools:
+        offs.append(offs[-1] + len(pool))
+    toks = {}
+    for grp, wins in forwards:
+        key = (tuple(grp), len(wins))
+        if key in toks:
+            continue
+        rows = [ids[i] for i in grp for _ in wins]  # caption-major: a caption's windows are neighbours
+        if len(rows) == 1:  # one caption, one window: the host ids, as run_video passes them
+            toks[key] = rows[0]
+        elif mixed_lengths:  # right-padded on the host (validated there), lengths derived again on the device
+            from .model import pad_captions
+            toks[key] = pad_captions(rows, model._pad_id())[0].to(dev)
+        else:
+            toks[key] = torch.cat([r.to(dev) for r in rows], 0)
+    res = [{"masks": torch.empty((n,) + tuple(origin_hw), dtype=torch.uint8, device=dev),
+            "best_query": torch.empty(len(plan), dtype=torch.int32, device=dev),
+            "pred_logits": [None] * len(plan), "pred_boxes": [None] * len(plan), "reference_points": [None] * len(plan)} for _ in caps]
+    for k, (grp, wins) in enumerate(forwards):
+        pool = frames.index_select(0, flat[offs[k]:offs[k + 1]])
+        outs = model.forward_indexed(pool, pools[k][1], toks[(tuple(grp), len(wins))], target,
+                                     **({"ragged": True} if mixed_lengths and len(grp) * len(wins) > 1 else {}))
+        _store_windows(res, plan, [(i, w) for i in grp for w in wins], outs, origin_hw, threshold, dev)
+    return _window_results(res, plan, single, dev)

@@ -4,7 +4,11 @@ ops.select_masks over the WHOLE clip, a slice of the kept planes.  Config-2 fram
 video, num_frames 5, f_extra 0 / 1 / 2, one caption of 9 tokens and five captions of 6 / 9 / 9 / 14 / 14 tokens (two shared pairs and
 one caption alone).  Every variant is warmed (eager sighting, capture, replay) right before it is timed, because the graph cache
 holds fewer shapes than the table has; the variants of a row are timed twice, alternating, inside this one process.  Host clock
-around a synchronise; no profiler.   python tools/window_bench.py [--reps N] [--out FILE]"""
+around a synchronise; no profiler.  The share="frames" driver (model.forward_indexed over each forward's pool of distinct frames,
+DESIGN 3.19) runs at max_pairs 4 / 8 beside them; its rows are judged against "driver wpf=4" (the default plan): faster only if the
+ratio of means exceeds 1.05 and the two passes of the two variants do not overlap.  Per variant and video: the graph shapes one
+video asks for, and the graphs captured DURING the timed videos (all shapes were warm: a capture there is an eviction inside a video).
+   python tools/window_bench.py [--reps N] [--out FILE] [--only NAME,NAME]"""
 import argparse
 import os
 import sys
@@ -22,6 +26,7 @@ ap.add_argument("--frames", type=int, default=40)
 ap.add_argument("--hw", default="360,640")
 ap.add_argument("--origin", default="720,1280")
 ap.add_argument("--out", default=None)
+ap.add_argument("--only", default=None, help="comma list of variant names (the hand loop always runs: it is the reference)")
 args = ap.parse_args()
 
 if not torch.cuda.is_available():
@@ -70,14 +75,29 @@ def driver(wpf):
     return run
 
 
-VARIANTS = [("hand loop", hand_loop), ("driver wpf=1", driver(1)), ("driver wpf=4", driver(4)), ("driver wpf=8", driver(8))]
+def frames_driver(mp):
+    def run(caps, e):
+        return [r["masks"] for r in run_video_windows(model, frames, caps, ORIGIN, NF, e, share="frames", max_pairs=mp)]
+    return run
+
+
+VARIANTS = [("hand loop", hand_loop), ("driver wpf=1", driver(1)), ("driver wpf=4", driver(4)), ("driver wpf=8", driver(8)),
+            ("frames mp=4", frames_driver(4)), ("frames mp=8", frames_driver(8))]
+if args.only:
+    VARIANTS = [v for v in VARIANTS if v[0] == "hand loop" or v[0] in args.only.split(",")]
+BASE = "driver wpf=4"  # the default plan: what share="frames" is judged against
+# graph shapes a video asks for / graphs captured while it is timed
+shapes, captured = set(), [0]
+_want, _capture = model._want_graph, model._capture
+model._want_graph = lambda key: (shapes.add(key), _want(key))[1]
+model._capture = lambda *a, **k: (captured.__setitem__(0, captured[0] + 1), _capture(*a, **k))[1]
 lines = [f"window_bench: swin_t_p4w7 {H}x{W} -> {ORIGIN[0]}x{ORIGIN[1]}, {N} frames, num_frames {NF}, reps {args.reps}, "
          f"{torch.cuda.get_device_name(0)}",
          "frames/s = video frames that got a mask, per second, summed over the captions; two alternating passes per variant"]
 for lens in ([9], [6, 9, 9, 14, 14]):
     caps = captions(lens)
     for e in (0, 1, 2):
-        ref, fps = None, {name: [] for name, _ in VARIANTS}
+        ref, fps, graphs = None, {name: [] for name, _ in VARIANTS}, {}
         for _ in range(2):  # alternate the variants: the second pass shows the spread
             for name, fn in VARIANTS:
                 try:
@@ -87,11 +107,14 @@ for lens in ([9], [6, 9, 9, 14, 14]):
                     if ref is None:
                         ref = got
                     same = sum(int((a != b).sum()) for a, b in zip(got, ref))  # pixels that differ from the hand loop's
+                    shapes.clear()
+                    captured[0] = 0
                     t0 = time.perf_counter()
                     for _ in range(args.reps):
                         fn(caps, e)
                     torch.cuda.synchronize()
                     dt = (time.perf_counter() - t0) / args.reps
+                    graphs[name] = (len(shapes), max(captured[0], graphs.get(name, (0, 0))[1]))
                     fps[name].append((N * len(caps) / dt, same))
                 except torch.cuda.OutOfMemoryError as err:  # a group too large for the card's free memory: reported, not timed
                     fps[name].append((float("nan"), -1))
@@ -102,7 +125,14 @@ for lens in ([9], [6, 9, 9, 14, 14]):
             mean = sum(v for v, _ in fps[name]) / 2
             lines.append(f"  {name:13s} {fps[name][0][0]:8.1f} {fps[name][1][0]:8.1f} frames/s   x{mean / base:5.3f} of the hand loop   "
                          f"{max(s for _, s in fps[name])} of {N * len(caps) * ORIGIN[0] * ORIGIN[1]} mask pixels differ from the hand loop's")
-        print("\n".join(lines[-5:]), flush=True)
+            if name in graphs:
+                lines[-1] += f"   {graphs[name][0]} graph shapes per video, {graphs[name][1]} captured while timed"
+            if name.startswith("frames") and BASE in fps:
+                mine, theirs = [v for v, _ in fps[name]], [v for v, _ in fps[BASE]]
+                ratio = mean / (sum(theirs) / 2)
+                faster = ratio > 1.05 and min(mine) > max(theirs)
+                lines[-1] += f"   x{ratio:5.3f} of {BASE}: {'faster' if faster else 'NOT faster'}"
+        print("\n".join(lines[-(1 + len(VARIANTS)):]), flush=True)
         if args.out:  # after every row: a later failure keeps what was measured
             with open(args.out, "w") as f:
                 f.write("\n".join(lines) + "\n")
