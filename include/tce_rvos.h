@@ -294,7 +294,10 @@ int tce_resize_v_norm_f32(const uint8_t* tmp, const int32_t* coef, const int32_t
  *   tce_embed_ln_f32     out[t] = LayerNorm(word[ids[t]] + position[pos_ids[t]] + token_type[0])   (ids int64, device);
  *                        pos_ids NULL: derived in-kernel as HF's create_position_ids_from_input_ids does
  *                        (pad_id + running count of non-pad tokens; pad tokens -> pad_id)
- *   tce_mha_small64_f32  self-attention core over packed qkv [L, 3*nheads*64] (head_dim 64, L <= 128) -> [L, nheads*64]
+ *   tce_mha_small64_f32  self-attention core over packed qkv [L, 3*nheads*64] (head_dim 64, 1 <= L <= 512) -> [L, nheads*64];
+ *                        up to 128 tokens K and V of the sentence sit in LDS whole, above that they pass through it in tiles
+ *                        of 64 keys: each key meets the same arithmetic in the same order either way.  The same holds for
+ *                        the _splits_, _seqs_ and _lens_ forms below; L outside 1..512 is rejected before any launch.
  *   tce_tanh_f32         pooler activation */
 int tce_embed_ln_f32(const int64_t* ids, const int64_t* pos_ids, const float* word, const float* pos, const float* type0,
                      const float* gamma, const float* beta, float* out, int32_t L, int32_t C, float eps, int32_t pad_id,

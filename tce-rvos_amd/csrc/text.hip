@@ -54,8 +54,44 @@ __global__ void __launch_bounds__(256) embed_ln_kernel(const int64_t* __restrict
   }
 }
 
-// Short-sequence self-attention with head_dim 64 (12 heads x 64 for RoBERTa-base).  One workgroup per head; K and V
-// of the whole sentence (L <= 128 tokens) live in LDS; lane = query row.
+// The keys sK / sV[0 .. n) of one staged tile folded into a query quarter's running softmax (m, l, o[]), one key at a time.  Both
+// attention kernels below walk their keys through this one body, so a key meets the same statements in the same order whether the
+// sentence was staged whole or in tiles: the result of a row depends on its keys and their order only, not on the kernel.
+template <int HDIM>
+__device__ __forceinline__ void mha_fold_keys(const float* __restrict__ sK, const float* __restrict__ sV, int n, int part,
+                                              const float (&q)[HDIM / 4], float& m, float& l, float (&o)[HDIM / 4]) {
+  constexpr int QD = HDIM / 4;
+  for (int j = 0; j < n; ++j) {
+    const f32x4* kp = reinterpret_cast<const f32x4*>(&sK[j * HDIM + part * QD]);
+    float a = 0.f;
+#pragma unroll
+    for (int d4 = 0; d4 < QD / 4; ++d4) {
+      const f32x4 kv = kp[d4];
+      a = fmaf(q[d4 * 4 + 0], kv[0], a);
+      a = fmaf(q[d4 * 4 + 1], kv[1], a);
+      a = fmaf(q[d4 * 4 + 2], kv[2], a);
+      a = fmaf(q[d4 * 4 + 3], kv[3], a);
+    }
+    a += __shfl_xor(a, 1, 64);
+    a += __shfl_xor(a, 2, 64);
+    const float mnew = fmaxf(m, a);
+    const float corr = __expf(m - mnew), pj = __expf(a - mnew);
+    l = l * corr + pj;
+    const f32x4* vp = reinterpret_cast<const f32x4*>(&sV[j * HDIM + part * QD]);
+#pragma unroll
+    for (int d4 = 0; d4 < QD / 4; ++d4) {
+      const f32x4 vv = vp[d4];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) o[d4 * 4 + c] = fmaf(pj, vv[c], o[d4 * 4 + c] * corr);
+    }
+    m = mnew;
+  }
+}
+
+// Short-sequence self-attention with head_dim 64 (12 heads x 64 for RoBERTa-base).  One workgroup per (head, block of 32
+// queries, sequence), four lanes per query.  Two kernels share this contract: mha_small_kernel keeps K and V of the whole
+// sentence (L <= LMAX = 128 tokens) in LDS; mha_tiled_kernel below walks longer sentences (the launchers send it 129..512
+// tokens, RoBERTa's position table) in tiles of TK keys.
 // splits > 1 / bias: qkv is given as `splits` partial planes [L, 3E] (split-K partial sums, plane stride L*3E) + a bias [3E]:
 // the reduction of the projection rides in this kernel's loads (no reduce launch between projection and attention).
 // lens != NULL (right-padded captions of a ragged clip group): sequence z's keys stop at lens[z] (HF's attention_mask); every
@@ -108,32 +144,76 @@ __global__ void __launch_bounds__(256) mha_small_kernel(const float* __restrict_
   float o[QD];
 #pragma unroll
   for (int d = 0; d < QD; ++d) o[d] = 0.f;
-  for (int j = 0; j < Lk; ++j) {  // online softmax, one key at a time (L is tiny)
-    const f32x4* kp = reinterpret_cast<const f32x4*>(&sK[j * HDIM + part * QD]);
-    float a = 0.f;
-#pragma unroll
-    for (int d4 = 0; d4 < QD / 4; ++d4) {
-      const f32x4 kv = kp[d4];
-      a = fmaf(q[d4 * 4 + 0], kv[0], a);
-      a = fmaf(q[d4 * 4 + 1], kv[1], a);
-      a = fmaf(q[d4 * 4 + 2], kv[2], a);
-      a = fmaf(q[d4 * 4 + 3], kv[3], a);
-    }
-    a += __shfl_xor(a, 1, 64);
-    a += __shfl_xor(a, 2, 64);
-    const float mnew = fmaxf(m, a);
-    const float corr = __expf(m - mnew), pj = __expf(a - mnew);
-    l = l * corr + pj;
-    const f32x4* vp = reinterpret_cast<const f32x4*>(&sV[j * HDIM + part * QD]);
-#pragma unroll
-    for (int d4 = 0; d4 < QD / 4; ++d4) {
-      const f32x4 vv = vp[d4];
-#pragma unroll
-      for (int c = 0; c < 4; ++c) o[d4 * 4 + c] = fmaf(pj, vv[c], o[d4 * 4 + c] * corr);
-    }
-    m = mnew;
-  }
+  mha_fold_keys<HDIM>(sK, sV, Lk, part, q, m, l, o);  // online softmax, one key at a time (L is tiny)
   if (i >= L) return;
+  const float inv = 1.f / l;
+  float* po = out + (long long)i * E + h * HDIM + part * QD;
+#pragma unroll
+  for (int d4 = 0; d4 < QD / 4; ++d4) {
+    f32x4 v = {o[d4 * 4] * inv, o[d4 * 4 + 1] * inv, o[d4 * 4 + 2] * inv, o[d4 * 4 + 3] * inv};
+    *reinterpret_cast<f32x4*>(po + d4 * 4) = v;
+  }
+}
+
+// The same attention for sentences that do not fit LDS whole: same arguments, same grid, same four lanes per query, but K and V
+// pass through LDS in tiles of TK keys and (m, l, o[]) stay in registers from one tile to the next.  TK = 64 (2 x 16 KB of LDS): a
+// workgroup alternates between staging and folding with nothing in flight across its barriers, so what covers a staging round
+// trip is the other workgroups of the CU -- five of them at 32 KB against two at the 64 KB of a 128-key tile.
+// Barriers: the trip count comes from Lk of blockIdx.z alone, so it is the same for all 256 threads, and every thread -- the upper
+// 128 that only stage, and the idle queries i >= L of a last block -- runs every tile's two barriers; nothing returns before the
+// loop ends and only the final store is predicated.  Tiles wholly past lens[z] are never entered.
+template <int HDIM, int TK>
+__global__ void __launch_bounds__(256) mha_tiled_kernel(const float* __restrict__ qkv, float* __restrict__ out, int L,
+                                                        int nheads, float scale, int splits, const float* __restrict__ bias,
+                                                        const int* __restrict__ lens) {
+  __shared__ __attribute__((aligned(16))) float sK[TK * HDIM];
+  __shared__ __attribute__((aligned(16))) float sV[TK * HDIM];
+  const int h = blockIdx.x;
+  const int E = nheads * HDIM;
+  const int tid = threadIdx.x;
+  const int Lk = lens ? min(max(lens[blockIdx.z], 1), L) : L;  // keys of this sequence: uniform over the workgroup
+  const long long plane = (long long)L * gridDim.z * 3 * E;
+  qkv += (long long)blockIdx.z * L * 3 * E;
+  out += (long long)blockIdx.z * L * E;
+  auto ld4 = [&](const float* p, int col) {  // sum of the partial planes (+ bias) at p
+    f32x4 v = *reinterpret_cast<const f32x4*>(p);
+    for (int s = 1; s < splits; ++s) v += *reinterpret_cast<const f32x4*>(p + s * plane);
+    if (bias) v += *reinterpret_cast<const f32x4*>(bias + col);
+    return v;
+  };
+  constexpr int QD = HDIM / 4;
+  const bool folds = tid < 128;  // the upper 128 threads stage only
+  const int i = blockIdx.y * 32 + ((tid & 127) >> 2), part = tid & 3;
+  const int ic = min(i, L - 1);
+  float q[QD];
+#pragma unroll
+  for (int d = 0; d < QD; ++d) q[d] = 0.f;
+  if (folds) {
+    const float* p = qkv + (long long)ic * 3 * E + h * HDIM + part * QD;
+#pragma unroll
+    for (int d4 = 0; d4 < QD / 4; ++d4) {
+      const f32x4 v = ld4(p + d4 * 4, h * HDIM + part * QD + d4 * 4);
+#pragma unroll
+      for (int c = 0; c < 4; ++c) q[d4 * 4 + c] = v[c] * scale;
+    }
+  }
+  float m = -3.0e38f, l = 0.f;
+  float o[QD];
+#pragma unroll
+  for (int d = 0; d < QD; ++d) o[d] = 0.f;
+  for (int k0 = 0; k0 < Lk; k0 += TK) {
+    const int n = min(TK, Lk - k0);  // keys of this tile
+    if (k0) __syncthreads();         // the previous tile has been folded by every query
+    for (int e = tid; e < n * (HDIM / 4); e += 256) {
+      const int j = e / (HDIM / 4), d4 = e % (HDIM / 4);
+      const float* p = qkv + (long long)(k0 + j) * 3 * E + h * HDIM + d4 * 4;
+      *reinterpret_cast<f32x4*>(&sK[j * HDIM + d4 * 4]) = ld4(p + E, E + h * HDIM + d4 * 4);
+      *reinterpret_cast<f32x4*>(&sV[j * HDIM + d4 * 4]) = ld4(p + 2 * E, 2 * E + h * HDIM + d4 * 4);
+    }
+    __syncthreads();
+    if (folds) mha_fold_keys<HDIM>(sK, sV, n, part, q, m, l, o);
+  }
+  if (!folds || i >= L) return;
   const float inv = 1.f / l;
   float* po = out + (long long)i * E + h * HDIM + part * QD;
 #pragma unroll
@@ -176,6 +256,17 @@ __global__ void __launch_bounds__(256) tanh_kernel(const float* __restrict__ x, 
   if (i < n) out[i] = (float)tanh((double)x[i]);
 }
 
+// The four tce_mha_small64_* entries share this dispatch: up to 128 tokens the whole-sentence kernel (the launch it has always
+// been), 129 .. MHA_SMALL_LMAX the key-tiled one on the same grid.  The callers have checked 1 <= L <= MHA_SMALL_LMAX.
+constexpr int MHA_SMALL_LMAX = 512;  // RoBERTa's position table (514 rows, ids from pad_id + 1)
+void mha_small64_launch(dim3 grid, hipStream_t stream, const float* qkv, float* out, int L, int nheads, float scale, int splits,
+                        const float* bias, const int* lens) {
+  if (L <= 128)
+    hipLaunchKernelGGL((mha_small_kernel<64, 128>), grid, dim3(256), 0, stream, qkv, out, L, nheads, scale, splits, bias, lens);
+  else
+    hipLaunchKernelGGL((mha_tiled_kernel<64, 64>), grid, dim3(256), 0, stream, qkv, out, L, nheads, scale, splits, bias, lens);
+}
+
 }  // namespace
 
 extern "C" int tce_embed_ln_f32(const int64_t* ids, const int64_t* pos_ids, const float* word, const float* pos,
@@ -204,10 +295,9 @@ extern "C" int tce_embed_ln_seqs_f32(const int64_t* ids, const float* word, cons
 extern "C" int tce_mha_small64_f32(const float* qkv, float* out, int32_t L, int32_t nheads, float scale,
                                    tceStream stream) {
   TCE_CHECK_ARG(qkv && out && nheads > 0, "tce_mha_small64_f32: bad arguments");
-  TCE_CHECK_ARG(L > 0 && L <= 128, "tce_mha_small64_f32: sequence length %d outside 1..128", L);
+  TCE_CHECK_ARG(L > 0 && L <= MHA_SMALL_LMAX, "tce_mha_small64_f32: sequence length %d outside 1..512", L);
   TCE_CHECK_ARG(tce_aligned16(qkv) && tce_aligned16(out), "tce_mha_small64_f32: pointers must be 16-byte aligned");
-  hipLaunchKernelGGL((mha_small_kernel<64, 128>), dim3(nheads, tce_cdiv(L, 32)), dim3(256), 0, (hipStream_t)stream, qkv, out, L,
-                     nheads, scale, 1, (const float*)nullptr, (const int*)nullptr);
+  mha_small64_launch(dim3(nheads, tce_cdiv(L, 32)), (hipStream_t)stream, qkv, out, L, nheads, scale, 1, (const float*)nullptr, (const int*)nullptr);
   TCE_CHECK_LAUNCH("tce_mha_small64_f32");
   return TCE_OK;
 }
@@ -215,11 +305,10 @@ extern "C" int tce_mha_small64_f32(const float* qkv, float* out, int32_t L, int3
 extern "C" int tce_mha_small64_splits_f32(const float* qkv_planes, int32_t splits, const float* bias, float* out, int32_t L,
                                           int32_t nheads, float scale, tceStream stream) {
   TCE_CHECK_ARG(qkv_planes && out && nheads > 0 && splits >= 1 && splits <= 64, "tce_mha_small64_splits_f32: bad arguments");
-  TCE_CHECK_ARG(L > 0 && L <= 128, "tce_mha_small64_splits_f32: sequence length %d outside 1..128", L);
+  TCE_CHECK_ARG(L > 0 && L <= MHA_SMALL_LMAX, "tce_mha_small64_splits_f32: sequence length %d outside 1..512", L);
   TCE_CHECK_ARG(tce_aligned16(qkv_planes) && tce_aligned16(out) && (!bias || tce_aligned16(bias)),
                 "tce_mha_small64_splits_f32: pointers must be 16-byte aligned");
-  hipLaunchKernelGGL((mha_small_kernel<64, 128>), dim3(nheads, tce_cdiv(L, 32)), dim3(256), 0, (hipStream_t)stream, qkv_planes, out,
-                     L, nheads, scale, splits, bias, (const int*)nullptr);
+  mha_small64_launch(dim3(nheads, tce_cdiv(L, 32)), (hipStream_t)stream, qkv_planes, out, L, nheads, scale, splits, bias, (const int*)nullptr);
   TCE_CHECK_LAUNCH("tce_mha_small64_splits_f32");
   return TCE_OK;
 }
@@ -227,11 +316,10 @@ extern "C" int tce_mha_small64_splits_f32(const float* qkv_planes, int32_t split
 extern "C" int tce_mha_small64_seqs_f32(const float* qkv_planes, int32_t splits, const float* bias, float* out, int32_t nseq, int32_t L,
                                         int32_t nheads, float scale, tceStream stream) {
   TCE_CHECK_ARG(qkv_planes && out && nheads > 0 && splits >= 1 && splits <= 64 && nseq > 0 && nseq <= 64, "tce_mha_small64_seqs_f32: bad arguments");
-  TCE_CHECK_ARG(L > 0 && L <= 128, "tce_mha_small64_seqs_f32: sequence length %d outside 1..128", L);
+  TCE_CHECK_ARG(L > 0 && L <= MHA_SMALL_LMAX, "tce_mha_small64_seqs_f32: sequence length %d outside 1..512", L);
   TCE_CHECK_ARG(tce_aligned16(qkv_planes) && tce_aligned16(out) && (!bias || tce_aligned16(bias)),
                 "tce_mha_small64_seqs_f32: pointers must be 16-byte aligned");
-  hipLaunchKernelGGL((mha_small_kernel<64, 128>), dim3(nheads, tce_cdiv(L, 32), nseq), dim3(256), 0, (hipStream_t)stream, qkv_planes,
-                     out, L, nheads, scale, splits, bias, (const int*)nullptr);
+  mha_small64_launch(dim3(nheads, tce_cdiv(L, 32), nseq), (hipStream_t)stream, qkv_planes, out, L, nheads, scale, splits, bias, (const int*)nullptr);
   TCE_CHECK_LAUNCH("tce_mha_small64_seqs_f32");
   return TCE_OK;
 }
@@ -240,11 +328,10 @@ extern "C" int tce_mha_small64_lens_f32(const float* qkv_planes, int32_t splits,
                                         int32_t L, int32_t nheads, float scale, const int32_t* lens, tceStream stream) {
   TCE_CHECK_ARG(qkv_planes && out && lens && nheads > 0 && splits >= 1 && splits <= 64 && nseq > 0 && nseq <= 64,
                 "tce_mha_small64_lens_f32: bad arguments");
-  TCE_CHECK_ARG(L > 0 && L <= 128, "tce_mha_small64_lens_f32: sequence length %d outside 1..128", L);
+  TCE_CHECK_ARG(L > 0 && L <= MHA_SMALL_LMAX, "tce_mha_small64_lens_f32: sequence length %d outside 1..512", L);
   TCE_CHECK_ARG(tce_aligned16(qkv_planes) && tce_aligned16(out) && (!bias || tce_aligned16(bias)),
                 "tce_mha_small64_lens_f32: pointers must be 16-byte aligned");
-  hipLaunchKernelGGL((mha_small_kernel<64, 128>), dim3(nheads, tce_cdiv(L, 32), nseq), dim3(256), 0, (hipStream_t)stream, qkv_planes,
-                     out, L, nheads, scale, splits, bias, (const int*)lens);
+  mha_small64_launch(dim3(nheads, tce_cdiv(L, 32), nseq), (hipStream_t)stream, qkv_planes, out, L, nheads, scale, splits, bias, (const int*)lens);
   TCE_CHECK_LAUNCH("tce_mha_small64_lens_f32");
   return TCE_OK;
 }

@@ -648,13 +648,14 @@ class ReferFormer(nn.Module):
         select = int(targets[0]["valid_indices"]) if "valid_indices" in targets[0] else None
         if select is not None and not 0 <= select < vids.shape[1]:
             raise IndexError(f"valid_indices {select} outside the clip's {vids.shape[1]} frames")
+        ids, att, ids_host = self._tokenise(captions, vids.device)  # on the host: nothing is launched or copied here
+        self._check_caption_tokens(ids.shape[1])
         if not vids.is_cuda:
             raise RuntimeError("inputs must be on the GPU: this path has no CPU implementation")
         frames = vids[0].to(torch.float32).contiguous()
         valid = self._valid_region(samples, mask, frames)
         size = targets[0]["size"]
         img_h, img_w = float(size[0]), float(size[1])
-        ids, att, ids_host = self._tokenise(captions, frames.device)
         self._ensure_packed()
         ops.range_poll(frames.device)  # split-fp16 range guard: a tripped flag of an EARLIER forward raises here
         cached = self._text_lookup(ids, ids_host, frames.device)
@@ -677,7 +678,7 @@ class ReferFormer(nn.Module):
                         return self._text_plan().forward(st[1], alloc)
 
                     ent = self._capture(key, st, lambda res: self._run(st[0], text_fn, img_h, img_w, res, valid=valid, select=select),
-                                        frames, slot)
+                                        frames, slot, text=(1, ids.shape[1]))
                 if ent is None:  # the capture's arenas did not fit this shape's fallback kernels: eager from now on
                     out = self._run(frames, lambda alloc: self._text_plan().forward(ids, alloc), img_h, img_w, None, slot,
                                     valid=valid, select=select)
@@ -688,6 +689,17 @@ class ReferFormer(nn.Module):
 
     def _pad_id(self):
         return int(getattr(getattr(self.text_encoder, "config", None), "pad_token_id", 1) or 1)
+
+    def _check_caption_tokens(self, L):
+        """ValueError for a caption of L tokens (the width of a [G, L] id tensor) beyond what the text encoder takes: part of the
+        argument validation of every boundary, on the host and before any launch (text_encoder.max_caption_tokens)."""
+        from .text_encoder import caption_too_long, max_caption_tokens
+        emb = getattr(getattr(self.text_encoder, "embeddings", None), "position_embeddings", None)
+        if emb is None:  # a text encoder that is not HuggingFace's RobertaModel: TextPlan refuses it on its own terms
+            return
+        limit = max_caption_tokens(emb.weight.shape[0], self._pad_id())
+        if int(L) > limit:
+            raise ValueError(caption_too_long(int(L), limit))
 
     def _group_text(self, ids, ragged):
         """The text callable of a clip group's launch program.  Ragged: the captions' lengths, key padding mask and position table
@@ -750,16 +762,20 @@ class ReferFormer(nn.Module):
             if ragged and torch.is_tensor(cap):  # one caption: no padding needed (its length on the host: one read-back)
                 cap = cap[:, :caption_lengths(cap.cpu(), self._pad_id())[0]]
             return [self.forward([clips[0]], cap, targets[:1], slot=slot)]
-        shp = tuple(clips[0].shape)
-        if any(tuple(c.shape) != shp or not c.is_cuda for c in clips) or len(shp) != 4:
-            raise ValueError("clip groups: G CUDA tensors [T,3,H,W] of one shape")
+        # the captions first (tokenised on the host): one beyond the text encoder's limit is refused before anything else is looked at
         if isinstance(captions, (list, tuple)):
             rows = [self._tokenise([c], clips[0].device)[0] for c in captions]
+            self._check_caption_tokens(max(int(r.shape[1]) for r in rows))
             if len({int(r.shape[1]) for r in rows}) != 1:
                 raise ValueError("clip groups: the captions must tokenise to one length")
             ids = torch.cat(rows, 0)
         else:
             ids = captions
+            if ids.dim() == 2:
+                self._check_caption_tokens(ids.shape[1])
+        shp = tuple(clips[0].shape)
+        if any(tuple(c.shape) != shp or not c.is_cuda for c in clips) or len(shp) != 4:
+            raise ValueError("clip groups: G CUDA tensors [T,3,H,W] of one shape")
         if ids.dim() != 2 or ids.shape[0] != G or G > 64:
             raise ValueError("clip groups: token ids [G, L], G <= 64")
         size = targets[0]["size"]
@@ -806,7 +822,7 @@ class ReferFormer(nn.Module):
                 text_fn = self._group_text(st[1], ragged)
                 like = types.SimpleNamespace(shape=(G * Tc,) + shp[1:], device=dev)  # arenas are sized for the whole group
                 ent = self._capture(key, st, lambda res: self._run(st[0], text_fn, img_h, img_w, res, groups=G, shared=shared, select=sel),
-                                    like, slot)
+                                    like, slot, text=(G, ids.shape[1]))
             if ent is None:
                 out = eager()
             else:  # the clips go straight into their slices of the graph's static frame buffer (one copy launch)
@@ -860,13 +876,19 @@ class ReferFormer(nn.Module):
         if (len(captions) if isinstance(captions, (list, tuple)) else int(captions.shape[0])) != G:
             raise ValueError(f"indexed groups: {G} index tuples but "
                              f"{len(captions) if isinstance(captions, (list, tuple)) else int(captions.shape[0])} captions")
+        dev = pool.device
+        rows = None
+        if isinstance(captions, (list, tuple)):  # tokenised on the host: a caption beyond the text encoder's limit is an argument error
+            rows = [self._tokenise([c], dev)[0] for c in captions]
+            self._check_caption_tokens(max(int(r.shape[1]) for r in rows))
+        elif captions.dim() == 2:
+            self._check_caption_tokens(captions.shape[1])
         if not pool.is_cuda:
             raise RuntimeError("inputs must be on the GPU: this path has no CPU implementation")
-        dev = pool.device
         if ragged:
             pad_id = self._pad_id()
-            if isinstance(captions, (list, tuple)):
-                captions, _ = pad_captions([self._tokenise([c], dev)[0] for c in captions], pad_id)
+            if rows is not None:
+                captions, _ = pad_captions(rows, pad_id)
             elif not captions.is_cuda:
                 caption_lengths(captions, pad_id)  # validation only: the device derives the lengths itself
         if G == 1:
@@ -875,7 +897,6 @@ class ReferFormer(nn.Module):
                 cap = cap[:, :caption_lengths(cap.cpu(), self._pad_id())[0]]
             return [self.forward([pool[list(index[0])]], cap, targets[:1], slot=slot)]
         if isinstance(captions, (list, tuple)):
-            rows = [self._tokenise([c], dev)[0] for c in captions]
             if len({int(r.shape[1]) for r in rows}) != 1:
                 raise ValueError("indexed groups: the captions must tokenise to one length (or ragged=True)")
             ids = torch.cat(rows, 0)
@@ -925,7 +946,8 @@ class ReferFormer(nn.Module):
                 st = (frames_now().clone() if whole else frames_now(), ids.clone())
                 text_fn = self._group_text(st[1], ragged)
                 like = types.SimpleNamespace(shape=(G * Tc,) + shp[1:], device=dev, gather=True)
-                ent = self._capture(key, st, lambda res: self._run(st[0], text_fn, img_h, img_w, res, groups=G, index=index), like, slot)
+                ent = self._capture(key, st, lambda res: self._run(st[0], text_fn, img_h, img_w, res, groups=G, index=index), like, slot,
+                                    text=(G, ids.shape[1]))
             if ent is None:
                 out = eager()
             else:  # the pool's runs go straight into their rows of the graph's static frame buffer (one copy launch)
@@ -1098,7 +1120,19 @@ class ReferFormer(nn.Module):
                         fork2=(arena2, stream2) if os.environ.get("TCE_FORK2", "1") != "0" else None,
                         fork3=((arena3, stream3), (arena4, stream4)) if os.environ.get("TCE_FORK3", "1") != "0" else None)
 
-    def _branch_resources(self, like, slot=0):
+    def _text_arena_extra(self, text):
+        """Bytes the text branch of text = (G captions, L tokens each) needs in its arena beyond the flat allowance of
+        _branch_resources, which was sized for captions of up to 128 tokens: 0 up to there (those shapes keep the arenas they had).
+        Per token row: RoBERTa's activations (x, packed qkv, attention output, the MLP's hidden row and one GEMM workspace row of
+        that width) and the 256-wide rows after the resizer (its two maps, keys and values of the five cross-attention sites, a
+        ragged group's position table), rounded up."""
+        if text is None or int(text[1]) <= 128:
+            return 0
+        tc = getattr(self.text_encoder, "config", None)
+        C, ff = int(getattr(tc, "hidden_size", 768)), int(getattr(tc, "intermediate_size", 3072))
+        return int(text[0]) * int(text[1]) * 4 * (5 * C + ff + max(ff, 3 * C) + 16 * self.cfg.hidden_dim) + (8 << 20)
+
+    def _branch_resources(self, like, slot=0, text=None):
         """(arena, side arena, side stream, arena2, stream2, arena3, stream3, arena4, stream4) of one capture: the main arena
         and one arena per parallel branch that allocates; the side streams are the (device, slot)'s shared set.  like.gather (an
         indexed group): T frames' maps are gathered from the backbone's -- room for each in the arena of the branch that consumes it
@@ -1108,7 +1142,7 @@ class ReferFormer(nn.Module):
         st = _side_streams(like.device, slot)
         gb = self._gather_bytes(T, H0, W0) if getattr(like, "gather", False) else [0, 0, 0, 0]
         return (ops.Arena(like.device, self._arena_bytes(T, H0, W0) + sum(gb)),
-                ops.Arena(like.device, T * self._tokens_per_frame(H0, W0) * 256 * 4 * 4 + (32 << 20)),
+                ops.Arena(like.device, T * self._tokens_per_frame(H0, W0) * 256 * 4 * 4 + (32 << 20) + self._text_arena_extra(text)),
                 st[0],
                 # third branch: the pixel decoder's stride-4 lateral path (tgt + its self-attention / FFN temporaries)
                 ops.Arena(like.device, int(tok0 * 4 * (2048 * 1.1 + 256 * 4)) + (64 << 20) + gb[0]),
@@ -1150,7 +1184,7 @@ class ReferFormer(nn.Module):
             like = types.SimpleNamespace(shape=(groups * len(index[0]), 3, H0, W0), device=frames.device, gather=True)
         else:
             like = types.SimpleNamespace(shape=(T * (groups if shared else 1), 3, H0, W0), device=frames.device)
-        res = self._branch_resources(like, slot)
+        res = self._branch_resources(like, slot, text=(groups, ids.shape[1]))
         st = (frames.clone(), ids.to(frames.device).clone())
         if select is not None:
             select = int(select) if groups == 1 and not isinstance(select, (tuple, list)) else tuple(int(v) for v in select)
@@ -1174,11 +1208,12 @@ class ReferFormer(nn.Module):
         torch.cuda.current_stream().wait_stream(main)
         return rec.analyse()
 
-    def _capture(self, key, statics, fn, like, slot=0):
+    def _capture(self, key, statics, fn, like, slot=0, text=None):
         """Captures fn((arena, side_arena, side_stream, ...)) into a graph; the arenas belong to the graph (their
         addresses are baked into it), the side streams are the (device, slot)'s shared set.  Returns None (and pins the
-        key to the eager path) if a branch arena turns out too small for this shape's kernels."""
-        res = self._branch_resources(like, slot)
+        key to the eager path) if a branch arena turns out too small for this shape's kernels.  text: (captions, tokens each) of
+        the program's text branch (_text_arena_extra)."""
+        res = self._branch_resources(like, slot, text=text)
         try:
             fn(res)  # eager warm-up on the same resources: builds per-shape constants, lazy inits
         except MemoryError as e:
@@ -1286,7 +1321,7 @@ class ReferFormer(nn.Module):
         if ent is None:
             st = (frames.clone(), text_hidden.clone(), text_pooled.clone())
             ent = self._capture(key, st, lambda res: self._run(st[0], (st[1], st[2]), img_h, img_w, res, valid=valid_hw, select=select),
-                                frames, slot)
+                                frames, slot, text=(1, text_hidden.shape[0]))
             if ent is None:
                 return self._tag_diagnostics(self._run(frames, (text_hidden, text_pooled), img_h, img_w, None, slot, valid=valid_hw,
                                                        select=select))
@@ -1327,7 +1362,7 @@ class ReferFormer(nn.Module):
                 st = (frames.clone(), text_hidden.clone(), text_pooled.clone())
                 like = types.SimpleNamespace(shape=(G * Tc,) + tuple(frames.shape[1:]), device=frames.device)
                 ent = self._capture(key, st, lambda res: self._run(st[0], (st[1], st[2]), img_h, img_w, res, groups=G, shared=shared,
-                                                                   select=sel), like, slot)
+                                                                   select=sel), like, slot, text=(G, text_hidden.shape[0] // G))
             out = eager() if ent is None else self._replay(key, ent, (frames, text_hidden, text_pooled))
         return self._split_group(out, G, Tc if sel is None else 1)
 

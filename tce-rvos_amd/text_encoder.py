@@ -13,6 +13,20 @@ from ._lib import check, lib
 from .ops import ACT_GELU, RES_ADD, gemm_ex
 
 
+MHA_MAX_TOKENS = 512  # tce_mha_small64_*: whole sentence in LDS up to 128 tokens, key tiles up to here (csrc/text.hip)
+
+
+def max_caption_tokens(position_rows, pad_id):
+    """Tokens a caption may have: position ids run from pad_id + 1 to pad_id + L (HF create_position_ids_from_input_ids) and must
+    stay inside the position table (514 rows and pad id 1 for RoBERTa: 512), and the self-attention kernels take up to 512."""
+    return min(int(position_rows) - int(pad_id) - 1, MHA_MAX_TOKENS)
+
+
+def caption_too_long(L, limit):
+    return (f"caption of {L} tokens: the text encoder takes at most {limit} (its position table and the self-attention kernels "
+            f"end there; the reference fails on such a caption too, with an index error in the position embedding)")
+
+
 class TextPlan:
     def __init__(self, hf_model):
         cfg = hf_model.config
@@ -47,6 +61,11 @@ class TextPlan:
         sd, C = self.sd, self.C
         G, Ls = int(ids.shape[0]), int(ids.shape[1])
         L = G * Ls  # rows of every activation below
+        # position ids run up to pad + Ls and the embedding kernel indexes the table with no bound of its own (the table's row
+        # count is not in its signature): a caption beyond the table is refused here, before that launch
+        limit = max_caption_tokens(int(sd["embeddings.position_embeddings.weight"].shape[0]), self.pad)
+        if Ls > limit:
+            raise ValueError(caption_too_long(Ls, limit))
         s = ops._stream()
         xbuf = A(L + G, C)  # rows L.. receive the pooler outputs
         x = xbuf[:L]
@@ -82,7 +101,8 @@ class TextPlan:
                 ops.splitk_reduce(ws_b, t_f2, L, C, x, bias=sd[p + "output.dense.bias"], res=x, ldres=C, res_mode=RES_ADD,
                                   ln=(sd[p + "output.LayerNorm.weight"], sd[p + "output.LayerNorm.bias"]), eps=self.eps)
             return self._pooler(x, xbuf, G, Ls, s)
-        # (more than 128 rows -- a large clip group -- or the exact-fp32 arithmetic: tiled GEMMs; attention per caption as above)
+        # (more than 128 rows -- a large clip group, or a caption of 129..512 tokens, whose attention launches walk key tiles -- or
+        # the exact-fp32 arithmetic: tiled GEMMs; attention per caption as above)
         ws = A(max(sk_qkv * L * 3 * C, sk_out * L * C, sk_f1 * L * self.ff, sk_f2 * L * C))
         for wqkv, bqkv, p in self.layers:
             gemm_ex(x, wqkv, qkv, L, 3 * C, C, C, C, 3 * C, bias=bqkv, splitk=sk_qkv, ws=ws)
