@@ -226,6 +226,20 @@ PNG_SIGNATURES = {
 HEADERS = {"tce_rvos.h": SIGNATURES, "tce_rvos_debug.h": DEBUG_SIGNATURES, "tce_rvos_video.h": VIDEO_SIGNATURES,
            "tce_rvos_eval.h": EVAL_SIGNATURES, "tce_rvos_score.h": SCORE_SIGNATURES, "tce_rvos_png.h": PNG_SIGNATURES}
 
+# csrc/tce_rvos_vis.h: visualisation-stage entry points (the --visualize images drawn on the device and their RGB PNG streams).  The
+# stage's header lives beside the sources and its table here, outside HEADERS: the headers of include/ are a closed set.
+VIS_SIGNATURES = {
+    # frames [N,H0,W0,3] u8, out, masks [L,N,H0,W0] u8 | NULL, boxes [L,N,4] | NULL, points [L,N,2] | NULL, colors [L,3] u8, L, N, H0, W0
+    "tce_vis_overlay_u8": (i32, [c_f, c_f, c_f, c_f, c_f, c_f, i32, i32, i32, i32, c_f]),
+    # img [P,H,W,3] u8, rows [P,H,1+3W] u8, P, H, W
+    "tce_png_filter_rgb_u8": (i32, [c_f, c_f, i32, i32, i32, c_f]),
+    # rows [P,H,R] u8, streams [P,bound] u8, nbytes [P] i32, ws, P, H, R, rows_per_strip
+    "tce_png_deflate_rows_u8": (i32, [c_f, c_f, c_f, c_f, i32, i32, i32, i32, c_f]),
+}
+
+# header (relative to the package's csrc/) -> its table: EVERY symbol of its header and no other, as HEADERS (tests check this)
+STAGE_HEADERS = {"tce_rvos_vis.h": VIS_SIGNATURES}
+
 _LIB = None
 
 
@@ -246,7 +260,7 @@ def lib():
             warnings.warn(f"tce_rvos_amd: GPU_MAX_HW_QUEUES={hwq} is set; the HIP runtime's default (4) is the only value this "
                           f"launch program runs well with (1-3 crash the runtime, 5-16 double the clip time)", RuntimeWarning)
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in [kv for table in HEADERS.values() for kv in table.items()]:
+        for name, (res, args) in [kv for table in list(HEADERS.values()) + list(STAGE_HEADERS.values()) for kv in table.items()]:
             fn = getattr(l, name)  # AttributeError if the symbol is absent
             fn.restype, fn.argtypes = res, args
         _LIB = l

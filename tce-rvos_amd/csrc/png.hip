@@ -1,8 +1,10 @@
 // PNG-writing stage kernels (csrc/tce_rvos_png.h, csrc/tce_rvos_png_dyn.h): the zlib stream of every uint8 output plane -- filter
 // bytes, RLE-only deflate with the fixed Huffman code or, behind the second entry, with the cheaper of the fixed code and a code of
 // the strip's own, Adler-32 -- in three launches.  Byte and bit kernels: bound by LDS traffic and barriers, not by arithmetic.
+// RGB images (at the end of the file): a row filter chosen per row, then the second encoding over rows that are filtered already.
 #include "common.h"
 #include "../../include/tce_rvos_png.h"
+#include "tce_rvos_vis.h"
 
 namespace {
 
@@ -540,7 +542,9 @@ __device__ __forceinline__ void dyn_long_run(DynShared& S, uint32_t* __restrict_
 
 // One walk of the strip's n filtered bytes, png_strip_kernel's: EMIT = false counts every token into S.cnt / S.extra / S.matches
 // (integer LDS atomics: the sums do not depend on their order), EMIT = true writes them through S.tab and sums the Adler pair.
-template <bool EMIT>
+// The byte source has two forms.  ROWS = false: pl is the strip's plane bytes, W1 - 1 a row; a row's filtered bytes are a zero and
+// its mapped plane bytes.  ROWS = true (tce_png_deflate_rows_u8): pl is the strip's filtered bytes themselves, W1 a row, ns = n.
+template <bool EMIT, bool ROWS>
 __device__ __forceinline__ void dyn_walk(DynShared& S, const uint8_t* __restrict__ pl, const int n, const int ns, const int W1, const int nonzero,
                                          uint32_t* __restrict__ out, long long& flushed, int& wb, unsigned long long& sa, unsigned long long& sb) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -565,7 +569,7 @@ __device__ __forceinline__ void dyn_walk(DynShared& S, const uint8_t* __restrict
   for (int f0 = 0; f0 < n; f0 += TCE_PNG_PASS) {
     const int len = min(TCE_PNG_PASS, n - f0);
     const int r0 = f0 / W1, c0 = f0 - r0 * W1, fe = f0 + len - 1, re = fe / W1;
-    const int q0 = f0 - r0 - (c0 ? 1 : 0), q1 = fe - re;
+    const int q0 = ROWS ? f0 : f0 - r0 - (c0 ? 1 : 0), q1 = ROWS ? fe + 1 : fe - re;
     const int lead = (int)((reinterpret_cast<uintptr_t>(pl) + (uintptr_t)q0) & 3u);
     for (int j = tid; 4 * j < lead + (q1 - q0); j += PT) S.raw[j] = strip_dword(pl, q0 - lead + 4 * j, ns);
     __syncthreads();
@@ -577,6 +581,7 @@ __device__ __forceinline__ void dyn_walk(DynShared& S, const uint8_t* __restrict
     if (f < f0 + len) {
       int r = f / W1, c = f - r * W1;
       auto fbyte = [&](const int ff, const int rr, const int cc) -> uint32_t {
+        if (ROWS) return rawb[lead + (ff - q0)];
         if (cc == 0) return 0u;
         const uint32_t x = rawb[lead + (ff - rr - 1 - q0)];
         return nonzero ? (x ? (uint32_t)nonzero : 0u) : x;
@@ -881,7 +886,9 @@ __device__ __forceinline__ void dyn_build(DynShared& S) {
   __syncthreads();
 }
 
-// First launch of the dynamic encoding, in png_strip_kernel's place: the same workspace layout, the same meta words.
+// First launch of the dynamic encoding, in png_strip_kernel's place: the same workspace layout, the same meta words.  ROWS = true:
+// `planes` is rows [P,H,W+1], the filtered bytes as they are (dyn_walk).
+template <bool ROWS>
 __global__ void __launch_bounds__(PT) png_strip_dyn_kernel(const uint8_t* __restrict__ planes, uint32_t* __restrict__ ws, const int H, const int W,
                                                            const int S_rows, const int nstrips, const long long stride_dw, const int nonzero) {
   __shared__ DynShared S;
@@ -889,8 +896,8 @@ __global__ void __launch_bounds__(PT) png_strip_dyn_kernel(const uint8_t* __rest
   const int strip = blockIdx.x, p = blockIdx.y;
   const long long sidx = (long long)p * nstrips + strip, nstr = (long long)gridDim.y * nstrips;
   const int row0 = strip * S_rows, rows = min(S_rows, H - row0), W1 = W + 1;
-  const int n = rows * W1, ns = rows * W;
-  const uint8_t* __restrict__ pl = planes + ((long long)p * H + row0) * W;
+  const int n = rows * W1, ns = ROWS ? n : rows * W;
+  const uint8_t* __restrict__ pl = planes + ((long long)p * H + row0) * (ROWS ? W1 : W);
   uint32_t* __restrict__ out = ws + nstr * 3 + sidx * stride_dw;
 
   for (int i = tid; i < DWIN_DW; i += PT) S.win[i] = 0u;
@@ -900,12 +907,12 @@ __global__ void __launch_bounds__(PT) png_strip_dyn_kernel(const uint8_t* __rest
   int wb = 0;
   long long flushed = 0;
   unsigned long long sa = 0ull, sb = 0ull;
-  dyn_walk<false>(S, pl, n, ns, W1, nonzero, out, flushed, wb, sa, sb);
+  dyn_walk<false, ROWS>(S, pl, n, ns, W1, nonzero, out, flushed, wb, sa, sb);
   __syncthreads();
   dyn_build(S);
   wb = S.hbits;
   flush(S.win, out, flushed, wb);
-  dyn_walk<true>(S, pl, n, ns, W1, nonzero, out, flushed, wb, sa, sb);
+  dyn_walk<true, ROWS>(S, pl, n, ns, W1, nonzero, out, flushed, wb, sa, sb);
 
   // end of block, a stored-block header, zero bits to the byte boundary, 00 00 FF FF
   const Tok eob = sym_tok(S.tab, 0, Sym{256, 0u, 0});
@@ -999,12 +1006,155 @@ extern "C" int tce_png_deflate_dyn_u8(const uint8_t* planes, uint8_t* streams, i
   TCE_CHECK_ARG(((uintptr_t)ws & 7u) == 0 && ((uintptr_t)nbytes & 3u) == 0,
                 "tce_png_deflate_dyn_u8: ws must be 8-byte aligned, nbytes 4-byte aligned");
   const int S = rows_per_strip < H ? rows_per_strip : H;
-  hipLaunchKernelGGL(png_strip_dyn_kernel, dim3(pl.nstrips, P), dim3(PT), 0, (hipStream_t)stream, planes, (uint32_t*)ws, H, W, S, pl.nstrips,
+  hipLaunchKernelGGL(png_strip_dyn_kernel<false>, dim3(pl.nstrips, P), dim3(PT), 0, (hipStream_t)stream, planes, (uint32_t*)ws, H, W, S, pl.nstrips,
                      pl.stride_dw, nonzero_value);
   hipLaunchKernelGGL(png_plane_kernel, dim3(P), dim3(PT), 0, (hipStream_t)stream, (uint32_t*)ws, streams, nbytes, H, W, S, pl.nstrips,
                      pl.bound);
   hipLaunchKernelGGL(png_copy_kernel, dim3(pl.nstrips, P), dim3(PT), 0, (hipStream_t)stream, (const uint32_t*)ws, streams, pl.nstrips,
                      pl.stride_dw, pl.bound);
   TCE_CHECK_LAUNCH("tce_png_deflate_dyn_u8");
+  return TCE_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ RGB images (csrc/tce_rvos_vis.h)
+namespace {
+
+constexpr int FCH = 4096;  // filtered bytes of a row staged at a time, with the 3 bytes in front of them
+
+__device__ __forceinline__ int paeth(const int a, const int b, const int c) {
+  const int p = a + b - c, pa = abs(p - a), pb = abs(p - b), pc = abs(p - c);
+  return (pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c);
+}
+
+// byte i of the row filtered with type t: cs / us hold bytes i0-3 .. of the row and of the row above
+__device__ __forceinline__ uint32_t filt_byte(const uint8_t* cs, const uint8_t* us, const int k, const int i, const bool top, const int t) {
+  const int x = cs[k + 3], a = i >= 3 ? cs[k] : 0, b = top ? 0 : us[k + 3], c = (top || i < 3) ? 0 : us[k];
+  const int pred = t == 0 ? 0 : t == 1 ? a : t == 2 ? b : t == 3 ? ((a + b) >> 1) : paeth(a, b, c);
+  return (uint32_t)(x - pred) & 255u;
+}
+
+// A workgroup per image row.  Pass 1: the five sums of |filtered byte as int8| over the row, in chunks staged in LDS (whole dwords
+// of the image wherever four bytes are one aligned word), one reduction, the choice.  Pass 2: the chosen row, a thread per
+// aligned dword of rows.
+__global__ void __launch_bounds__(PT) png_filter_rgb_kernel(const uint8_t* __restrict__ img, uint8_t* __restrict__ rows, const int H, const int W) {
+  __shared__ uint32_t craw[FCH / 4 + 4], uraw[FCH / 4 + 4];
+  __shared__ uint32_t part[5][PWAVES];
+  __shared__ int chosen;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int y = blockIdx.x, p = blockIdx.y, n = 3 * W, ns = H * n;
+  const bool top = y == 0;
+  const uint8_t* __restrict__ im = img + (long long)p * ns;
+  uint8_t* __restrict__ dst = rows + ((long long)p * H + y) * (n + 1);
+  const uint8_t* cs = reinterpret_cast<const uint8_t*>(craw);
+  const uint8_t* us = reinterpret_cast<const uint8_t*>(uraw);
+  int clead = 0, ulead = 0;
+  auto stage = [&](const int i0, const int len) {  // bytes i0-3 .. i0+len-1 of the row and of the row above; outside the image: 0
+    const int s = y * n + i0 - 3, u = s - n;
+    clead = (int)((reinterpret_cast<uintptr_t>(im) + (uintptr_t)(intptr_t)s) & 3u);
+    ulead = (int)((reinterpret_cast<uintptr_t>(im) + (uintptr_t)(intptr_t)u) & 3u);
+    for (int j = tid; 4 * j < clead + len + 3; j += PT) craw[j] = strip_dword(im, s - clead + 4 * j, ns);
+    if (!top)
+      for (int j = tid; 4 * j < ulead + len + 3; j += PT) uraw[j] = strip_dword(im, u - ulead + 4 * j, ns);
+    __syncthreads();
+  };
+
+  uint32_t sum[5] = {0u, 0u, 0u, 0u, 0u};  // a wave's share: at most 128 * 3W / 4 < 2^32 (W <= 2^24)
+  for (int i0 = 0; i0 < n; i0 += FCH) {
+    const int len = min(FCH, n - i0);
+    stage(i0, len);
+    for (int k = tid; k < len; k += PT) {
+#pragma unroll
+      for (int t = 0; t < 5; ++t) {
+        const int f = (int)(int8_t)filt_byte(cs + clead, us + ulead, k, i0 + k, top, t);
+        sum[t] += (uint32_t)abs(f);
+      }
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int t = 0; t < 5; ++t) {
+    uint32_t v = sum[t];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o, 64);
+    if (lane == 0) part[t][wave] = v;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    int best = 0;
+    unsigned long long bs = ~0ull;
+    for (int t = 0; t < 5; ++t) {
+      unsigned long long v = 0ull;
+      for (int k = 0; k < PWAVES; ++k) v += part[t][k];
+      if (v < bs) {  // a tie goes to the lowest type
+        bs = v;
+        best = t;
+      }
+    }
+    chosen = best;
+  }
+  __syncthreads();
+  const int t = chosen;
+
+  for (int i0 = 0; i0 < n; i0 += FCH) {
+    const int len = min(FCH, n - i0);
+    stage(i0, len);
+    // bytes k_lo .. k_hi-1 of the output row: byte 0 is the type, byte k the filtered byte k - 1
+    const int k_lo = i0 ? i0 + 1 : 0, k_hi = i0 + len + 1;
+    const int shift = (int)(reinterpret_cast<uintptr_t>(dst + k_lo) & 3u);
+    for (int g = tid; 4 * g - shift < k_hi - k_lo; g += PT) {
+      const int kk = k_lo + 4 * g - shift;
+      uint32_t d = 0u;
+      bool whole = true;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int k = kk + q;
+        if (k >= k_lo && k < k_hi) {
+          const uint32_t b = k == 0 ? (uint32_t)t : filt_byte(cs + clead, us + ulead, k - 1 - i0, k - 1, top, t);
+          d |= b << (8 * q);
+        } else {
+          whole = false;
+        }
+      }
+      if (whole) {
+        *reinterpret_cast<uint32_t*>(dst + kk) = d;
+      } else {
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          if (kk + q >= k_lo && kk + q < k_hi) dst[kk + q] = (uint8_t)(d >> (8 * q));
+      }
+    }
+    __syncthreads();
+  }
+}
+
+}  // namespace
+
+extern "C" int tce_png_filter_rgb_u8(const uint8_t* img, uint8_t* rows, int32_t P, int32_t H, int32_t W, tceStream stream) {
+  TCE_CHECK_ARG(P > 0 && H > 0 && W > 0, "tce_png_filter_rgb_u8: non-positive extent");
+  TCE_CHECK_ARG(P <= 65535 && W <= (1 << 24) && (long long)H * (3ll * W + 1) < (1ll << 31) - 4096,
+                "tce_png_filter_rgb_u8: an image's rows must stay below 2^31 - 4096 bytes, W at or below 2^24 and P at or below 65535");
+  TCE_CHECK_ARG(img && rows, "tce_png_filter_rgb_u8: null pointer");
+  hipLaunchKernelGGL(png_filter_rgb_kernel, dim3(H, P), dim3(PT), 0, (hipStream_t)stream, img, rows, H, W);
+  TCE_CHECK_LAUNCH("tce_png_filter_rgb_u8");
+  return TCE_OK;
+}
+
+extern "C" int tce_png_deflate_rows_u8(const uint8_t* rows, uint8_t* streams, int32_t* nbytes, void* ws, int32_t P, int32_t H, int32_t R,
+                                       int32_t rows_per_strip, tceStream stream) {
+  PngPlan pl;
+  TCE_CHECK_ARG(P > 0 && H > 0 && R > 1 && rows_per_strip > 0, "tce_png_deflate_rows_u8: non-positive extent (R must be at least 2)");
+  TCE_CHECK_ARG(P <= 65535 && png_plan(H, R - 1, rows_per_strip, &pl),
+                "tce_png_deflate_rows_u8: H * (R - 1) must stay below 2^31, the stream bound below 2^31 - 4096 bytes, the strips at or below 2^22 and P at or below 65535");
+  TCE_CHECK_ARG(rows && streams && nbytes && ws, "tce_png_deflate_rows_u8: null pointer");
+  TCE_CHECK_ARG(((uintptr_t)ws & 7u) == 0 && ((uintptr_t)nbytes & 3u) == 0,
+                "tce_png_deflate_rows_u8: ws must be 8-byte aligned, nbytes 4-byte aligned");
+  const int S = rows_per_strip < H ? rows_per_strip : H;
+  hipLaunchKernelGGL(png_strip_dyn_kernel<true>, dim3(pl.nstrips, P), dim3(PT), 0, (hipStream_t)stream, rows, (uint32_t*)ws, H, R - 1, S,
+                     pl.nstrips, pl.stride_dw, 0);
+  hipLaunchKernelGGL(png_plane_kernel, dim3(P), dim3(PT), 0, (hipStream_t)stream, (uint32_t*)ws, streams, nbytes, H, R - 1, S, pl.nstrips,
+                     pl.bound);
+  hipLaunchKernelGGL(png_copy_kernel, dim3(pl.nstrips, P), dim3(PT), 0, (hipStream_t)stream, (const uint32_t*)ws, streams, pl.nstrips,
+                     pl.stride_dw, pl.bound);
+  TCE_CHECK_LAUNCH("tce_png_deflate_rows_u8");
   return TCE_OK;
 }

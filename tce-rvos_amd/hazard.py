@@ -9,7 +9,8 @@ checks it statically.
 
   * every C-ABI launch (`lib().tce_*`) is intercepted: the stream it was issued on and -- from the same pointers and sizes
     the kernel receives -- the byte ranges it reads and writes (`MODELS`: one access model for every launching entry point
-    of every header of include/ (_lib.HEADERS), the drivers' output stages included; an entry point that is neither modelled
+    of every header of include/ (_lib.HEADERS), the drivers' output stages included, `STAGE_MODELS` for the stage headers beside
+    the sources (_lib.STAGE_HEADERS); an entry point that is neither modelled
     nor listed in `NOT_LAUNCHES` is an error, so coverage cannot rot);
   * every event record / wait (torch's `wait_stream` is `wait_event(record_event())`) and every host synchronisation is
     intercepted and turned into vector clocks: launch A happens-before launch B iff B's clock has seen A's tick;
@@ -388,6 +389,27 @@ def _png_deflate(a):
     return [dense(_p(planes), P * H * W), wsb], [dense(_p(streams), P * L.tce_png_stream_bound(H, W, S)), dense(_p(nbytes), P * 4), wsb]
 
 
+def _png_filter_rgb(a):
+    """img, rows, P, H, W: every image byte is read, every byte of rows written"""
+    img, rows, P, H, W = a[:5]
+    return [dense(_p(img), P * H * W * 3)], [dense(_p(rows), P * H * (3 * W + 1))]
+
+
+def _png_deflate_rows(a):
+    """rows, streams, nbytes, ws, P, H, R, rows_per_strip: _png_deflate's ranges for planes of R - 1 columns, the rows read whole"""
+    rows, streams, nbytes, ws, P, H, R, S = a[:8]
+    L = _lib.lib_raw()
+    wsb = dense(_p(ws), L.tce_png_ws_bytes(P, H, R - 1, S))
+    return [dense(_p(rows), P * H * R), wsb], [dense(_p(streams), P * L.tce_png_stream_bound(H, R - 1, S)), dense(_p(nbytes), P * 4), wsb]
+
+
+def _vis_overlay(a):
+    """frames, out, masks, boxes, points, colors, L, N, H0, W0: the optional inputs only where given (dense of a NULL is empty)"""
+    frames, out, masks, boxes, points, colors, L, N, H0, W0 = a[:10]
+    return ([dense(_p(frames), N * H0 * W0 * 3), dense(_p(masks), L * N * H0 * W0), dense(_p(boxes), L * N * 4 * F),
+             dense(_p(points), L * N * 2 * F), dense(_p(colors), L * 3)], [dense(_p(out), N * H0 * W0 * 3)])
+
+
 def _a2d_group_masks(a):
     """samples (host table), B, N, h, w: per sample what _a2d_masks names, plus its N logits (logit_stride floats apart) and scores"""
     samples, B, N, h, w = a[:5]
@@ -551,6 +573,13 @@ MODELS = {
     "tce_a2d_group_masks_u8": _a2d_group_masks,
 }
 
+# The launching entry points of the stage headers beside the sources (_lib.STAGE_HEADERS): one model each, as MODELS for include/.
+STAGE_MODELS = {
+    "tce_vis_overlay_u8": _vis_overlay,
+    "tce_png_filter_rgb_u8": _png_filter_rgb,
+    "tce_png_deflate_rows_u8": _png_deflate_rows,
+}
+
 
 # Entry points that launch nothing (queries, process switches, graph helpers, tuning aids): passed through.
 NOT_LAUNCHES = {"tce_abi_version", "tce_last_error", "tce_gemm_select_tile", "tce_gemm_select_tile_ex", "tce_set_gemm_mode", "tce_set_gemm_mode_thread",
@@ -698,7 +727,7 @@ class _LibProxy:
         fn = getattr(self._real, name)
         if name in NOT_LAUNCHES or not name.startswith("tce_"):
             return fn
-        model = MODELS.get(name)
+        model = MODELS.get(name) or STAGE_MODELS.get(name)
         if model is None:
             raise RuntimeError(f"hazard checker: no access model for {name} (add one to hazard.MODELS)")
         rec, dry = self._rec, self._dry

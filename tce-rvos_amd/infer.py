@@ -11,6 +11,8 @@
   run_video_windows / run_video_objects): every mask is what a sequential loop over the same calls produces, bit for bit.
 * The PNG streams are made on the device (png.mask_pngs / label_pngs); writer threads create the directories and write the files
   while the next video runs.
+* overlays= additionally writes the drivers' --visualize images (vis.overlay_expression / overlay_objects on the raw frames that
+  are on the device already, png.rgb_pngs), through the same writer threads.
 
 No kernel is added here: the module is host orchestration over launches that exist.  Threads only, never processes; no pool size
 is read from the machine.
@@ -29,7 +31,7 @@ import numpy as np
 import torch
 from PIL import Image
 
-from . import dist, png, video
+from . import dist, png, video, vis
 
 MAX_WORKERS = 16
 STAGES = ("decode", "upload_wait", "forward", "encode", "write")
@@ -342,16 +344,17 @@ class _Uploader:
         return dev, copied
 
     def consumed(self, v):
-        """the front-end calls that read buffer v % 2 have been issued on the compute stream"""
+        """every call that reads buffer v % 2 -- the front-end, and with overlays on the video's overlay launches -- has been issued
+        on the compute stream"""
         self.free[v % 2] = torch.cuda.Event()
         self.free[v % 2].record(self.compute)
 
 
-def _default_run(mode, kw):
+def _default_run(mode, kw, ref_points=False):
     def run(model, frames, job, origin_hw):
         captions = list(job.expressions.values())
-        if mode == "video":
-            return video.run_video_expressions(model, frames, captions, origin_hw, **kw)
+        if mode == "video":  # (ref_points: the overlays' cross; the windows driver returns the points anyway)
+            return video.run_video_expressions(model, frames, captions, origin_hw, **({"ref_points": True, **kw} if ref_points else kw))
         if mode == "windows":
             return video.run_video_windows(model, frames, captions, origin_hw, **kw)
         k = dict(kw)
@@ -371,8 +374,32 @@ def _paths(mode, out_dir, job, n_results, n_frames):
     return [[os.path.join(out_dir, job.name, str(e), str(f) + ".png") for f in job.frame_names] for e in exp_ids]  # inference_ytvos.py:355-363
 
 
+def _check_overlays(overlays):
+    """overlays= of run_split -> (dir, colors uint8 [K,3] on the host, rows_per_strip or None)"""
+    if not isinstance(overlays, Mapping) or "dir" not in overlays or "colors" not in overlays or set(overlays) - {"dir", "colors", "rows_per_strip"}:
+        raise ValueError("run_split: overlays must be dict(dir=..., colors=uint8 [K,3]) (optionally rows_per_strip=)")
+    colors = torch.as_tensor(overlays["colors"])
+    if colors.dtype != torch.uint8 or colors.dim() != 2 or colors.shape[0] < 1 or colors.shape[1] != 3:
+        raise ValueError(f"run_split: overlays['colors'] must be uint8 [K,3] with K >= 1, got {colors.dtype} {list(colors.shape)}")
+    return os.fspath(overlays["dir"]), colors.cpu().contiguous(), overlays.get("rows_per_strip")
+
+
+def _overlay_items(mode, ov_dir, job, results):
+    """What the overlay files of one video are made from, in order: (paths, result, colour positions).  Modes "video" and "windows":
+    one image series per expression, <dir>/<video>/<expression position>/<frame_name>.png, colour `position` (inference_ytvos.py:
+    337-350).  Mode "objects": the boxes of ONE object set's objects, colour `object`, at <dir>/<video>/<frame_name>.png -- the
+    reference writes every annotator's image to that one path (inference_davis.py:287-291), so the last set's is what it leaves, and
+    only that one is made here."""
+    if mode == "objects":
+        if not results:
+            return []
+        r = results[-1]
+        return [([os.path.join(ov_dir, job.name, str(f) + ".png") for f in job.frame_names], r, list(range(int(r["pred_boxes"].shape[0]))))]
+    return [([os.path.join(ov_dir, job.name, str(i), str(f) + ".png") for f in job.frame_names], r, [i]) for i, r in enumerate(results)]
+
+
 def run_split(model, jobs, out_dir, *, mode="video", frontend=None, driver_kwargs=None, palette=None, codes="fixed",
-              rows_per_strip=None, workers=8, depth=2, writers=2, rank=0, world=1, run=None, encode=None):
+              rows_per_strip=None, workers=8, depth=2, writers=2, rank=0, world=1, run=None, encode=None, overlays=None):
     """Every video of `jobs` (this rank's block of them: dist.shard_range(len(jobs), rank, world); no collective, each process
     writes its own files) through decode, upload, front-end, driver, PNG encoder and file writer.
 
@@ -386,6 +413,12 @@ def run_split(model, jobs, out_dir, *, mode="video", frontend=None, driver_kwarg
     run(model, frames, job, origin_hw) -> list of dicts with "masks" ("labels" in objects mode) replaces the driver call,
     encode(planes) -> list of bytes replaces the PNG encoder.  With frontend, run and encode all given (and the front-end not a
     ClipFrontEnd) nothing here touches a GPU: no stream, no pinning, the frames stay host tensors.
+    overlays=dict(dir=..., colors=uint8 [K,3]) (device path only) additionally writes the reference's --visualize images as RGB
+    PNGs, drawn on the raw frames on the device (vis.overlay_expression / vis.overlay_objects, png.rgb_pngs).  "video" / "windows":
+    <dir>/<video>/<expression position>/<frame_name>.png, one layer (mask tint, box, reference point -- the default driver is
+    called with ref_points=True), colour colors[position % K].  "objects": <dir>/<video>/<frame_name>.png, the boxes of the last
+    object set's objects, colour colors[object % K].  The files go through the same writer threads and count in `files`.  With
+    overlays=None nothing changes.
 
     Returns dict(videos, frames, pairs (video x expression), files, seconds (wall), busy {decode, upload_wait, forward, encode,
     write: seconds summed over the stage's calls; decode over the worker threads' frames, write over the writer threads'
@@ -409,8 +442,11 @@ def run_split(model, jobs, out_dir, *, mode="video", frontend=None, driver_kwarg
                            "(there is no host fallback; pass frontend=, run= and encode= to drive the pipeline without one)")
     if frontend is None:
         frontend = ClipFrontEnd()
+    ov = None if overlays is None else _check_overlays(overlays)
+    if ov is not None and not on_device:
+        raise ValueError("run_split: overlays are drawn and encoded on the GPU; they need the device path (frames on the device)")
     if run is None:
-        run = _default_run(mode, kw)
+        run = _default_run(mode, kw, ref_points=ov is not None)
     if encode is None:
         if mode == "objects":
             encode = lambda planes: png.label_pngs(planes, palette, rows_per_strip=rows_per_strip, codes=codes)  # noqa: E731
@@ -422,6 +458,7 @@ def run_split(model, jobs, out_dir, *, mode="video", frontend=None, driver_kwarg
     pf = FramePrefetcher(jobs, workers=workers, depth=depth, pin=on_device)
     tl = pf._tl
     up = _Uploader(torch.device("cuda", torch.cuda.current_device())) if on_device else None
+    ov_colors = None if ov is None else ov[1].to(up.device)
     wr = _Writers(writers, tl)
     count = {"videos": 0, "frames": 0, "pairs": 0, "files": 0}
 
@@ -455,7 +492,7 @@ def run_split(model, jobs, out_dir, *, mode="video", frontend=None, driver_kwarg
                 if on_device:
                     up.compute.wait_event(copied)  # the front-end reads what the side stream wrote
                 frames = frontend(dev)
-                if on_device:
+                if on_device and ov is None:
                     up.consumed(v)  # invariant 1: recorded behind the front-end kernels, before anything else reads or waits
                 origin_hw = (int(host.shape[1]), int(host.shape[2]))
                 results = run(model, frames, job, origin_hw)
@@ -468,6 +505,25 @@ def run_split(model, jobs, out_dir, *, mode="video", frontend=None, driver_kwarg
                         raise ValueError(f"run_split: {len(bs)} files for the {len(ps)} frames of video {job.name!r}")
                     paths += ps
                     blobs += bs
+                if ov is not None:
+                    # Invariant 1 with overlays on: the overlay launches read the RAW frames `dev` long after the front-end did, so
+                    # the buffer's `consumed` event is recorded behind the video's LAST overlay launch instead of behind the
+                    # front-end -- the upload that overwrites this buffer (video v + 2, issued in a later iteration) waits for it
+                    # on the side stream.  Every exit between here and that record ends the loop: no later upload is issued.
+                    items = _overlay_items(mode, ov[0], job, results)
+                    if not items:
+                        up.consumed(v)
+                    for k, (ps, r, pos) in enumerate(items):
+                        col = ov_colors[[p % int(ov_colors.shape[0]) for p in pos]]
+                        img = vis.overlay_objects(dev, r["pred_boxes"], col) if mode == "objects" else vis.overlay_expression(dev, r, col)
+                        if k == len(items) - 1:
+                            up.consumed(v)  # invariant 1 (above): behind the last launch that reads `dev`
+                        bs = png.rgb_pngs(img, rows_per_strip=ov[2])
+                        if len(bs) != len(ps):
+                            raise ValueError(f"run_split: {len(bs)} overlay files for the {len(ps)} frames of video {job.name!r}")
+                        paths += ps
+                        blobs += bs
+                        del img
                 tl.add("encode", tl.mark("encode", v, "end") - t0)
                 del frames, results
                 count["videos"] += 1

@@ -1299,6 +1299,85 @@ def png_deflate(planes, rows_per_strip=8, nonzero_value=0, streams=None, nbytes=
     return streams, nbytes
 
 
+def _u8_gpu(t, op, name, dims):
+    if not torch.is_tensor(t) or t.dim() != len(dims.split(",")):
+        raise ValueError(f"{op}: {name} must be [{dims}]")
+    if t.dtype != torch.uint8 or not t.is_cuda or not t.is_contiguous():
+        raise ValueError(f"{op}: {name} must be a contiguous uint8 tensor on the GPU, got {t.dtype} on {t.device}, "
+                         f"contiguous={t.is_contiguous()}")
+    return t
+
+
+def png_filter_rgb(images, rows=None):
+    """The filtered rows of uint8 RGB images [P,H,W,3] on the GPU (tce_png_filter_rgb_u8) -> rows uint8 [P,H,1+3W]: per row its PNG
+    filter type (the one with the least sum of absolute signed filtered bytes, ties to the lowest) and its bytes filtered with it.
+    One launch, no host read-back."""
+    t = _u8_gpu(images, "png_filter_rgb", "images", "P,H,W,3")
+    P, H, W, C = (int(s) for s in t.shape)
+    if C != 3 or min(P, H, W) < 1 or P > 65535 or W > 2 ** 24 or H * (3 * W + 1) >= 2 ** 31 - 4096:
+        raise ValueError(f"png_filter_rgb: unsupported extents {tuple(t.shape)} (P in 1 .. 65535, 3 channels, W <= 2^24, "
+                         f"H * (3W + 1) < 2^31 - 4096)")
+    rows = _out_tensor(rows, "png_filter_rgb: rows [P,H,1+3W]", torch.uint8, (P, H, 1 + 3 * W), t.device)
+    check(lib().tce_png_filter_rgb_u8(t.data_ptr(), rows.data_ptr(), P, H, W, _stream()), "tce_png_filter_rgb_u8")
+    return rows
+
+
+def png_deflate_rows(rows, rows_per_strip=32, streams=None, nbytes=None, ws=None):
+    """The zlib stream of filtered rows uint8 [P,H,R] on the GPU (tce_png_deflate_rows_u8: png_deflate's dynamic stream over bytes
+    that are filtered already, filter byte included) -> (streams uint8 [P,bound], nbytes int32 [P]), bound and the workspace those
+    of png_deflate for planes [P,H,R-1].  Three launches, no host read-back."""
+    t = _u8_gpu(rows, "png_deflate_rows", "rows", "P,H,R")
+    P, H, R = (int(s) for s in t.shape)
+    S = int(rows_per_strip)
+    ok = min(P, H, S) >= 1 and R >= 2 and H * (R - 1) < 2 ** 31 and S < 2 ** 31
+    bound = lib().tce_png_stream_bound(H, R - 1, S) if ok else -1
+    need = lib().tce_png_ws_bytes(P, H, R - 1, S) if ok else -1
+    if bound < 0 or need < 0:
+        raise ValueError(f"png_deflate_rows: unsupported extents P = {P} (1 .. 65535), (H, R) = {(H, R)} (R >= 2, below 2^31 bytes, "
+                         f"the stream bound below 2^31 bytes), rows_per_strip = {S} (>= 1, at most 2^22 strips)")
+    dev = t.device
+    streams = _out_tensor(streams, "png_deflate_rows: streams [P,bound]", torch.uint8, (P, bound), dev)
+    nbytes = _out_tensor(nbytes, "png_deflate_rows: nbytes [P]", torch.int32, (P,), dev)
+    ws = _workspace(ws, "png_deflate_rows", need, dev)
+    check(lib().tce_png_deflate_rows_u8(t.data_ptr(), streams.data_ptr(), nbytes.data_ptr(), ws.data_ptr(), P, H, R, S, _stream()),
+          "tce_png_deflate_rows_u8")
+    return streams, nbytes
+
+
+VIS_MAX_LAYERS = 16  # TCE_VIS_MAX_LAYERS (csrc/tce_rvos_vis.h)
+
+
+def vis_overlay(frames, colors, masks=None, boxes=None, points=None, out=None):
+    """The --visualize image of the reference's drivers on the GPU (tce_vis_overlay_u8, csrc/tce_rvos_vis.h has the per-pixel
+    rule): frames uint8 [N,H0,W0,3] with L layers drawn on them in order -> out uint8 [N,H0,W0,3] (a new tensor, or `out`, which
+    must not overlap frames).  Per layer l, each optional: masks uint8 [L,N,H0,W0] (nonzero = tinted), boxes float32 [L,N,4]
+    (cx, cy, w, h, normalised), points float32 [L,N,2] (x, y, normalised); colors uint8 [L,3].  One launch, no host read-back."""
+    f = _u8_gpu(frames, "vis_overlay", "frames", "N,H0,W0,3")
+    N, H0, W0, C = (int(s) for s in f.shape)
+    dev = f.device
+    c = _u8_gpu(colors, "vis_overlay", "colors", "L,3")
+    L = int(c.shape[0])
+    if C != 3 or int(c.shape[1]) != 3 or c.device != dev:
+        raise ValueError("vis_overlay: frames must be [N,H0,W0,3] and colors [L,3] on one device")
+    if not 1 <= L <= VIS_MAX_LAYERS:
+        raise ValueError(f"vis_overlay: 1..{VIS_MAX_LAYERS} layers, got {L}")
+    if min(N, H0, W0) < 1 or N > 65535 or H0 * W0 * 3 >= 2 ** 31 - 2048:
+        raise ValueError(f"vis_overlay: unsupported extents {tuple(f.shape)} (N in 1 .. 65535, a frame below 2^31 bytes)")
+    if masks is not None:
+        masks = _u8_gpu(masks, "vis_overlay", "masks", "L,N,H0,W0")
+        if tuple(masks.shape) != (L, N, H0, W0) or masks.device != dev:
+            raise ValueError(f"vis_overlay: masks must be {[L, N, H0, W0]} on the frames' device, got {list(masks.shape)}")
+    for t, name, k in ((boxes, "boxes", 4), (points, "points", 2)):
+        if t is not None and (not torch.is_tensor(t) or t.dtype != torch.float32 or tuple(t.shape) != (L, N, k) or not t.is_contiguous()
+                              or t.device != dev):
+            raise ValueError(f"vis_overlay: {name} must be a contiguous float32 {[L, N, k]} on the frames' device")
+    out = _out_tensor(out, "vis_overlay: out [N,H0,W0,3]", torch.uint8, (N, H0, W0, 3), dev)
+    p = lambda t: None if t is None else t.data_ptr()
+    check(lib().tce_vis_overlay_u8(f.data_ptr(), out.data_ptr(), p(masks), p(boxes), p(points), c.data_ptr(), L, N, H0, W0, _stream()),
+          "tce_vis_overlay_u8")
+    return out
+
+
 def ffn_pack(w1, b1, w2, out=None):
     """Packs nn.Linear weights W1 [Hd,C], b1 [Hd], W2 [C,Hd] into the fused-FFN stream (csrc/ffn.hip): fp16 hi/lo
     planes in MFMA-fragment order.  Done once per load_state_dict (static weights) or once per clip into an arena

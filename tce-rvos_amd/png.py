@@ -2,6 +2,7 @@
 
     inference_ytvos.py:354-363   Image.fromarray(mask * 255).convert('L').save(...)       -> mask_pngs(run_video(...)["masks"])
     inference_davis.py:300-311   Image.fromarray(labels), putpalette(palette), save(...)  -> label_pngs(run_video_objects(...)[i]["labels"], palette)
+    the --visualize images       Image.fromarray(frame with box, point, mask).save(...)    -> rgb_pngs(vis.overlay_expression(...))
 
 The device makes each plane's complete zlib stream (ops.png_deflate, include/tce_rvos_png.h: filter bytes, deflate, Adler-32); the host
 reads back the byte counts and then only the bytes in use -- a few KB per mask instead of the plane -- and adds the chunk framing
@@ -9,7 +10,10 @@ below.  The files decode to the same pixels as the reference's.  With codes="fix
 are several times LARGER than Pillow's (fixed Huffman codes, run-length matches only, a flush per strip of 8 rows).  With
 codes="dynamic" every strip's block takes the cheaper of the fixed code and a Huffman code of its own (tce_png_deflate_dyn_u8) and
 the strips are DYNAMIC_ROWS_PER_STRIP rows: files about the size of Pillow's (DESIGN.md section 3.16 has the measured sizes and
-times), never longer than the fixed stream of the same strips.  The framing functions need neither the GPU nor the shared library.
+times), never longer than the fixed stream of the same strips.  RGB images (rgb_pngs, frame_rgb) take a row filter chosen per
+row on the device and then the dynamic stream over the filtered rows (ops.png_filter_rgb, ops.png_deflate_rows); with no distance
+matches a photograph's file is larger than Pillow's.  The framing functions need neither the GPU nor the
+shared library.
 """
 import struct
 import zlib
@@ -37,7 +41,7 @@ def palette_bytes(palette):
 
 def frame(stream, width, height, mode, palette=None):
     """One complete PNG file around a zlib stream of the height * (width + 1) filtered bytes of an 8-bit image: signature, IHDR
-    (bit depth 8, colour type 0 for 'L' and 3 for 'P', no interlace), PLTE for 'P', one IDAT, IEND."""
+    (bit depth 8, colour type 0 for 'L' and 3 for 'P', no interlace), PLTE for 'P', one IDAT, IEND.  (RGB images: frame_rgb.)"""
     if mode not in COLOUR_TYPE:
         raise ValueError(f"png: mode must be 'L' or 'P', got {mode!r}")
     if (palette is None) != (mode == "L"):
@@ -55,7 +59,7 @@ def frame(stream, width, height, mode, palette=None):
 def encode(planes, mode, palette=None, nonzero_value=0, rows_per_strip=None, codes="fixed"):
     """One complete PNG file (bytes) per plane of a uint8 [P,H,W] tensor on the GPU.  One device call (three launches), one
     read-back of the P byte counts, one read-back of the streams' prefixes in use, then the framing.  codes: "fixed" or "dynamic";
-    rows_per_strip = None: 8 for the fixed code, DYNAMIC_ROWS_PER_STRIP for dynamic codes."""
+    rows_per_strip = None: 8 for the fixed code, DYNAMIC_ROWS_PER_STRIP for dynamic codes.  (RGB images: rgb_pngs.)"""
     from . import ops
     if codes not in ("fixed", "dynamic"):
         raise ValueError(f"png: codes must be 'fixed' or 'dynamic', got {codes!r}")
@@ -82,6 +86,34 @@ def label_pngs(labels, palette, rows_per_strip=None, codes="fixed"):
     """The files inference_davis.py:308-311 writes, from run_video_objects(...)[i]["labels"] (uint8 [T,H0,W0] on the GPU): mode
     'P' with the caller's palette bytes (what Image.putpalette takes), the labels as they are."""
     return encode(labels, "P", palette=palette, rows_per_strip=rows_per_strip, codes=codes)
+
+
+def frame_rgb(stream, width, height):
+    """One complete PNG file around a zlib stream of the height * (3 * width + 1) filtered bytes of an 8-bit RGB image: signature,
+    IHDR (bit depth 8, colour type 2, no interlace), one IDAT, IEND.  A function of its own: frame() keeps to the modes 'L' and
+    'P' of 8-bit planes and rejects every other mode, as it always did."""
+    width, height = int(width), int(height)
+    if not (0 < width < 2 ** 31 and 0 < height < 2 ** 31):
+        raise ValueError(f"png: bad size {(width, height)}")
+    return b"".join([SIGNATURE, chunk(b"IHDR", struct.pack(">IIBBBBB", width, height, 8, 2, 0, 0, 0)), chunk(b"IDAT", bytes(stream)),
+                     chunk(b"IEND", b"")])
+
+
+def rgb_pngs(images, rows_per_strip=None):
+    """One complete PNG file (bytes) per image of a uint8 [P,H,W,3] tensor on the GPU, colour type 2: the --visualize images of the
+    reference's drivers (vis.overlay_expression / vis.overlay_objects make the pixels).  Two device calls (the row filter: one
+    launch; the dynamic stream over the filtered rows: three), then the same two read-backs as the other modes and the framing.
+    rows_per_strip = None: DYNAMIC_ROWS_PER_STRIP.  The Ref-DAVIS reference saves these images as RGBA with a constant alpha of
+    255 (inference_davis.py:291); the files here are RGB, which decode to the same colours."""
+    from . import ops
+    if rows_per_strip is None:
+        rows_per_strip = DYNAMIC_ROWS_PER_STRIP
+    rows = ops.png_filter_rgb(images)
+    streams, nbytes = ops.png_deflate_rows(rows, rows_per_strip=rows_per_strip)
+    used = nbytes.cpu().tolist()                                   # read-back 1: P integers
+    flat = streams[:, :max(used)].cpu().numpy()                    # read-back 2: the bytes in use
+    H, W = int(images.shape[1]), int(images.shape[2])
+    return [frame_rgb(flat[p, :n].tobytes(), W, H) for p, n in enumerate(used)]
 
 
 def write_files(paths, blobs):

@@ -41,10 +41,13 @@ from . import ops
 
 
 @torch.no_grad()
-def run_video(model, frames: torch.Tensor, caption, origin_hw, clip_size: Optional[int] = 32, threshold: float = 0.5):
+def run_video(model, frames: torch.Tensor, caption, origin_hw, clip_size: Optional[int] = 32, threshold: float = 0.5,
+              ref_points: bool = False):
     """frames [N,3,H,W] float32 on the GPU (already resized + normalised: frontend.py); caption: str or LongTensor
     [1,L] of token ids; origin_hw = (H0, W0) of the decoded video.
-    Returns dict(masks uint8 [N,H0,W0] (1 = object), best_query int32 [n_chunks], pred_logits [N,K], pred_boxes [N,4])."""
+    Returns dict(masks uint8 [N,H0,W0] (1 = object), best_query int32 [n_chunks], pred_logits [N,K], pred_boxes [N,4]).
+    ref_points=True (opt-in: what vis.overlay_expression draws the cross from): also reference_points [N,2], the best query's
+    rows of the forward's reference_points, gathered like pred_boxes."""
     if frames.dim() != 4 or frames.shape[1] != 3:
         raise ValueError("run_video: frames must be [N,3,H,W]")
     n = frames.shape[0]
@@ -54,7 +57,7 @@ def run_video(model, frames: torch.Tensor, caption, origin_hw, clip_size: Option
     target = [{"size": torch.tensor([H, W])}]
     cap = [caption] if isinstance(caption, str) else caption
     step = n if not clip_size else int(clip_size)
-    masks, best, logits, boxes = [], [], [], []
+    masks, best, logits, boxes, points = [], [], [], [], []
     for lo in range(0, n, step):
         clip = frames[lo:lo + step]
         out = model([clip], cap, target)
@@ -66,9 +69,14 @@ def run_video(model, frames: torch.Tensor, caption, origin_hw, clip_size: Option
         ar = torch.arange(pl.shape[0], device=pl.device)
         logits.append(pl[ar, idx])
         boxes.append(out["pred_boxes"][0][ar, idx])
+        if ref_points:
+            points.append(out["reference_points"][0][ar, idx])
     ops.check_range(frames.device)  # the driver synchronises here anyway: surface a tripped range flag now
-    return {"masks": torch.cat(masks, 0), "best_query": torch.cat(best, 0), "pred_logits": torch.cat(logits, 0),
-            "pred_boxes": torch.cat(boxes, 0)}
+    res = {"masks": torch.cat(masks, 0), "best_query": torch.cat(best, 0), "pred_logits": torch.cat(logits, 0),
+           "pred_boxes": torch.cat(boxes, 0)}
+    if ref_points:
+        res["reference_points"] = torch.cat(points, 0)
+    return res
 
 
 def _collect(out, origin_hw, threshold, acc):
@@ -80,6 +88,8 @@ def _collect(out, origin_hw, threshold, acc):
     acc["best_query"].append(b)
     acc["pred_logits"].append(pl[ar, idx])
     acc["pred_boxes"].append(out["pred_boxes"][0][ar, idx])
+    if "reference_points" in acc:
+        acc["reference_points"].append(out["reference_points"][0][ar, idx])
 
 
 def plan_expression_groups(lengths, max_group: int = 4, mixed_lengths: bool = False):
@@ -98,11 +108,12 @@ def plan_expression_groups(lengths, max_group: int = 4, mixed_lengths: bool = Fa
 
 @torch.no_grad()
 def run_video_expressions(model, frames: torch.Tensor, captions, origin_hw, clip_size: Optional[int] = 32,
-                          threshold: float = 0.5, max_group: int = 4, mixed_lengths: bool = False):
+                          threshold: float = 0.5, max_group: int = 4, mixed_lengths: bool = False, ref_points: bool = False):
     """Every expression of ONE video.  frames as in run_video; captions: list of str (or of LongTensor [1,L]).  Returns a list with
     one run_video-style dict per caption, in order.  Captions of equal token length are grouped (at most `max_group` per forward);
     mixed_lengths=True groups them in input order whatever their lengths, right-padded to the group's longest
-    (forward_group(..., ragged=True): fewer forwards per chunk, the pad rows cost some text work)."""
+    (forward_group(..., ragged=True): fewer forwards per chunk, the pad rows cost some text work).  ref_points=True: every dict also
+    carries reference_points [N,2], as run_video's."""
     if frames.dim() != 4 or frames.shape[1] != 3 or frames.shape[0] == 0:
         raise ValueError("run_video_expressions: frames must be a non-empty [N,3,H,W]")
     n = frames.shape[0]
@@ -110,7 +121,8 @@ def run_video_expressions(model, frames: torch.Tensor, captions, origin_hw, clip
     target = [{"size": torch.tensor([H, W])}]
     ids = [c if torch.is_tensor(c) else model._tokenise([c], frames.device)[0] for c in captions]
     step = n if not clip_size else int(clip_size)
-    accs = [{"masks": [], "best_query": [], "pred_logits": [], "pred_boxes": []} for _ in captions]
+    accs = [{"masks": [], "best_query": [], "pred_logits": [], "pred_boxes": [], **({"reference_points": []} if ref_points else {})}
+            for _ in captions]
     for grp in plan_expression_groups([int(t.shape[1]) for t in ids], max_group, mixed_lengths):
         if mixed_lengths:  # right-padded on the host (validated there), lengths derived again on the device
             from .model import pad_captions
