@@ -240,6 +240,17 @@ VIS_SIGNATURES = {
 # header (relative to the package's csrc/) -> its table: EVERY symbol of its header and no other, as HEADERS (tests check this)
 STAGE_HEADERS = {"tce_rvos_vis.h": VIS_SIGNATURES}
 
+# csrc/tce_rvos_pngfile.h: PNG-file stage entry points (the IDAT chunk's CRC-32 and the chunk framing around the streams, on the
+# device).  A third set beside HEADERS and STAGE_HEADERS, which are both closed; held to its header in the same way.
+PNGFILE_SIGNATURES = {
+    "tce_png_file_bound": (i64, [i32, i64]),  # head_bytes, stream_stride
+    "tce_png_file_ws_bytes": (i64, [i32, i64]),  # P, stream_stride
+    # streams [P,stream_stride] u8, nbytes [P] i32, head [head_bytes] u8, head_bytes, files [P,file_stride] u8, file_bytes [P] i32, ws,
+    # P, stream_stride, file_stride
+    "tce_png_file_u8": (i32, [c_f, c_f, c_f, i32, c_f, c_f, c_f, i32, i64, i64, c_f]),
+}
+FILE_HEADERS = {"tce_rvos_pngfile.h": PNGFILE_SIGNATURES}
+
 _LIB = None
 
 
@@ -260,7 +271,7 @@ def lib():
             warnings.warn(f"tce_rvos_amd: GPU_MAX_HW_QUEUES={hwq} is set; the HIP runtime's default (4) is the only value this "
                           f"launch program runs well with (1-3 crash the runtime, 5-16 double the clip time)", RuntimeWarning)
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in [kv for table in list(HEADERS.values()) + list(STAGE_HEADERS.values()) for kv in table.items()]:
+        for name, (res, args) in [kv for table in list(HEADERS.values()) + list(STAGE_HEADERS.values()) + list(FILE_HEADERS.values()) for kv in table.items()]:
             fn = getattr(l, name)  # AttributeError if the symbol is absent
             fn.restype, fn.argtypes = res, args
         _LIB = l

@@ -10,7 +10,8 @@ checks it statically.
   * every C-ABI launch (`lib().tce_*`) is intercepted: the stream it was issued on and -- from the same pointers and sizes
     the kernel receives -- the byte ranges it reads and writes (`MODELS`: one access model for every launching entry point
     of every header of include/ (_lib.HEADERS), the drivers' output stages included, `STAGE_MODELS` for the stage headers beside
-    the sources (_lib.STAGE_HEADERS); an entry point that is neither modelled
+    the sources (_lib.STAGE_HEADERS), `FILE_MODELS` / `FILE_NOT_LAUNCHES` for the PNG-file stage (_lib.FILE_HEADERS); an entry
+    point that is neither modelled
     nor listed in `NOT_LAUNCHES` is an error, so coverage cannot rot);
   * every event record / wait (torch's `wait_stream` is `wait_event(record_event())`) and every host synchronisation is
     intercepted and turned into vector clocks: launch A happens-before launch B iff B's clock has seen A's tick;
@@ -581,6 +582,22 @@ STAGE_MODELS = {
 }
 
 
+def _png_file(a):
+    """streams, nbytes, head, head_bytes, files, file_bytes, ws, P, stream_stride, file_stride: how far a stream row is read and a
+    file row written is device data (nbytes), so the rows are named whole (a file row: its tce_png_file_bound bytes), as
+    _png_deflate names its streams; ws is written by the first launch and read by the second"""
+    streams, nbytes, head, head_bytes, files, file_bytes, ws, P, sstride, fstride = a[:10]
+    L = _lib.lib_raw()
+    wsb = dense(_p(ws), L.tce_png_file_ws_bytes(P, sstride))
+    return ([dense(_p(streams), P * sstride), dense(_p(nbytes), P * 4), dense(_p(head), head_bytes), wsb],
+            [strided(_p(files), L.tce_png_file_bound(head_bytes, sstride), (P, fstride)), dense(_p(file_bytes), P * 4), wsb])
+
+
+# The PNG-file stage (_lib.FILE_HEADERS): a third set beside MODELS / NOT_LAUNCHES and STAGE_MODELS, which are closed.
+FILE_MODELS = {"tce_png_file_u8": _png_file}
+FILE_NOT_LAUNCHES = {"tce_png_file_bound", "tce_png_file_ws_bytes"}
+
+
 # Entry points that launch nothing (queries, process switches, graph helpers, tuning aids): passed through.
 NOT_LAUNCHES = {"tce_abi_version", "tce_last_error", "tce_gemm_select_tile", "tce_gemm_select_tile_ex", "tce_set_gemm_mode", "tce_set_gemm_mode_thread",
                 "tce_get_gemm_mode", "tce_set_range_flag", "tce_groupnorm_nsplit", "tce_mha_ws_bytes", "tce_ffn_packed_bytes", "tce_ffn_split_ws_floats", "tce_ffn_split_counters",
@@ -725,9 +742,9 @@ class _LibProxy:
 
     def __getattr__(self, name):
         fn = getattr(self._real, name)
-        if name in NOT_LAUNCHES or not name.startswith("tce_"):
+        if name in NOT_LAUNCHES or name in FILE_NOT_LAUNCHES or not name.startswith("tce_"):
             return fn
-        model = MODELS.get(name) or STAGE_MODELS.get(name)
+        model = MODELS.get(name) or STAGE_MODELS.get(name) or FILE_MODELS.get(name)
         if model is None:
             raise RuntimeError(f"hazard checker: no access model for {name} (add one to hazard.MODELS)")
         rec, dry = self._rec, self._dry

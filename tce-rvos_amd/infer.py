@@ -399,7 +399,8 @@ def _overlay_items(mode, ov_dir, job, results):
 
 
 def run_split(model, jobs, out_dir, *, mode="video", frontend=None, driver_kwargs=None, palette=None, codes="fixed",
-              rows_per_strip=None, workers=8, depth=2, writers=2, rank=0, world=1, run=None, encode=None, overlays=None):
+              rows_per_strip=None, workers=8, depth=2, writers=2, rank=0, world=1, run=None, encode=None, overlays=None,
+              framing="host"):
     """Every video of `jobs` (this rank's block of them: dist.shard_range(len(jobs), rank, world); no collective, each process
     writes its own files) through decode, upload, front-end, driver, PNG encoder and file writer.
 
@@ -419,6 +420,8 @@ def run_split(model, jobs, out_dir, *, mode="video", frontend=None, driver_kwarg
     called with ref_points=True), colour colors[position % K].  "objects": <dir>/<video>/<frame_name>.png, the boxes of the last
     object set's objects, colour colors[object % K].  The files go through the same writer threads and count in `files`.  With
     overlays=None nothing changes.
+    framing="host" | "device": where the PNG chunk framing and the IDAT's CRC-32 are made (png.encode); it goes to the default
+    encoder and to the overlays' png.rgb_pngs, a caller's encode= is untouched.  The files are the same bytes either way.
 
     Returns dict(videos, frames, pairs (video x expression), files, seconds (wall), busy {decode, upload_wait, forward, encode,
     write: seconds summed over the stage's calls; decode over the worker threads' frames, write over the writer threads'
@@ -430,6 +433,8 @@ def run_split(model, jobs, out_dir, *, mode="video", frontend=None, driver_kwarg
         raise ValueError("run_split: mode='objects' writes palette PNGs and needs `palette`")
     if isinstance(writers, bool) or not isinstance(writers, int) or not 1 <= writers <= MAX_WORKERS:
         raise ValueError(f"run_split: writers must be an int in 1..{MAX_WORKERS}, got {writers!r}")
+    if framing not in png.FRAMINGS:
+        raise ValueError(f"run_split: framing must be 'host' or 'device', got {framing!r}")
     jobs = list(jobs)
     lo, hi = dist.shard_range(len(jobs), int(rank), int(world))
     jobs = jobs[lo:hi]
@@ -449,9 +454,9 @@ def run_split(model, jobs, out_dir, *, mode="video", frontend=None, driver_kwarg
         run = _default_run(mode, kw, ref_points=ov is not None)
     if encode is None:
         if mode == "objects":
-            encode = lambda planes: png.label_pngs(planes, palette, rows_per_strip=rows_per_strip, codes=codes)  # noqa: E731
+            encode = lambda planes: png.label_pngs(planes, palette, rows_per_strip=rows_per_strip, codes=codes, framing=framing)  # noqa: E731
         else:
-            encode = lambda planes: png.mask_pngs(planes, rows_per_strip=rows_per_strip, codes=codes)  # noqa: E731
+            encode = lambda planes: png.mask_pngs(planes, rows_per_strip=rows_per_strip, codes=codes, framing=framing)  # noqa: E731
     key = "labels" if mode == "objects" else "masks"
 
     t_start = time.perf_counter()
@@ -518,7 +523,7 @@ def run_split(model, jobs, out_dir, *, mode="video", frontend=None, driver_kwarg
                         img = vis.overlay_objects(dev, r["pred_boxes"], col) if mode == "objects" else vis.overlay_expression(dev, r, col)
                         if k == len(items) - 1:
                             up.consumed(v)  # invariant 1 (above): behind the last launch that reads `dev`
-                        bs = png.rgb_pngs(img, rows_per_strip=ov[2])
+                        bs = png.rgb_pngs(img, rows_per_strip=ov[2], framing=framing)
                         if len(bs) != len(ps):
                             raise ValueError(f"run_split: {len(bs)} overlay files for the {len(ps)} frames of video {job.name!r}")
                         paths += ps

@@ -1344,6 +1344,71 @@ def png_deflate_rows(rows, rows_per_strip=32, streams=None, nbytes=None, ws=None
     return streams, nbytes
 
 
+PNG_FILE_PIECE = 64       # TCE_PNG_FILE_PIECE (csrc/tce_rvos_pngfile.h)
+PNG_FILE_SEGMENT = 16384  # TCE_PNG_FILE_SEGMENT
+PNG_FILE_MIN_HEAD, PNG_FILE_MAX_HEAD = 8, 1024  # TCE_PNG_FILE_MIN_HEAD, TCE_PNG_FILE_MAX_HEAD
+
+
+def _rows_u8(t, op, name):
+    """A uint8 [P,n] tensor on the GPU whose rows are contiguous -> (P, n, row stride); the stride may exceed n (a view)"""
+    if not torch.is_tensor(t) or t.dim() != 2 or t.dtype != torch.uint8 or not t.is_cuda:
+        raise ValueError(f"{op}: {name} must be a uint8 [P,n] tensor on the GPU")
+    P, n = (int(s) for s in t.shape)
+    stride = n if P <= 1 else int(t.stride(0))
+    if n > 1 and int(t.stride(1)) != 1 or stride < n:
+        raise ValueError(f"{op}: the rows of {name} must be contiguous and must not overlap, got strides {tuple(t.stride())}")
+    return P, n, stride
+
+
+def png_file(streams, nbytes, head, files=None, file_bytes=None, ws=None):
+    """The finished PNG file around every zlib stream on the GPU (tce_png_file_u8, csrc/tce_rvos_pngfile.h has the layout): head,
+    the IDAT chunk of streams[p, :nbytes[p]] with its length and CRC-32, IEND -> (files uint8 [P,file_bound], file_bytes int32 [P]);
+    row p holds its file_bytes[p] = len(head) + 24 + nbytes[p] bytes, what lies behind them is not written.  streams: the [P,bound]
+    tensor of png_deflate / png_deflate_rows, or a view of one whose rows are contiguous and lie further apart (the row stride is
+    passed on, and file_bound = len(head) + 24 + that stride); nbytes int32 [P].  head: bytes, the same for every file (signature,
+    IHDR, PLTE for mode 'P': png.head / png.head_rgb), 8 .. 1024 of them; it goes to the device in a small uint8 tensor (a uint8
+    tensor on the GPU is taken as it is: inside a graph capture no host memory can be copied).  files may be a view with a larger
+    row stride too and must overlap none of the inputs.  Two launches, no host read-back."""
+    P, n, sstride = _rows_u8(streams, "png_file", "streams")
+    dev = streams.device
+    if not torch.is_tensor(nbytes) or nbytes.dtype != torch.int32 or tuple(nbytes.shape) != (P,) or not nbytes.is_contiguous() or nbytes.device != dev:
+        raise ValueError(f"png_file: nbytes must be a contiguous int32 [{P}] on the streams' device")
+    if torch.is_tensor(head):
+        if head.dtype != torch.uint8 or head.dim() != 1 or not head.is_contiguous() or head.device != dev:
+            raise ValueError("png_file: head as a tensor must be a contiguous uint8 [head_bytes] on the streams' device")
+        hb = int(head.numel())
+    else:
+        head = bytes(head)
+        hb = len(head)
+    if not 1 <= P <= 65535:
+        raise ValueError(f"png_file: P = {P} outside 1 .. 65535")
+    if not PNG_FILE_MIN_HEAD <= hb <= PNG_FILE_MAX_HEAD:
+        raise ValueError(f"png_file: head holds {hb} bytes, outside {PNG_FILE_MIN_HEAD} .. {PNG_FILE_MAX_HEAD}")
+    bound = lib().tce_png_file_bound(hb, sstride) if n >= 1 else -1
+    need = lib().tce_png_file_ws_bytes(P, sstride) if n >= 1 else -1
+    if bound < 0 or need < 0:
+        raise ValueError(f"png_file: unsupported extents: rows of {n} bytes, {sstride} apart (at least 1, head + 24 + stride below 2^31 - 4096)")
+    if files is None:
+        files = torch.empty((P, bound), dtype=torch.uint8, device=dev)
+    fP, fn, fstride = _rows_u8(files, "png_file", "files")
+    if (fP, fn) != (P, bound) or files.device != dev:
+        raise ValueError(f"png_file: files must be {[P, bound]} on the streams' device (tce_png_file_bound), got {list(files.shape)}")
+    if fstride >= 2 ** 31 - 4096:
+        raise ValueError(f"png_file: the rows of files lie {fstride} bytes apart, not below 2^31 - 4096")
+    file_bytes = _out_tensor(file_bytes, "png_file: file_bytes [P]", torch.int32, (P,), dev)
+    ws = _workspace(ws, "png_file", need, dev)
+    if not torch.is_tensor(head):
+        head = torch.frombuffer(bytearray(head), dtype=torch.uint8).to(dev)
+    lo, hi = files.data_ptr(), files.data_ptr() + (P - 1) * fstride + bound
+    for t, name, nb in ((streams, "streams", P * sstride), (nbytes, "nbytes", 4 * P), (head, "head", hb),
+                        (file_bytes, "file_bytes", 4 * P), (ws, "ws", need)):
+        if t.data_ptr() < hi and lo < t.data_ptr() + nb:
+            raise ValueError(f"png_file: files overlaps {name}")
+    check(lib().tce_png_file_u8(streams.data_ptr(), nbytes.data_ptr(), head.data_ptr(), hb, files.data_ptr(), file_bytes.data_ptr(),
+                                ws.data_ptr(), P, sstride, fstride, _stream()), "tce_png_file_u8")
+    return files, file_bytes
+
+
 VIS_MAX_LAYERS = 16  # TCE_VIS_MAX_LAYERS (csrc/tce_rvos_vis.h)
 
 
