@@ -70,6 +70,11 @@ class A2dGroupSample(C.Structure):  # tceA2dGroupSample (include/tce_rvos_eval.h
                 ("logit_stride", i32), ("reserved", i32)]
 
 
+class RefexpSample(C.Structure):  # tceRefexpSample (csrc/tce_rvos_refexp.h)
+    _fields_ = [("logits", c_f), ("boxes_in", c_f), ("masks", c_f), ("scores", c_f), ("order", c_f), ("boxes_out", c_f), ("out", c_f),
+                ("fh", i32), ("fw", i32), ("H0", i32), ("W0", i32)]
+
+
 # name -> (restype, argtypes), one table per header of include/ (HEADERS): EVERY symbol of its header and no other (tests check this)
 SIGNATURES = {
     "tce_abi_version": (i32, []),
@@ -251,6 +256,19 @@ PNGFILE_SIGNATURES = {
 }
 FILE_HEADERS = {"tce_rvos_pngfile.h": PNGFILE_SIGNATURES}
 
+# csrc/tce_rvos_refexp.h: RefCOCO evaluation-stage entry points (the box / mask post-processors for a group of samples, the
+# generalised IoU behind precision@k).  A fourth set beside HEADERS, STAGE_HEADERS and FILE_HEADERS, which are all closed; held to its
+# header in the same way.
+REFEXP_GROUP_MAX = 16   # TCE_REFEXP_GROUP_MAX
+REFEXP_MAX_CAND = 1024  # TCE_REFEXP_MAX_CAND
+REFEXP_SIGNATURES = {
+    # samples (host table), B, Q, K, h, w, threshold
+    "tce_refexp_group_u8": (i32, [C.POINTER(RefexpSample), i32, i32, i32, i32, i32, f32, c_f]),
+    # boxes [M,Q,4], gt [M,4], giou [M,Q], best [M,Q], M, Q
+    "tce_refexp_giou_f32": (i32, [c_f, c_f, c_f, c_f, i32, i32, c_f]),
+}
+REFEXP_HEADERS = {"tce_rvos_refexp.h": REFEXP_SIGNATURES}
+
 _LIB = None
 
 
@@ -271,7 +289,7 @@ def lib():
             warnings.warn(f"tce_rvos_amd: GPU_MAX_HW_QUEUES={hwq} is set; the HIP runtime's default (4) is the only value this "
                           f"launch program runs well with (1-3 crash the runtime, 5-16 double the clip time)", RuntimeWarning)
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in [kv for table in list(HEADERS.values()) + list(STAGE_HEADERS.values()) + list(FILE_HEADERS.values()) for kv in table.items()]:
+        for name, (res, args) in [kv for table in list(HEADERS.values()) + list(STAGE_HEADERS.values()) + list(FILE_HEADERS.values()) + list(REFEXP_HEADERS.values()) for kv in table.items()]:
             fn = getattr(l, name)  # AttributeError if the symbol is absent
             fn.restype, fn.argtypes = res, args
         _LIB = l

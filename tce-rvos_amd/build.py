@@ -19,7 +19,7 @@ LIB = os.path.join(LIBDIR, "libtce_rvos.so")
 # slowest first (they gate the parallel build): the GEMM translation units carry one epilogue body per (act, res) combination
 SOURCES = ["gemm_f16x3_big_256_split.hip", "gemm_f16x3_big_256_single.hip", "gemm_f16x3_big_128_split.hip", "gemm_f16x3_big_128_single.hip",
            "ffn.hip", "rowlin.hip", "conv3x3.hip", "gemm_f16x3_big.hip", "gemm_f16x3_small.hip", "gemm.hip", "attn.hip", "misc.hip", "norm.hip", "msda.hip",
-           "text.hip", "resnet.hip", "frontend.hip", "fewrow.hip", "swinattn.hip", "patch_embed.hip", "thin.hip", "label.hip", "eval.hip", "score.hip", "capi.hip", "a2d_score.hip", "a2d_group.hip", "vis.hip", "pngfile.hip", "png.hip"]
+           "text.hip", "resnet.hip", "frontend.hip", "fewrow.hip", "swinattn.hip", "patch_embed.hip", "thin.hip", "label.hip", "eval.hip", "score.hip", "capi.hip", "a2d_score.hip", "a2d_group.hip", "refexp.hip", "vis.hip", "pngfile.hip", "png.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"] + \
     os.environ.get("HIPCC_EXTRA", "").split()  # audit builds only (e.g. -DFEWROW_RPT2); the shipped library has none

@@ -1,6 +1,6 @@
 // The A2D-Sentences / JHMDB-Sentences post-processor's output stage for a group of samples (csrc/tce_rvos_a2d_group.h): the
 // dataset-size masks and the query scores of up to TCE_A2D_GROUP_MAX samples from one launch.  A byte kernel like a2d_masks_kernel
-// (eval.hip), whose per-pixel body it repeats on the shared rules of mask_planes.h; what it saves is launches, not bytes.
+// (eval.hip), whose per-pixel body it takes from mask_planes.h (mask_quad_bits, shared with refexp.hip); what it saves is launches, not bytes.
 #include "common.h"
 #include "mask_planes.h"
 #include "../../include/tce_rvos_eval.h"
@@ -24,16 +24,10 @@ __global__ void __launch_bounds__(QUAD_THREADS) a2d_group_masks_kernel(const A2d
   const int shift = (int)((uintptr_t)s.out & 3u);
   const int p0 = byte_quad_p0(shift);
   if (p0 >= total) return;
-  const float sy = (float)s.fh / (float)s.H0, sx = (float)s.fw / (float)s.W0;
   QuadPixel px[4];
   byte_quad_pixels(p0, total, s.H0, s.W0, px);
   uint32_t bit[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int ys = min((int)floorf((float)px[j].y * sy), s.fh - 1), xs = min((int)floorf((float)px[j].x * sx), s.fw - 1);
-    const float v = mask_tap_value(s.masks + (long long)px[j].plane * h * w, mask_tap(ys, xs, h, w, 0.25f, 0.25f));
-    bit[j] = mask_sigmoid(v) > threshold ? 1u : 0u;
-  }
+  mask_quad_bits(px, h, w, s.fh, s.fw, s.H0, s.W0, threshold, [&](const int n) { return s.masks + (long long)n * h * w; }, bit);
   byte_quad_store(s.out, p0, total, bit);
 }
 

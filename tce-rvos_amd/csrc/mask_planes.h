@@ -97,3 +97,19 @@ __device__ __forceinline__ void byte_quad_store(uint8_t* __restrict__ out, const
   for (int j = 0; j < 4; ++j)
     if (p0 + j >= 0 && p0 + j < total) out[p0 + j] = (uint8_t)b[j];
 }
+
+// ------------------------------------------------------------------------------------------------------- dataset-size bits
+// The four bits of a byte quad of a dataset-size output [planes,H0,W0] (the group kernels of a2d_group.hip and refexp.hip): per
+// byte the nearest source pixel (ONE fp32 multiply, as ATen) of the (fh, fw) crop of the x4 bilinear plane, its blended logit,
+// sigmoid > threshold -- a2d_masks_kernel's operation sequence (eval.hip).  plane_of(n) = the [h,w] plane behind output plane n.
+template <class PlaneOf>
+__device__ __forceinline__ void mask_quad_bits(const QuadPixel px[4], const int h, const int w, const int fh, const int fw, const int H0,
+                                               const int W0, const float threshold, PlaneOf plane_of, uint32_t bit[4]) {
+  const float sy = (float)fh / (float)H0, sx = (float)fw / (float)W0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int ys = min((int)floorf((float)px[j].y * sy), fh - 1), xs = min((int)floorf((float)px[j].x * sx), fw - 1);
+    const float v = mask_tap_value(plane_of(px[j].plane), mask_tap(ys, xs, h, w, 0.25f, 0.25f));
+    bit[j] = mask_sigmoid(v) > threshold ? 1u : 0u;
+  }
+}

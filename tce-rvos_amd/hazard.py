@@ -10,7 +10,8 @@ checks it statically.
   * every C-ABI launch (`lib().tce_*`) is intercepted: the stream it was issued on and -- from the same pointers and sizes
     the kernel receives -- the byte ranges it reads and writes (`MODELS`: one access model for every launching entry point
     of every header of include/ (_lib.HEADERS), the drivers' output stages included, `STAGE_MODELS` for the stage headers beside
-    the sources (_lib.STAGE_HEADERS), `FILE_MODELS` / `FILE_NOT_LAUNCHES` for the PNG-file stage (_lib.FILE_HEADERS); an entry
+    the sources (_lib.STAGE_HEADERS), `FILE_MODELS` / `FILE_NOT_LAUNCHES` for the PNG-file stage (_lib.FILE_HEADERS), `REFEXP_MODELS` for
+    the RefCOCO evaluation stage (_lib.REFEXP_HEADERS); an entry
     point that is neither modelled
     nor listed in `NOT_LAUNCHES` is an error, so coverage cannot rot);
   * every event record / wait (torch's `wait_stream` is `wait_event(record_event())`) and every host synchronisation is
@@ -598,6 +599,36 @@ FILE_MODELS = {"tce_png_file_u8": _png_file}
 FILE_NOT_LAUNCHES = {"tce_png_file_bound", "tce_png_file_ws_bytes"}
 
 
+def _refexp_group(a):
+    """samples (host table), B, Q, K, h, w: per sample its Q*K logits and Q boxes are read; any of its Q mask planes can be a ranked
+    one, so all are named (none for a box-only sample: masks or out NULL, nothing is written through out then); scores, order and
+    boxes_out are written whole; order is written by the first launch and read by the second (the write covers both).  A ranked
+    sample (logits NULL) has no first launch: its order is read, and of the outputs only out is written"""
+    samples, B, Q, K, h, w = a[:6]
+    rd, wr = [], []
+    for b in range(B):
+        e = samples[b]
+        if _p(e.logits):
+            rd += [dense(_p(e.logits), Q * K * F), dense(_p(e.boxes_in), Q * 4 * F)]
+            wr += [dense(_p(e.scores), Q * F), dense(_p(e.order), Q * 4), dense(_p(e.boxes_out), Q * 4 * F)]
+        else:
+            rd.append(dense(_p(e.order), Q * 4))
+        if _p(e.masks) and _p(e.out):
+            rd.append(dense(_p(e.masks), Q * h * w * F))
+            wr.append(dense(_p(e.out), Q * e.H0 * e.W0))
+    return rd, wr
+
+
+def _refexp_giou(a):
+    """boxes, gt, giou, best, M, Q: everything read and written whole"""
+    boxes, gt, giou, best, M, Q = a[:6]
+    return [dense(_p(boxes), M * Q * 4 * F), dense(_p(gt), M * 4 * F)], [dense(_p(giou), M * Q * F), dense(_p(best), M * Q * F)]
+
+
+# The RefCOCO evaluation stage (_lib.REFEXP_HEADERS): a fourth set, every entry of it launches.
+REFEXP_MODELS = {"tce_refexp_group_u8": _refexp_group, "tce_refexp_giou_f32": _refexp_giou}
+
+
 # Entry points that launch nothing (queries, process switches, graph helpers, tuning aids): passed through.
 NOT_LAUNCHES = {"tce_abi_version", "tce_last_error", "tce_gemm_select_tile", "tce_gemm_select_tile_ex", "tce_set_gemm_mode", "tce_set_gemm_mode_thread",
                 "tce_get_gemm_mode", "tce_set_range_flag", "tce_groupnorm_nsplit", "tce_mha_ws_bytes", "tce_ffn_packed_bytes", "tce_ffn_split_ws_floats", "tce_ffn_split_counters",
@@ -729,7 +760,8 @@ def _site():
     best = "?"
     for fr in traceback.extract_stack(limit=24)[:-3]:
         fn = fr.filename.rsplit("/", 1)[-1]
-        if fn in ("pipeline.py", "text_encoder.py", "model.py", "video.py", "postprocess.py", "score.py", "a2d_score.py", "png.py"):
+        if fn in ("pipeline.py", "text_encoder.py", "model.py", "video.py", "postprocess.py", "score.py", "a2d_score.py", "png.py", "refexp.py",
+                  "refexp_score.py"):
             best = f"{fn}:{fr.lineno} {fr.name}"
     return best
 
@@ -744,7 +776,7 @@ class _LibProxy:
         fn = getattr(self._real, name)
         if name in NOT_LAUNCHES or name in FILE_NOT_LAUNCHES or not name.startswith("tce_"):
             return fn
-        model = MODELS.get(name) or STAGE_MODELS.get(name) or FILE_MODELS.get(name)
+        model = MODELS.get(name) or STAGE_MODELS.get(name) or FILE_MODELS.get(name) or REFEXP_MODELS.get(name)
         if model is None:
             raise RuntimeError(f"hazard checker: no access model for {name} (add one to hazard.MODELS)")
         rec, dry = self._rec, self._dry

@@ -1163,6 +1163,123 @@ def a2d_group_masks(pred_masks_list, logits_list, sizes, orig_sizes, threshold=0
     return res, list(scores.unbind(0))
 
 
+REFEXP_GROUP_MAX = 16   # TCE_REFEXP_GROUP_MAX (csrc/tce_rvos_refexp.h): samples per call
+REFEXP_MAX_CAND = 1024  # TCE_REFEXP_MAX_CAND: Q*K candidates per sample
+
+
+def refexp_group(logits_list, boxes_list, masks_list, sizes, orig_sizes, threshold=0.5, outs=None, order=None):
+    """The reference's PostProcess and PostProcessSegm (postprocessors.py:72-100, 128-152) for B samples on the GPU, at most two
+    launches per REFEXP_GROUP_MAX samples (csrc/tce_rvos_refexp.h).  logits_list: B tensors [Q,K] (outputs['pred_logits'][b]
+    flattened over frames and queries); boxes_list: B tensors [Q,4] cxcywh; masks_list: B tensors [Q,h,w] of one shape, or None for
+    a box-only call (sizes may be None then); sizes / orig_sizes: B pairs (the un-padded model-input size, the original image size)
+    -> (scores, order, boxes, masks), each a list of B tensors: float32 [Q] descending, int32 [Q] flat candidate indices
+    (topk_indexes; ties go to the lower index), float32 [Q,4] xyxy in pixels of the original image, uint8 [Q,H0_b,W0_b] of 0/1
+    (masks is None for a box-only call).  The tensors' addresses go into the launch's table as they are, so every input must be
+    contiguous float32 on the GPU.  outs: B tensors to write the masks into (any address) instead of new ones.
+    order: B int32 [Q] tensors that an earlier (box-only) call on the same logits returned -- a ranked call: the ranking is not
+    launched again, masks are required, and scores, order and boxes come back as None, the given order and None."""
+    lg, bx = list(logits_list), list(boxes_list)
+    pm = None if masks_list is None else list(masks_list)
+    B = len(lg)
+    if B < 1:
+        raise ValueError("refexp_group: at least one sample")
+    if not (len(bx) == len(orig_sizes) == B) or (pm is not None and (len(pm) != B or sizes is None or len(sizes) != B)) \
+            or (outs is not None and len(outs) != B):
+        raise ValueError(f"refexp_group: {B} logits but {len(bx)} boxes, {len(orig_sizes)} original sizes"
+                         + ("" if pm is None else f", {len(pm)} masks, {0 if sizes is None else len(sizes)} sizes")
+                         + ("" if outs is None else f", {len(outs)} outs"))
+    if outs is not None and pm is None:
+        raise ValueError("refexp_group: outs without masks (a box-only call writes no masks)")
+    if order is not None and (pm is None or len(order) != B):
+        raise ValueError("refexp_group: a ranked call (order given) takes masks and one order per sample")
+    t0 = lg[0]
+    if not torch.is_tensor(t0) or t0.dim() != 2:
+        raise ValueError("refexp_group: logits must be one [Q,K] tensor per sample")
+    Q, K = (int(s) for s in t0.shape)
+    if Q < 1 or K < 1 or Q * K > REFEXP_MAX_CAND:
+        raise ValueError(f"refexp_group: 1..{REFEXP_MAX_CAND} candidates (Q*K) per sample, got {Q} x {K}")
+    dev = t0.device
+    h = w = 0
+    if pm is not None:
+        if not torch.is_tensor(pm[0]) or pm[0].dim() != 3:
+            raise ValueError("refexp_group: masks must be one [Q,h,w] tensor per sample")
+        h, w = int(pm[0].shape[1]), int(pm[0].shape[2])
+    geo = []
+    named = [[(lg[b], "logits", (Q, K)), (bx[b], "boxes", (Q, 4))] + ([] if pm is None else [(pm[b], "masks", (Q, h, w))])
+             for b in range(B)]
+    for b in range(B):  # the shapes of all samples before anything else is looked at
+        for t, name, shape in named[b]:
+            if not torch.is_tensor(t) or tuple(t.shape) != shape:
+                raise ValueError(f"refexp_group: {name}[{b}] has shape {tuple(getattr(t, 'shape', ()))}, expected {shape}")
+    for b in range(B):
+        for t, name, shape in named[b]:
+            if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.device != dev:
+                raise ValueError(f"refexp_group: {name}[{b}] must be a contiguous float32 tensor on the GPU (one device), got "
+                                 f"{t.dtype} on {t.device}, contiguous={t.is_contiguous()}")
+        H0, W0 = int(orig_sizes[b][0]), int(orig_sizes[b][1])
+        fh, fw = (0, 0) if pm is None else (int(sizes[b][0]), int(sizes[b][1]))
+        if min(H0, W0) < 1 or (pm is not None and min(h, w, fh, fw) < 1):
+            raise ValueError("refexp_group: empty extent")
+        if pm is not None and (fh > 4 * h or fw > 4 * w):
+            raise ValueError(f"refexp_group: size {(fh, fw)} of sample {b} exceeds 4x the mask plane {(h, w)}")
+        if pm is not None and Q * H0 * W0 >= 2 ** 31 - 4096:
+            raise ValueError("refexp_group: an output must stay below 2^31 elements")
+        geo.append((fh, fw, H0, W0))
+    res = None if pm is None else [_out_tensor(None if outs is None else outs[b], f"refexp_group: outs[{b}] [Q,H0,W0]", torch.uint8,
+                                               (Q, g[2], g[3]), dev) for b, g in enumerate(geo)]
+    ranked = order is not None
+    if ranked:
+        order = list(order)
+        for b, t in enumerate(order):
+            if not torch.is_tensor(t) or tuple(t.shape) != (Q,) or t.dtype != torch.int32 or not t.is_contiguous() or t.device != dev:
+                raise ValueError(f"refexp_group: order[{b}] must be a contiguous int32 [Q = {Q}] tensor on the inputs' device")
+        scores = boxes = None
+    else:
+        scores = torch.empty(B, Q, dtype=torch.float32, device=dev)
+        order = torch.empty(B, Q, dtype=torch.int32, device=dev)
+        boxes = torch.empty(B, Q, 4, dtype=torch.float32, device=dev)
+    from ._lib import RefexpSample
+    st = _stream()
+    for lo in range(0, B, REFEXP_GROUP_MAX):
+        n = min(REFEXP_GROUP_MAX, B - lo)
+        table = (RefexpSample * n)()  # read by the entry point on the host, at this call
+        for k in range(n):
+            b, e = lo + k, table[k]
+            e.order = order[b].data_ptr()
+            if not ranked:
+                e.logits, e.boxes_in, e.scores, e.boxes_out = lg[b].data_ptr(), bx[b].data_ptr(), scores[b].data_ptr(), boxes[b].data_ptr()
+            if pm is not None:
+                e.masks, e.out = pm[b].data_ptr(), res[b].data_ptr()
+            e.fh, e.fw, e.H0, e.W0 = geo[b]
+        check(lib().tce_refexp_group_u8(table, n, Q, K, h, w, float(threshold), st), "tce_refexp_group_u8")
+    if ranked:
+        return None, order, None, res
+    return list(scores.unbind(0)), list(order.unbind(0)), list(boxes.unbind(0)), res
+
+
+def refexp_giou(boxes, gt, giou=None, best=None):
+    """Generalised IoU (util/box_ops.py:44-81 in fp32, operation for operation) of boxes [M,Q,4] against the one ground-truth box
+    gt [M,4] of each image, all xyxy, and its running maximum over the Q boxes in their order -> (giou [M,Q], best [M,Q]) float32:
+    best[m, k-1] >= thresh_iou is the hit of refexp_eval.py:67 at k.  One launch; M <= 65535, Q <= 1024."""
+    for t, name, dims in ((boxes, "boxes [M,Q,4]", 3), (gt, "gt [M,4]", 2)):
+        if not torch.is_tensor(t) or t.dim() != dims or int(t.shape[-1]) != 4:
+            raise ValueError(f"refexp_giou: {name} expected, got {tuple(getattr(t, 'shape', ()))}")
+    for t, name in ((boxes, "boxes [M,Q,4]"), (gt, "gt [M,4]")):
+        if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.device != boxes.device:
+            raise ValueError(f"refexp_giou: {name} must be a contiguous float32 tensor on the GPU (one device), got {t.dtype} on "
+                             f"{t.device}, contiguous={t.is_contiguous()}")
+    M, Q = int(boxes.shape[0]), int(boxes.shape[1])
+    if int(gt.shape[0]) != M:
+        raise ValueError(f"refexp_giou: {M} images of boxes but {int(gt.shape[0])} ground-truth boxes")
+    if not (1 <= M <= 65535 and 1 <= Q <= 1024):
+        raise ValueError(f"refexp_giou: 1..65535 images of 1..1024 boxes per call, got {M} x {Q}")
+    giou = _out_tensor(giou, "refexp_giou: giou [M,Q]", torch.float32, (M, Q), boxes.device)
+    best = _out_tensor(best, "refexp_giou: best [M,Q]", torch.float32, (M, Q), boxes.device)
+    check(lib().tce_refexp_giou_f32(boxes.data_ptr(), gt.data_ptr(), giou.data_ptr(), best.data_ptr(), M, Q, _stream()),
+          "tce_refexp_giou_f32")
+    return giou, best
+
+
 def rle_counts(masks, counts=None, nruns=None, ws=None):
     """Uncompressed COCO run lengths (cocoapi rleEncode, column-major) of uint8 masks [P,H,W] on the GPU -> (counts uint32-valued
     int32 [P,H*W+1], nruns int32 [P]): row p holds its nruns[p] counts, zeros behind them.  Two launches, no host read-back."""

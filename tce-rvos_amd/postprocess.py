@@ -3,8 +3,11 @@ engine.py:308-319): dataset-size binary masks and their COCO run-length strings.
 
 The masks and the run lengths are computed on the GPU (ops.a2d_masks, ops.rle_counts: include/tce_rvos_eval.h); the host sees the
 run counts and the used prefix of the run lengths only, and packs them into the strings pycocotools' encoder returns
-(rle_to_string).  The COCO-pretraining post-processors (PostProcess, PostProcessSegm) stay stubs: the reference itself does not
-use them for RVOS.
+(rle_to_string).
+
+The reference's image-setting post-processors, which its RefCOCO / RefCOCO+ / RefCOCOg evaluation calls (postprocessors.py:58-155,
+engine.py:113-120), are PostProcess and PostProcessSegm below, on ops.refexp_group (csrc/tce_rvos_refexp.h); they are reached through
+build_refexp_postprocessors.  build_postprocessors is unchanged and still hands out a stub for everything but A2D / JHMDB.
 """
 import numpy as np
 import torch
@@ -139,3 +142,136 @@ def build_postprocessors(args, dataset_name):
         return A2DSentencesPostProcess(threshold=getattr(args, "threshold", 0.5))
     from .model import _Stub
     return {"segm": _Stub("PostProcessSegm")}
+
+
+# ------------------------------------------------------------------------------------------ RefCOCO / RefCOCO+ / RefCOCOg
+class _Result(dict):
+    """A result dict of PostProcess with a private marker beside its keys: the flattened logits it was ranked from and the ranking,
+    so that PostProcessSegm on the same outputs does not rank again"""
+    _refexp = None
+
+
+def _refexp_samples(outputs, need_masks):
+    """outputs (one dict with a batch axis, or a list of such dicts, as forward_group returns them) -> per sample (logits [Q,K],
+    boxes [Q,4], masks [Q,h,w] | None) with Q = T*N: the reference's flatten(1, 2) (postprocessors.py:78-79, 128-129)"""
+    outs = [outputs] if isinstance(outputs, dict) else list(outputs)
+    res = []
+    for o in outs:
+        lg, bx = o["pred_logits"], o["pred_boxes"]
+        if lg.dim() != 4 or bx.dim() != 4 or tuple(bx.shape) != tuple(lg.shape[:3]) + (4,):
+            raise ValueError(f"PostProcess: pred_logits must be [B,T,N,K] and pred_boxes [B,T,N,4], got {tuple(lg.shape)} and "
+                             f"{tuple(bx.shape)}")
+        pm = o["pred_masks"] if need_masks else None
+        if pm is not None and (pm.dim() != 5 or tuple(pm.shape[:3]) != tuple(lg.shape[:3])):
+            raise ValueError(f"PostProcessSegm: pred_masks must be [B,T,N,h,w] beside pred_logits {tuple(lg.shape)}, got "
+                             f"{tuple(pm.shape)}")
+        K = int(lg.shape[3])
+        for b in range(lg.shape[0]):
+            res.append((lg[b].reshape(-1, K).to(torch.float32).contiguous(), bx[b].reshape(-1, 4).to(torch.float32).contiguous(),
+                        None if pm is None else pm[b].reshape((-1,) + tuple(pm.shape[3:])).to(torch.float32).contiguous()))
+    return res
+
+
+def _buckets(samples):
+    """sample indices by what one ops.refexp_group call shares: (Q, K), the mask plane, the device"""
+    buckets = {}
+    for b, (lg, _, pm) in enumerate(samples):
+        buckets.setdefault((tuple(lg.shape), None if pm is None else tuple(pm.shape[1:]), lg.device), []).append(b)
+    return list(buckets.values())
+
+
+def _same_logits(marker, lg):
+    """Was `marker` left by a ranking of exactly these logits (same memory, same shape, not written since)?"""
+    t = None if marker is None else marker[0]
+    return t is not None and t.data_ptr() == lg.data_ptr() and tuple(t.shape) == tuple(lg.shape) and t.device == lg.device \
+        and marker[2] == lg._version
+
+
+def _refexp_results(samples, orig, size, threshold):
+    """One ops.refexp_group call per bucket for boxes and (where the samples carry masks) masks: the _Result per sample"""
+    results = [None] * len(samples)
+    for members in _buckets(samples):
+        with_masks = samples[members[0]][2] is not None
+        scores, order, boxes, masks = ops.refexp_group([samples[b][0] for b in members], [samples[b][1] for b in members],
+                                                       [samples[b][2] for b in members] if with_masks else None,
+                                                       [size[b] for b in members] if with_masks else None,
+                                                       [orig[b] for b in members], threshold=threshold)
+        labels = torch.ones(len(members), scores[0].shape[0], dtype=torch.int64, device=scores[0].device)
+        for k, b in enumerate(members):
+            r = _Result(scores=scores[k], labels=labels[k], boxes=boxes[k])
+            if with_masks:
+                r["masks"] = masks[k].unsqueeze(1)
+            r._refexp = (samples[b][0], order[k], samples[b][0]._version)
+            results[b] = r
+    return results
+
+
+class PostProcess(nn.Module):
+    """models/postprocessors.py:58-100 on the GPU.  forward(outputs, target_sizes) -> one dict per sample, all on the GPU:
+      scores  fp32 [Q]    the Q = T*N largest of the Q*K sigmoid scores, descending (torch.topk, sorted)
+      labels  int64 [Q]   ones (:98, "binary for the pretraining")
+      boxes   fp32 [Q,4]  x0,y0,x1,y1 in pixels of target_sizes: the ranked candidates' boxes, bit for bit the reference's
+    outputs: one dict with a batch axis, or a list of such dicts (what model.forward_group returns).  One launch per
+    ops.REFEXP_GROUP_MAX samples that share (Q, K).  Deviation: equal scores are ordered by their flat candidate index (topk
+    leaves their order unspecified)."""
+
+    @torch.no_grad()
+    def forward(self, outputs, target_sizes):
+        samples = _refexp_samples(outputs, need_masks=False)
+        orig = _sizes(target_sizes)
+        if len(orig) != len(samples):
+            raise ValueError(f"PostProcess: {len(samples)} samples, {len(orig)} target sizes")
+        return _refexp_results(samples, orig, None, 0.5)
+
+
+class PostProcessSegm(nn.Module):
+    """models/postprocessors.py:103-154 on the GPU.  forward(results, outputs, orig_target_sizes, max_target_sizes) adds to every
+    result 'masks' uint8 [Q,1,H0,W0] of 0/1 on the GPU (the reference's dtype, on the host there): plane r is the mask of the
+    r-th ranked candidate, up-sampled x4, binarised at `threshold` (used, unlike the A2D class's), cropped to max_target_sizes and
+    resized (nearest) to orig_target_sizes -- the bytes of ops.a2d_masks for that plane.
+    When `results` came from this module's PostProcess on the same outputs (a private marker says so), its ranking is used and only
+    the masks launch runs; any other results take the full call (ranking and masks; their other keys are left as they are).
+    with_boxes(outputs, orig_target_sizes, max_target_sizes) is both classes in ONE ops.refexp_group call per group: what
+    refexp.run_images uses."""
+
+    def __init__(self, threshold=0.5):
+        super().__init__()
+        self.threshold = threshold
+
+    @staticmethod
+    def _checked(outputs, orig_target_sizes, max_target_sizes):
+        samples = _refexp_samples(outputs, need_masks=True)
+        orig, size = _sizes(orig_target_sizes), _sizes(max_target_sizes)
+        if not len(orig) == len(size) == len(samples):
+            raise ValueError(f"PostProcessSegm: {len(samples)} samples, {len(orig)} original sizes, {len(size)} sizes")
+        return samples, orig, size
+
+    @torch.no_grad()
+    def with_boxes(self, outputs, orig_target_sizes, max_target_sizes):
+        samples, orig, size = self._checked(outputs, orig_target_sizes, max_target_sizes)
+        return _refexp_results(samples, orig, size, self.threshold)
+
+    @torch.no_grad()
+    def forward(self, results, outputs, orig_target_sizes, max_target_sizes):
+        samples, orig, size = self._checked(outputs, orig_target_sizes, max_target_sizes)
+        if len(results) != len(samples):
+            raise ValueError(f"PostProcessSegm: {len(samples)} samples, {len(results)} results")
+        for members in _buckets(samples):
+            ranked = all(_same_logits(getattr(results[b], "_refexp", None), samples[b][0]) for b in members)
+            _, _, _, masks = ops.refexp_group([samples[b][0] for b in members], [samples[b][1] for b in members],
+                                              [samples[b][2] for b in members], [size[b] for b in members],
+                                              [orig[b] for b in members], threshold=self.threshold,
+                                              order=[results[b]._refexp[1] for b in members] if ranked else None)
+            for k, b in enumerate(members):
+                results[b]["masks"] = masks[k].unsqueeze(1)
+        return results
+
+
+def build_refexp_postprocessors(args):
+    """What models/postprocessors.py:162-166 returns for the image setting: {'bbox': PostProcess()} and, with args.masks,
+    'segm': PostProcessSegm(threshold=args.threshold).  A builder of its own: build_postprocessors keeps returning what it
+    returned (INTEGRATION.md has the swap in main.py's RefCOCO branch)."""
+    post = {"bbox": PostProcess()}
+    if getattr(args, "masks", False):
+        post["segm"] = PostProcessSegm(threshold=getattr(args, "threshold", 0.5))
+    return post
