@@ -78,9 +78,28 @@ int tce_set_gemm_mode_thread(int32_t mode);
 
 /* Operand-range guard of the split-fp16 arithmetic (its operands must lie inside the fp16 range, |x| < 65504: larger
  * values saturate silently in v_cvt_pkrtz).  Weights are checked on the host when they are packed; activations are
- * checked where they are PRODUCED: every GEMM / fused-FFN epilogue of the split mode sets *flag = 1 when it stores a
- * value with |v| >= 60000 or a NaN.  `flag` is a device int32 owned by the caller (NULL disables the check); the caller
- * reads and clears it at its own synchronisation points (tce_rvos_amd.ops.check_range). */
+ * checked where they are PRODUCED: a store site of the split mode sets *flag = 1 when it stores a value with
+ * |v| >= 60000, an Inf or a NaN (modes 1 and 2; exact fp32, mode 0, has no operand contract and reports nothing).
+ * The stores that report (tests/_range.py lists them, one case each):
+ *   - tce_gemm_f32: the tile epilogue of every split-mode tile (bias, activation, residual applied), and the
+ *     elementwise fix-up pass behind epilogue combinations without a specialised body (the value after the residual
+ *     and the trailing ReLU);
+ *   - tce_gemm_splitk_f32 / tce_splitk_reduce_f32: the partial planes (by the tile epilogue; conservative: a plane may
+ *     trip the flag while the sum is in range) AND the reduced value (sum + bias, activation, residual);
+ *   - tce_gemm_splitk_ln_f32 and the LayerNorm form of tce_splitk_reduce_f32: the LayerNorm output, both kernels;
+ *   - tce_rowlin_f32: the final store (after LayerNorm where one is folded);
+ *   - tce_ffn_fused_f32 / _split_f32 / tce_xattn_fused_f32 / tce_xattn_ffn_fused_f32: the hidden values, the chain's
+ *     intermediate rows and the final store;
+ *   - tce_conv3x3_f32 / _split_f32: the tile store, and the reduced value of the split entry;
+ *   - tce_swin_attn_fused_f32: the qkv rows, the attention output and the final store;
+ *   - tce_patch_embed_f32: the LayerNorm output (the matrix-core kernel, and the fp32 kernels that run in its place for
+ *     widths it does not cover);
+ *   - tce_thin_partials_f32 with xsplits > 0: the finished x (act(sum of planes + bias)) as it is LOADED -- that value is
+ *     never stored, the consumer reports on it before splitting it.
+ * Not reported: the A + A2 sum a GEMM forms before the split, and outputs of kernels that are not split products (norms,
+ * resampling, attention cores: DESIGN.md, "Range guard: what is not covered").  `flag` is a device int32 owned by the
+ * caller (NULL disables the check); the caller reads and clears it at its own synchronisation points
+ * (tce_rvos_amd.ops.check_range). */
 int tce_set_range_flag(int32_t* flag);
 
 /* LayerNorm over the last dim: out[m,:] = LN(x[m,:] (+ r[m,:])) * gamma + beta.   r may be NULL.

@@ -281,7 +281,7 @@ namespace {
 __global__ void __launch_bounds__(256) epi_fix_kernel(float* __restrict__ C, const float* __restrict__ res, const int M,
                                                       const int N, const long long ldc, const long long ldres,
                                                       const long long sC, const long long sRes, const int res_mode,
-                                                      const int relu) {
+                                                      const int relu, int* const range_flag) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= (long long)M * N) return;
   const int m = (int)(i / N), n = (int)(i % N);
@@ -293,13 +293,15 @@ __global__ void __launch_bounds__(256) epi_fix_kernel(float* __restrict__ C, con
   }
   if (relu) v = fmaxf(v, 0.f);
   *c = v;
+  tce_range_report(range_flag, tce_amax1(0, v));  // the final value: the GEMM's own report saw it before the residual
 }
 }  // namespace
 
 static int launch_epi_fix(const tceGemmArgs& a, int res_mode, bool relu, hipStream_t s) {
   const long long total = (long long)a.M * a.N;
   hipLaunchKernelGGL(epi_fix_kernel, dim3(tce_cdiv(total, 256), a.batch > 0 ? a.batch : 1), dim3(256), 0, s, a.C, a.res, a.M, a.N,
-                     (long long)a.ldc, (long long)a.ldres, (long long)a.sC, (long long)a.sRes, res_mode, relu ? 1 : 0);
+                     (long long)a.ldc, (long long)a.ldres, (long long)a.sC, (long long)a.sRes, res_mode, relu ? 1 : 0,
+                     g_gemm_mode >= 1 ? tce_range_flag() : nullptr);
   TCE_CHECK_LAUNCH("tce_gemm_f32(epilogue fix-up)");
   return TCE_OK;
 }
@@ -371,7 +373,8 @@ namespace {
 __global__ void __launch_bounds__(256) splitk_reduce_kernel(const float* __restrict__ ws, const float* __restrict__ bias,
                                                             const float* __restrict__ res, float* __restrict__ C,
                                                             const int M, const int N, const int splits, const int ldc,
-                                                            const int ldres, const int act, const int res_mode) {
+                                                            const int ldres, const int act, const int res_mode,
+                                                            int* const range_flag) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   const int n4 = N >> 2;
   if (i >= (long long)M * n4) return;
@@ -379,6 +382,7 @@ __global__ void __launch_bounds__(256) splitk_reduce_kernel(const float* __restr
   const long long plane = (long long)M * N;
   f32x4 v = *reinterpret_cast<const f32x4*>(ws + (long long)m * N + n);
   for (int s = 1; s < splits; ++s) v += *reinterpret_cast<const f32x4*>(ws + s * plane + (long long)m * N + n);
+  tce_amax_t amax = 0;
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
     float x = v[c] + (bias ? bias[n + c] : 0.f);
@@ -387,8 +391,11 @@ __global__ void __launch_bounds__(256) splitk_reduce_kernel(const float* __restr
     if (res_mode == 1) x += res[(long long)m * ldres + n + c];
     if (res_mode == 2) x *= res[(long long)m * ldres + n + c];
     if (act == 3) x = fmaxf(x, 0.f);
+    amax = tce_amax1(amax, x);
     C[(long long)m * ldc + n + c] = x;
   }
+  // the partial launches reported on the partial planes only: the sum, the bias and the residual meet here
+  tce_range_report(range_flag, amax);
 }
 // The same reduction with the LayerNorm that follows it in every post-norm block (RoBERTa's attention.output / output
 // sub-layers, the decoder's FFN): one wavefront per output row (N <= 1024) sums the splits, adds bias + residual and
@@ -401,7 +408,7 @@ __global__ void __launch_bounds__(256) splitk_reduce_ln_row_kernel(const float* 
                                                                    const float* res, float* C, const int M, const int N,
                                                                    const int splits, const int ldc, const int ldres,
                                                                    const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                                   const float eps) {
+                                                                   const float eps, int* const range_flag) {
   __shared__ float sPart[2][4];
   const int m = blockIdx.x, t = threadIdx.x, n4 = N >> 2;
   const long long plane = (long long)M * N;
@@ -435,6 +442,7 @@ __global__ void __launch_bounds__(256) splitk_reduce_ln_row_kernel(const float* 
 #pragma unroll
     for (int c = 0; c < 4; ++c) o[c] = (a[c] - mean) * rstd * g[c] + b[c];
     *reinterpret_cast<f32x4*>(C + (long long)m * ldc + 4 * t) = o;
+    tce_range_report(range_flag, tce_amax4(0, o));
   }
 }
 
@@ -444,7 +452,8 @@ __global__ void __launch_bounds__(256) splitk_reduce_ln_kernel(const float* __re
                                                                const float* res, float* C,
                                                                const int M, const int N, const int splits, const int ldc,
                                                                const int ldres, const float* __restrict__ gamma,
-                                                               const float* __restrict__ beta, const float eps) {
+                                                               const float* __restrict__ beta, const float eps,
+                                                               int* const range_flag) {
   const int lane = threadIdx.x & 63;
   const int m = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (m >= M) return;
@@ -489,6 +498,7 @@ __global__ void __launch_bounds__(256) splitk_reduce_ln_kernel(const float* __re
         sq = fmaf(d, d, sq);
       }
   const float rstd = rsqrtf(wave_sum(sq) / (float)N + eps);
+  tce_amax_t amax = 0;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const int q = lane + 64 * j;
@@ -497,9 +507,11 @@ __global__ void __launch_bounds__(256) splitk_reduce_ln_kernel(const float* __re
       f32x4 o;
 #pragma unroll
       for (int c = 0; c < 4; ++c) o[c] = (v[j][c] - mean) * rstd * g[c] + b[c];
+      amax = tce_amax4(amax, o);
       *reinterpret_cast<f32x4*>(C + (long long)m * ldc + 4 * q) = o;
     }
   }
+  tce_range_report(range_flag, amax);
 }
 }  // namespace
 
@@ -518,19 +530,20 @@ extern "C" int tce_splitk_reduce_f32(const float* ws, int32_t splits, int32_t M,
   TCE_CHECK_ARG(act >= 0 && act <= 3 && res_mode >= 0 && res_mode <= 2 && (res_mode == 0 || (res && ldres >= N)),
                 "tce_splitk_reduce_f32: bad act / res_mode");
   TCE_CHECK_ARG(tce_aligned16(ws) && (!bias || tce_aligned16(bias)), "tce_splitk_reduce_f32: ws / bias must be 16-byte aligned");
+  int* const rf = g_gemm_mode >= 1 ? tce_range_flag() : nullptr;  // exact fp32 has no operand contract
   if (gamma) {
     TCE_CHECK_ARG(beta && act == 0 && res_mode != 2 && N <= 1024 && ldc % 4 == 0 && (res_mode == 0 || ldres % 4 == 0) &&
                       tce_aligned16(C) && tce_aligned16(gamma) && tce_aligned16(beta) && (res_mode == 0 || tce_aligned16(res)),
                   "tce_splitk_reduce_f32: LayerNorm form: no activation, additive residual, N <= 1024, 16-byte aligned rows");
     if (M <= 256)
       hipLaunchKernelGGL(splitk_reduce_ln_row_kernel, dim3(M), dim3(256), 0, (hipStream_t)stream, ws, bias,
-                         res_mode == 1 ? res : nullptr, C, M, N, splits, ldc, ldres, gamma, beta, eps);
+                         res_mode == 1 ? res : nullptr, C, M, N, splits, ldc, ldres, gamma, beta, eps, rf);
     else
       hipLaunchKernelGGL(splitk_reduce_ln_kernel, dim3(tce_cdiv(M, 4)), dim3(256), 0, (hipStream_t)stream, ws, bias,
-                         res_mode == 1 ? res : nullptr, C, M, N, splits, ldc, ldres, gamma, beta, eps);
+                         res_mode == 1 ? res : nullptr, C, M, N, splits, ldc, ldres, gamma, beta, eps, rf);
   } else {
     hipLaunchKernelGGL(splitk_reduce_kernel, dim3(tce_cdiv((long long)M * (N / 4), 256)), dim3(256), 0, (hipStream_t)stream, ws, bias,
-                       res, C, M, N, splits, ldc, ldres, act, res_mode);
+                       res, C, M, N, splits, ldc, ldres, act, res_mode, rf);
   }
   TCE_CHECK_LAUNCH("tce_splitk_reduce_f32");
   return TCE_OK;
@@ -571,15 +584,16 @@ static int splitk_impl(const tceGemmArgs* args, int32_t splits, float* workspace
   const int st = tce_gemm_f32(&g, stream);
   if (st != TCE_OK) return st;
   const long long total = (long long)a.M * (a.N / 4);
+  int* const rf = g_gemm_mode >= 1 ? tce_range_flag() : nullptr;  // exact fp32 has no operand contract
   if (gamma && a.M <= 256)
     hipLaunchKernelGGL(splitk_reduce_ln_row_kernel, dim3(a.M), dim3(256), 0, (hipStream_t)stream, workspace, a.bias,
-                       a.res_mode == 1 ? a.res : nullptr, a.C, a.M, a.N, splits, a.ldc, a.ldres, gamma, beta, eps);
+                       a.res_mode == 1 ? a.res : nullptr, a.C, a.M, a.N, splits, a.ldc, a.ldres, gamma, beta, eps, rf);
   else if (gamma)
     hipLaunchKernelGGL(splitk_reduce_ln_kernel, dim3(tce_cdiv(a.M, 4)), dim3(256), 0, (hipStream_t)stream, workspace, a.bias,
-                       a.res_mode == 1 ? a.res : nullptr, a.C, a.M, a.N, splits, a.ldc, a.ldres, gamma, beta, eps);
+                       a.res_mode == 1 ? a.res : nullptr, a.C, a.M, a.N, splits, a.ldc, a.ldres, gamma, beta, eps, rf);
   else
     hipLaunchKernelGGL(splitk_reduce_kernel, dim3(tce_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, workspace, a.bias,
-                       a.res, a.C, a.M, a.N, splits, a.ldc, a.ldres, a.act, a.res_mode);
+                       a.res, a.C, a.M, a.N, splits, a.ldc, a.ldres, a.act, a.res_mode, rf);
   TCE_CHECK_LAUNCH("tce_gemm_splitk_f32(reduce)");
   return TCE_OK;
 }

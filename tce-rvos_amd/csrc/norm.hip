@@ -2,6 +2,7 @@
 // wavefront-shuffle reductions (64 lanes), statistics in fp32 two-pass form (mean, then centred variance)
 // to match PyTorch's numerics.
 #include "common.h"
+#include "gemm_epilogue.h"
 #include "../../include/tce_rvos.h"
 
 namespace {
@@ -151,8 +152,10 @@ __global__ void __launch_bounds__(256) patch_embed_kernel(const float* __restric
                                                           const float* __restrict__ w, const float* __restrict__ b,
                                                           const float* __restrict__ gamma,
                                                           const float* __restrict__ beta, float* __restrict__ out,
-                                                          int T, int H, int W, int C, float eps, int tokens_per_block) {
+                                                          int T, int H, int W, int C, float eps, int tokens_per_block,
+                                                          int* const range_flag) {
   extern __shared__ float sm[];
+  tce_amax_t amax = 0;
   float* ws = sm;                 // [48][C]  (k-major so that lanes read consecutive channels)
   float* taps = sm + 48 * C;      // [4 waves][48]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -208,11 +211,16 @@ __global__ void __launch_bounds__(256) patch_embed_kernel(const float* __restric
 #pragma unroll
       for (int j = 0; j < MAXC_PER_LANE; ++j) {
         const int c = lane + 64 * j;
-        if (c < C) out[tok * C + c] = (acc[j] - mean) * rstd * gamma[c] + beta[c];
+        if (c < C) {
+          const float o = (acc[j] - mean) * rstd * gamma[c] + beta[c];
+          amax = tce_amax1(amax, o);
+          out[tok * C + c] = o;
+        }
       }
     }
     __syncthreads();
   }
+  tce_range_report(range_flag, amax);
 }
 
 // Lane-per-token form (C % 8 == 0, C <= 152; TOK tokens x (C+4) floats of LDS): a lane gathers its
@@ -226,7 +234,8 @@ __global__ void __launch_bounds__(TOK) patch_embed_lane_kernel(const float* __re
                                                                const float* __restrict__ gamma,
                                                                const float* __restrict__ beta, float* __restrict__ out,
                                                                const int H, const int W, const int C, const float eps,
-                                                               const long long ntok, const int Hp, const int Wp) {
+                                                               const long long ntok, const int Hp, const int Wp,
+                                                               int* const range_flag) {
   extern __shared__ float sm[];
   const int pitch = C + 4;
   float* raw = sm;                      // [TOK][pitch]
@@ -299,6 +308,7 @@ __global__ void __launch_bounds__(TOK) patch_embed_lane_kernel(const float* __re
   const int c4n = C >> 2;
   const long long nvalid = min((long long)TOK, ntok - tok0);
   f32x4* o4 = reinterpret_cast<f32x4*>(out + tok0 * C);
+  tce_amax_t amax = 0;
   for (long long i = tid; i < nvalid * c4n; i += TOK) {
     const int r = (int)(i / c4n), c4 = (int)(i - (long long)r * c4n);
     const f32x4 v = *reinterpret_cast<const f32x4*>(raw + r * pitch + c4 * 4);
@@ -307,8 +317,10 @@ __global__ void __launch_bounds__(TOK) patch_embed_lane_kernel(const float* __re
     f32x4 o;
 #pragma unroll
     for (int e = 0; e < 4; ++e) o[e] = (v[e] - m) * rs * g4[e] + b4[e];
+    amax = tce_amax4(amax, o);
     o4[i] = o;
   }
+  tce_range_report(range_flag, amax);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -592,20 +604,23 @@ extern "C" int tce_patch_embed_f32(const float* frames, const float* w, const fl
     TCE_CHECK_LAUNCH("tce_patch_embed_f32");
     return TCE_OK;
   }
+  // widths the matrix-core kernel does not cover run the fp32 kernels on behalf of the split modes: their output feeds the
+  // same split products, so they report to the range guard as well (exact-fp32 mode has no contract: NULL)
+  int* const rf = tce_get_gemm_mode() != 0 ? tce_range_flag() : nullptr;
   // (C <= 120: the lane kernel's dynamic LDS stays below the 64 KB a launch may request without raising the function's
   // limit; wider embeddings take the generic kernel below.)
   if (C % 8 == 0 && C <= 120 && tce_aligned16(frames) && tce_aligned16(out) && tce_aligned16(gamma) && tce_aligned16(beta)) {
     constexpr int TOK = 128;  // tokens (= threads) per workgroup: 52 KiB of LDS at C = 96 -> three workgroups per CU
     const size_t lds = (size_t)(TOK * (C + 4) + 2 * TOK) * sizeof(float);
     hipLaunchKernelGGL((patch_embed_lane_kernel<8, TOK>), dim3(tce_cdiv(ntok, TOK)), dim3(TOK), lds, (hipStream_t)stream, frames, w, b,
-                       gamma, beta, out, H, W, C, eps, ntok, Hp, Wp);
+                       gamma, beta, out, H, W, C, eps, ntok, Hp, Wp, rf);
     TCE_CHECK_LAUNCH("tce_patch_embed_f32");
     return TCE_OK;
   }
   const int tpb = 64;
   const size_t smem = (size_t)(48 * C + 4 * 48) * sizeof(float);
   hipLaunchKernelGGL((patch_embed_kernel<4>), dim3(tce_cdiv(ntok, tpb)), dim3(256), smem, (hipStream_t)stream, frames, w,
-                     b, gamma, beta, out, T, H, W, C, eps, tpb);
+                     b, gamma, beta, out, T, H, W, C, eps, tpb, rf);
   TCE_CHECK_LAUNCH("tce_patch_embed_f32");
   return TCE_OK;
 }

@@ -15,6 +15,7 @@
 //   layer (fc1 -> fc2 needs no reduction launch); tce_mha_small64_splits_f32 reads q, k, v the same way.
 #include "common.h"
 #include "frag.h"
+#include "gemm_epilogue.h"
 #include "../../include/tce_rvos.h"
 
 namespace {
@@ -26,6 +27,7 @@ struct ThinArgs {
   float* ws;            // [K/256][M][N]
   long long ldx, ldw;
   int M, N, K, xsplits, act_x, single;
+  int* range_flag;      // tce_set_range_flag: PRO reports on the finished x (it is split here and never stored)
 };
 
 __device__ __forceinline__ int crow_t(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
@@ -65,6 +67,7 @@ __global__ void __launch_bounds__(256) thin_partials_kernel(const ThinArgs p) {
       }
     }
   if (PRO) {
+    tce_amax_t amax = 0;
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
       f32x4 bb = {0.f, 0.f, 0.f, 0.f};
@@ -79,9 +82,12 @@ __global__ void __launch_bounds__(256) thin_partials_kernel(const ThinArgs p) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) a[e] = tce_gelu(a[e]);
         }
+        amax = tce_amax4(amax, a);  // rows past M repeat row M - 1: valid values only
         xv[c][i] = a;
       }
     }
+    // consumer-side check: act_x(sum of the previous layer's planes + bias) goes straight into split8 below
+    tce_range_report(p.range_flag, amax);
   }
   f32x16 acc;
 #pragma unroll
@@ -146,6 +152,7 @@ extern "C" int tce_thin_partials_f32(const float* x, int64_t ldx, int32_t xsplit
   ThinArgs a;
   a.x = x; a.bias_x = bias_x; a.W = W; a.ws = ws; a.ldx = ldx; a.ldw = ldw; a.M = M; a.N = N; a.K = K;
   a.xsplits = xsplits; a.act_x = act_x; a.single = tce_gemm_single_pass();
+  a.range_flag = tce_range_flag();
   const dim3 grid(N / 32, tce_cdiv(M, 32), K / 256);
   if (a.single) {
     if (xsplits > 0) hipLaunchKernelGGL((thin_partials_kernel<true, true>), grid, dim3(256), 0, (hipStream_t)stream, a);
