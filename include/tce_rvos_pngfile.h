@@ -1,11 +1,8 @@
 /* tce_rvos_pngfile.h -- PNG-file stage entry points of libtce_rvos.so: the finished PNG file around every zlib stream that the
- * PNG-writing stage made on the device (include/tce_rvos_png.h, csrc/tce_rvos_vis.h): the IDAT chunk's CRC-32 and the chunk framing,
+ * PNG-writing stage made on the device (include/tce_rvos_png.h, include/tce_rvos_vis.h): the IDAT chunk's CRC-32 and the chunk framing,
  * so that what the host reads back is the file and no zlib.crc32 runs over the IDAT (tce_rvos_amd/png.py, framing="device").
  *
- * The header lives beside the sources, not in include/: the headers of include/ (_lib.HEADERS) and the stage headers
- * (_lib.STAGE_HEADERS) are closed sets that the project's tests hold to the symbol; this stage has a table of its own
- * (_lib.FILE_HEADERS) and access models of its own (hazard.FILE_MODELS, hazard.FILE_NOT_LAUNCHES), held to this header by
- * tests/test_png_file_cpu.py in the same way.
+ * The stage's host-side tests are in tests/test_png_file_cpu.py.
  *
  * THE FILE is one exact layout, so that a host restatement (tests/_png_file.py) and the kernel are compared byte for byte.  With
  * n = nbytes[p] clamped to [0, stream_stride], files[p, 0 .. file_bytes[p]) is, in order:
@@ -54,7 +51,7 @@
 #define TCE_RVOS_PNGFILE_H
 #include <stdint.h>
 
-#include "../../include/tce_rvos.h"
+#include "tce_rvos.h"
 
 #ifdef __cplusplus
 extern "C" {

@@ -2,10 +2,7 @@
  * evaluation (engine.py:97-161) does with the outputs of a forward -- the box and mask post-processors (models/postprocessors.py:
  * 58-155) for a group of samples, and the generalised IoU behind precision@k (datasets/refexp_eval.py:37-82, util/box_ops.py:44-81).
  *
- * The header lives beside the sources, not in include/: the headers of include/ (_lib.HEADERS), the stage headers
- * (_lib.STAGE_HEADERS) and the PNG-file header (_lib.FILE_HEADERS) are closed sets that the project's tests hold to the symbol; this
- * stage has a table of its own (_lib.REFEXP_HEADERS) and access models of its own (hazard.REFEXP_MODELS), held to this header by
- * tests/test_refexp_cpu.py in the same way.  The ABI version is unchanged.
+ * The stage's host-side tests are in tests/test_refexp_cpu.py.
  *
  * Conventions of include/tce_rvos_eval.h: device pointers to contiguous memory, the caller owns all of it, every entry takes the
  * hipStream_t to launch on, is asynchronous, allocates nothing, never synchronises (legal inside hipGraph capture), returns
@@ -16,7 +13,7 @@
 #define TCE_RVOS_REFEXP_H
 #include <stdint.h>
 
-#include "../../include/tce_rvos.h"
+#include "tce_rvos.h"
 
 #ifdef __cplusplus
 extern "C" {

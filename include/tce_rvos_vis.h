@@ -1,9 +1,7 @@
 /* tce_rvos_vis.h -- visualisation-stage entry points of libtce_rvos.so: the --visualize images of the reference's inference drivers
  * (the decoded frame with box, reference point and mask tint drawn on it) made on the device, and their RGB PNG streams.
  *
- * The header lives beside the sources, not in include/: the headers of include/ and their binding tables (_lib.HEADERS) are a
- * closed set that the project's tests hold to the symbol; this stage has a table of its own (_lib.STAGE_HEADERS) and access models
- * of its own (hazard.STAGE_MODELS), held to this header by tests/test_vis_cpu.py in the same way.
+ * The stage's host-side tests are in tests/test_vis_cpu.py.
  *
  * Conventions of the other stage headers: device pointers, the caller owns all memory, every entry takes the hipStream_t to launch
  * on, is asynchronous, allocates nothing, never synchronises (legal inside hipGraph capture), returns 0 = launched / <0 = rejected
@@ -13,8 +11,8 @@
 #define TCE_RVOS_VIS_H
 #include <stdint.h>
 
-#include "../../include/tce_rvos.h"
-#include "../../include/tce_rvos_png.h"
+#include "tce_rvos.h"
+#include "tce_rvos_png.h"
 
 #ifdef __cplusplus
 extern "C" {

@@ -65,12 +65,19 @@ class LabelObj(C.Structure):
     _fields_ = [("logits", c_f), ("masks", c_f)]
 
 
+A2D_GROUP_MAX = 16  # TCE_A2D_GROUP_MAX: samples per tce_a2d_group_masks_u8 call
+
+
 class A2dGroupSample(C.Structure):  # tceA2dGroupSample (include/tce_rvos_eval.h)
     _fields_ = [("masks", c_f), ("logits", c_f), ("out", c_f), ("scores", c_f), ("fh", i32), ("fw", i32), ("H0", i32), ("W0", i32),
                 ("logit_stride", i32), ("reserved", i32)]
 
 
-class RefexpSample(C.Structure):  # tceRefexpSample (csrc/tce_rvos_refexp.h)
+REFEXP_GROUP_MAX = 16   # TCE_REFEXP_GROUP_MAX: samples per tce_refexp_group_u8 call
+REFEXP_MAX_CAND = 1024  # TCE_REFEXP_MAX_CAND: Q*K candidates per sample
+
+
+class RefexpSample(C.Structure):  # tceRefexpSample (include/tce_rvos_refexp.h)
     _fields_ = [("logits", c_f), ("boxes_in", c_f), ("masks", c_f), ("scores", c_f), ("order", c_f), ("boxes_out", c_f), ("out", c_f),
                 ("fh", i32), ("fw", i32), ("H0", i32), ("W0", i32)]
 
@@ -194,7 +201,6 @@ VIDEO_SIGNATURES = {
 }
 
 # include/tce_rvos_eval.h: evaluation-stage entry points (the A2D-Sentences / JHMDB-Sentences post-processor)
-A2D_GROUP_MAX = 16  # TCE_A2D_GROUP_MAX
 EVAL_SIGNATURES = {
     # masks [N,h,w], out [N,H0,W0], N, h, w, fh, fw, H0, W0, threshold
     "tce_a2d_masks_u8": (i32, [c_f, c_f, i32, i32, i32, i32, i32, i32, i32, f32, c_f]),
@@ -228,11 +234,7 @@ PNG_SIGNATURES = {
     "tce_png_deflate_dyn_u8": (i32, [c_f, c_f, c_f, c_f, i32, i32, i32, i32, i32, c_f]),
 }
 
-HEADERS = {"tce_rvos.h": SIGNATURES, "tce_rvos_debug.h": DEBUG_SIGNATURES, "tce_rvos_video.h": VIDEO_SIGNATURES,
-           "tce_rvos_eval.h": EVAL_SIGNATURES, "tce_rvos_score.h": SCORE_SIGNATURES, "tce_rvos_png.h": PNG_SIGNATURES}
-
-# csrc/tce_rvos_vis.h: visualisation-stage entry points (the --visualize images drawn on the device and their RGB PNG streams).  The
-# stage's header lives beside the sources and its table here, outside HEADERS: the headers of include/ are a closed set.
+# include/tce_rvos_vis.h: visualisation-stage entry points (the --visualize images drawn on the device and their RGB PNG streams)
 VIS_SIGNATURES = {
     # frames [N,H0,W0,3] u8, out, masks [L,N,H0,W0] u8 | NULL, boxes [L,N,4] | NULL, points [L,N,2] | NULL, colors [L,3] u8, L, N, H0, W0
     "tce_vis_overlay_u8": (i32, [c_f, c_f, c_f, c_f, c_f, c_f, i32, i32, i32, i32, c_f]),
@@ -242,11 +244,8 @@ VIS_SIGNATURES = {
     "tce_png_deflate_rows_u8": (i32, [c_f, c_f, c_f, c_f, i32, i32, i32, i32, c_f]),
 }
 
-# header (relative to the package's csrc/) -> its table: EVERY symbol of its header and no other, as HEADERS (tests check this)
-STAGE_HEADERS = {"tce_rvos_vis.h": VIS_SIGNATURES}
-
-# csrc/tce_rvos_pngfile.h: PNG-file stage entry points (the IDAT chunk's CRC-32 and the chunk framing around the streams, on the
-# device).  A third set beside HEADERS and STAGE_HEADERS, which are both closed; held to its header in the same way.
+# include/tce_rvos_pngfile.h: PNG-file stage entry points (the IDAT chunk's CRC-32 and the chunk framing around the streams, on the
+# device)
 PNGFILE_SIGNATURES = {
     "tce_png_file_bound": (i64, [i32, i64]),  # head_bytes, stream_stride
     "tce_png_file_ws_bytes": (i64, [i32, i64]),  # P, stream_stride
@@ -254,20 +253,21 @@ PNGFILE_SIGNATURES = {
     # P, stream_stride, file_stride
     "tce_png_file_u8": (i32, [c_f, c_f, c_f, i32, c_f, c_f, c_f, i32, i64, i64, c_f]),
 }
-FILE_HEADERS = {"tce_rvos_pngfile.h": PNGFILE_SIGNATURES}
 
-# csrc/tce_rvos_refexp.h: RefCOCO evaluation-stage entry points (the box / mask post-processors for a group of samples, the
-# generalised IoU behind precision@k).  A fourth set beside HEADERS, STAGE_HEADERS and FILE_HEADERS, which are all closed; held to its
-# header in the same way.
-REFEXP_GROUP_MAX = 16   # TCE_REFEXP_GROUP_MAX
-REFEXP_MAX_CAND = 1024  # TCE_REFEXP_MAX_CAND
+# include/tce_rvos_refexp.h: RefCOCO evaluation-stage entry points (the box / mask post-processors for a group of samples, the
+# generalised IoU behind precision@k)
 REFEXP_SIGNATURES = {
     # samples (host table), B, Q, K, h, w, threshold
     "tce_refexp_group_u8": (i32, [C.POINTER(RefexpSample), i32, i32, i32, i32, i32, f32, c_f]),
     # boxes [M,Q,4], gt [M,4], giou [M,Q], best [M,Q], M, Q
     "tce_refexp_giou_f32": (i32, [c_f, c_f, c_f, c_f, i32, i32, c_f]),
 }
-REFEXP_HEADERS = {"tce_rvos_refexp.h": REFEXP_SIGNATURES}
+
+# header of include/ -> its table.  The set is closed over include/: a header there without a row here, or a row without its header,
+# fails tests/test_host_cpu.py, so a new stage adds its header, its table and this row
+HEADERS = {"tce_rvos.h": SIGNATURES, "tce_rvos_debug.h": DEBUG_SIGNATURES, "tce_rvos_video.h": VIDEO_SIGNATURES,
+           "tce_rvos_eval.h": EVAL_SIGNATURES, "tce_rvos_score.h": SCORE_SIGNATURES, "tce_rvos_png.h": PNG_SIGNATURES,
+           "tce_rvos_vis.h": VIS_SIGNATURES, "tce_rvos_pngfile.h": PNGFILE_SIGNATURES, "tce_rvos_refexp.h": REFEXP_SIGNATURES}
 
 _LIB = None
 
@@ -289,7 +289,7 @@ def lib():
             warnings.warn(f"tce_rvos_amd: GPU_MAX_HW_QUEUES={hwq} is set; the HIP runtime's default (4) is the only value this "
                           f"launch program runs well with (1-3 crash the runtime, 5-16 double the clip time)", RuntimeWarning)
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in [kv for table in list(HEADERS.values()) + list(STAGE_HEADERS.values()) + list(FILE_HEADERS.values()) + list(REFEXP_HEADERS.values()) for kv in table.items()]:
+        for name, (res, args) in [kv for table in HEADERS.values() for kv in table.items()]:
             fn = getattr(l, name)  # AttributeError if the symbol is absent
             fn.restype, fn.argtypes = res, args
         _LIB = l

@@ -4,7 +4,7 @@
 // RGB images (at the end of the file): a row filter chosen per row, then the second encoding over rows that are filtered already.
 #include "common.h"
 #include "../../include/tce_rvos_png.h"
-#include "tce_rvos_vis.h"
+#include "../../include/tce_rvos_vis.h"
 
 namespace {
 

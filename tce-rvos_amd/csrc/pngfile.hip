@@ -2,7 +2,7 @@
 // their place, the IDAT chunk's CRC-32, head, length, type and IEND -- in two launches.  Byte and table kernels: bound by LDS traffic
 // and by the streams' bytes going through once, not by arithmetic.
 #include "common.h"
-#include "tce_rvos_pngfile.h"
+#include "../../include/tce_rvos_pngfile.h"
 
 namespace {
 

@@ -4,7 +4,7 @@
 // generalised IoU with its running maximum behind precision@k (util/box_ops.py:44-81, datasets/refexp_eval.py:65-67).
 #include "common.h"
 #include "mask_planes.h"
-#include "tce_rvos_refexp.h"
+#include "../../include/tce_rvos_refexp.h"
 
 namespace {
 

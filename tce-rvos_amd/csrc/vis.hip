@@ -1,7 +1,7 @@
 // Visualisation overlay (csrc/tce_rvos_vis.h, tce_vis_overlay_u8): the decoded frame with box outline, reference cross and mask
 // tint of up to 16 layers, one pass over the pixels.  Memory-bound: 3 + L bytes read, 3 written per pixel.
 #include "common.h"
-#include "tce_rvos_vis.h"
+#include "../../include/tce_rvos_vis.h"
 
 namespace {
 

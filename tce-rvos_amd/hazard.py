@@ -9,10 +9,7 @@ checks it statically.
 
   * every C-ABI launch (`lib().tce_*`) is intercepted: the stream it was issued on and -- from the same pointers and sizes
     the kernel receives -- the byte ranges it reads and writes (`MODELS`: one access model for every launching entry point
-    of every header of include/ (_lib.HEADERS), the drivers' output stages included, `STAGE_MODELS` for the stage headers beside
-    the sources (_lib.STAGE_HEADERS), `FILE_MODELS` / `FILE_NOT_LAUNCHES` for the PNG-file stage (_lib.FILE_HEADERS), `REFEXP_MODELS` for
-    the RefCOCO evaluation stage (_lib.REFEXP_HEADERS); an entry
-    point that is neither modelled
+    of every header of include/ (_lib.HEADERS), the drivers' output stages included; an entry point that is neither modelled
     nor listed in `NOT_LAUNCHES` is an error, so coverage cannot rot);
   * every event record / wait (torch's `wait_stream` is `wait_event(record_event())`) and every host synchronisation is
     intercepted and turned into vector clocks: launch A happens-before launch B iff B's clock has seen A's tick;
@@ -423,6 +420,43 @@ def _a2d_group_masks(a):
     return rd, wr
 
 
+def _png_file(a):
+    """streams, nbytes, head, head_bytes, files, file_bytes, ws, P, stream_stride, file_stride: how far a stream row is read and a
+    file row written is device data (nbytes), so the rows are named whole (a file row: its tce_png_file_bound bytes), as
+    _png_deflate names its streams; ws is written by the first launch and read by the second"""
+    streams, nbytes, head, head_bytes, files, file_bytes, ws, P, sstride, fstride = a[:10]
+    L = _lib.lib_raw()
+    wsb = dense(_p(ws), L.tce_png_file_ws_bytes(P, sstride))
+    return ([dense(_p(streams), P * sstride), dense(_p(nbytes), P * 4), dense(_p(head), head_bytes), wsb],
+            [strided(_p(files), L.tce_png_file_bound(head_bytes, sstride), (P, fstride)), dense(_p(file_bytes), P * 4), wsb])
+
+
+def _refexp_group(a):
+    """samples (host table), B, Q, K, h, w: per sample its Q*K logits and Q boxes are read; any of its Q mask planes can be a ranked
+    one, so all are named (none for a box-only sample: masks or out NULL, nothing is written through out then); scores, order and
+    boxes_out are written whole; order is written by the first launch and read by the second (the write covers both).  A ranked
+    sample (logits NULL) has no first launch: its order is read, and of the outputs only out is written"""
+    samples, B, Q, K, h, w = a[:6]
+    rd, wr = [], []
+    for b in range(B):
+        e = samples[b]
+        if _p(e.logits):
+            rd += [dense(_p(e.logits), Q * K * F), dense(_p(e.boxes_in), Q * 4 * F)]
+            wr += [dense(_p(e.scores), Q * F), dense(_p(e.order), Q * 4), dense(_p(e.boxes_out), Q * 4 * F)]
+        else:
+            rd.append(dense(_p(e.order), Q * 4))
+        if _p(e.masks) and _p(e.out):
+            rd.append(dense(_p(e.masks), Q * h * w * F))
+            wr.append(dense(_p(e.out), Q * e.H0 * e.W0))
+    return rd, wr
+
+
+def _refexp_giou(a):
+    """boxes, gt, giou, best, M, Q: everything read and written whole"""
+    boxes, gt, giou, best, M, Q = a[:6]
+    return [dense(_p(boxes), M * Q * 4 * F), dense(_p(gt), M * 4 * F)], [dense(_p(giou), M * Q * F), dense(_p(best), M * Q * F)]
+
+
 MODELS = {
     "tce_gemm_f32": lambda a: _gemm(_st(a[0])),
     "tce_gemm_splitk_f32": lambda a: _gemm(_st(a[0]), ws=a[2], splits=a[1]),
@@ -573,61 +607,13 @@ MODELS = {
     "tce_png_deflate_u8": _png_deflate,
     "tce_png_deflate_dyn_u8": _png_deflate,
     "tce_a2d_group_masks_u8": _a2d_group_masks,
-}
-
-# The launching entry points of the stage headers beside the sources (_lib.STAGE_HEADERS): one model each, as MODELS for include/.
-STAGE_MODELS = {
     "tce_vis_overlay_u8": _vis_overlay,
     "tce_png_filter_rgb_u8": _png_filter_rgb,
     "tce_png_deflate_rows_u8": _png_deflate_rows,
+    "tce_png_file_u8": _png_file,
+    "tce_refexp_group_u8": _refexp_group,
+    "tce_refexp_giou_f32": _refexp_giou,
 }
-
-
-def _png_file(a):
-    """streams, nbytes, head, head_bytes, files, file_bytes, ws, P, stream_stride, file_stride: how far a stream row is read and a
-    file row written is device data (nbytes), so the rows are named whole (a file row: its tce_png_file_bound bytes), as
-    _png_deflate names its streams; ws is written by the first launch and read by the second"""
-    streams, nbytes, head, head_bytes, files, file_bytes, ws, P, sstride, fstride = a[:10]
-    L = _lib.lib_raw()
-    wsb = dense(_p(ws), L.tce_png_file_ws_bytes(P, sstride))
-    return ([dense(_p(streams), P * sstride), dense(_p(nbytes), P * 4), dense(_p(head), head_bytes), wsb],
-            [strided(_p(files), L.tce_png_file_bound(head_bytes, sstride), (P, fstride)), dense(_p(file_bytes), P * 4), wsb])
-
-
-# The PNG-file stage (_lib.FILE_HEADERS): a third set beside MODELS / NOT_LAUNCHES and STAGE_MODELS, which are closed.
-FILE_MODELS = {"tce_png_file_u8": _png_file}
-FILE_NOT_LAUNCHES = {"tce_png_file_bound", "tce_png_file_ws_bytes"}
-
-
-def _refexp_group(a):
-    """samples (host table), B, Q, K, h, w: per sample its Q*K logits and Q boxes are read; any of its Q mask planes can be a ranked
-    one, so all are named (none for a box-only sample: masks or out NULL, nothing is written through out then); scores, order and
-    boxes_out are written whole; order is written by the first launch and read by the second (the write covers both).  A ranked
-    sample (logits NULL) has no first launch: its order is read, and of the outputs only out is written"""
-    samples, B, Q, K, h, w = a[:6]
-    rd, wr = [], []
-    for b in range(B):
-        e = samples[b]
-        if _p(e.logits):
-            rd += [dense(_p(e.logits), Q * K * F), dense(_p(e.boxes_in), Q * 4 * F)]
-            wr += [dense(_p(e.scores), Q * F), dense(_p(e.order), Q * 4), dense(_p(e.boxes_out), Q * 4 * F)]
-        else:
-            rd.append(dense(_p(e.order), Q * 4))
-        if _p(e.masks) and _p(e.out):
-            rd.append(dense(_p(e.masks), Q * h * w * F))
-            wr.append(dense(_p(e.out), Q * e.H0 * e.W0))
-    return rd, wr
-
-
-def _refexp_giou(a):
-    """boxes, gt, giou, best, M, Q: everything read and written whole"""
-    boxes, gt, giou, best, M, Q = a[:6]
-    return [dense(_p(boxes), M * Q * 4 * F), dense(_p(gt), M * 4 * F)], [dense(_p(giou), M * Q * F), dense(_p(best), M * Q * F)]
-
-
-# The RefCOCO evaluation stage (_lib.REFEXP_HEADERS): a fourth set, every entry of it launches.
-REFEXP_MODELS = {"tce_refexp_group_u8": _refexp_group, "tce_refexp_giou_f32": _refexp_giou}
-
 
 # Entry points that launch nothing (queries, process switches, graph helpers, tuning aids): passed through.
 NOT_LAUNCHES = {"tce_abi_version", "tce_last_error", "tce_gemm_select_tile", "tce_gemm_select_tile_ex", "tce_set_gemm_mode", "tce_set_gemm_mode_thread",
@@ -636,7 +622,7 @@ NOT_LAUNCHES = {"tce_abi_version", "tce_last_error", "tce_gemm_select_tile", "tc
                 "tce_rowlin_packed_bytes", "tce_conv3x3_packed_bytes", "tce_conv3x3_split_ws_floats",
                 "tce_conv3x3_split_pieces", "tce_conv3x3_split_kstep", "tce_swin_attn_packed_bytes", "tce_thin_linear_splits", "tce_graph_begin", "tce_graph_end", "tce_graph_launch",
                 "tce_graph_destroy", "tce_graph_group", "tce_rle_ws_bytes", "tce_jf_ws_bytes", "tce_rle_decode_ws_bytes", "tce_mask_overlap_ws_bytes",
-                "tce_png_stream_bound", "tce_png_ws_bytes"} | set(_lib.DEBUG_SIGNATURES)
+                "tce_png_stream_bound", "tce_png_ws_bytes", "tce_png_file_bound", "tce_png_file_ws_bytes"} | set(_lib.DEBUG_SIGNATURES)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -774,9 +760,9 @@ class _LibProxy:
 
     def __getattr__(self, name):
         fn = getattr(self._real, name)
-        if name in NOT_LAUNCHES or name in FILE_NOT_LAUNCHES or not name.startswith("tce_"):
+        if name in NOT_LAUNCHES or not name.startswith("tce_"):
             return fn
-        model = MODELS.get(name) or STAGE_MODELS.get(name) or FILE_MODELS.get(name) or REFEXP_MODELS.get(name)
+        model = MODELS.get(name)
         if model is None:
             raise RuntimeError(f"hazard checker: no access model for {name} (add one to hazard.MODELS)")
         rec, dry = self._rec, self._dry

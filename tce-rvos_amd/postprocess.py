@@ -6,7 +6,7 @@ run counts and the used prefix of the run lengths only, and packs them into the 
 (rle_to_string).
 
 The reference's image-setting post-processors, which its RefCOCO / RefCOCO+ / RefCOCOg evaluation calls (postprocessors.py:58-155,
-engine.py:113-120), are PostProcess and PostProcessSegm below, on ops.refexp_group (csrc/tce_rvos_refexp.h); they are reached through
+engine.py:113-120), are PostProcess and PostProcessSegm below, on ops.refexp_group (include/tce_rvos_refexp.h); they are reached through
 build_refexp_postprocessors.  build_postprocessors is unchanged and still hands out a stub for everything but A2D / JHMDB.
 """
 import numpy as np

@@ -1,7 +1,7 @@
 """RefCOCO / RefCOCO+ / RefCOCOg precision@k of boxes that stay on the GPU: what the reference's RefExpEvaluator does with the
 results of PostProcess (datasets/refexp_eval.py:37-82, fed by engine.py:122-126).
 
-Per update call one launch (ops.refexp_giou, csrc/tce_rvos_refexp.h): the generalised IoU of every predicted box of every image of
+Per update call one launch (ops.refexp_giou, include/tce_rvos_refexp.h): the generalised IoU of every predicted box of every image of
 the call against the image's one ground-truth box, and its running maximum over the boxes in score order.  The running maxima
 `best [Q]` of every image wait in a device slab (one slab per box count Q: a model's queries give one); state() reads a slab
 back once.  What follows is host arithmetic on those floats:

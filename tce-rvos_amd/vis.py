@@ -4,7 +4,7 @@ reference point and the mask tint on it.
     inference_ytvos.py:325-351, inference_mevis.py (the same block)   -> overlay_expression(frames_u8, result, color)
     inference_davis.py:269-291                                        -> overlay_objects(frames_u8, boxes, colors)
 
-One launch per call (ops.vis_overlay; csrc/tce_rvos_vis.h states the per-pixel rule, which is Pillow's
+One launch per call (ops.vis_overlay; include/tce_rvos_vis.h states the per-pixel rule, which is Pillow's
 ImageDraw.rectangle(width=2) and ImageDraw.line(width=4) and the reference's numpy blend, byte for byte, except for boxes thinner
 than 2 pixels, which are drawn as the filled rectangle of their integer corners).  png.rgb_pngs turns the result into files without
 the pixels leaving the device.

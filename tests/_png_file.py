@@ -1,4 +1,4 @@
-"""Host restatement of the PNG-file stage (csrc/tce_rvos_pngfile.h): THE FILE around a zlib stream, built from png.chunk, and the
+"""Host restatement of the PNG-file stage (include/tce_rvos_pngfile.h): THE FILE around a zlib stream, built from png.chunk, and the
 register-level pieces of the header's two identities -- raw (the CRC register from a zero start, no final xor), mul (the product in
 GF(2)[x] mod G) and X (x^k mod G), all in the reflected representation -- in plain Python, with the combination the two launches
 make (segment_raw, combined_crc) restated from them."""

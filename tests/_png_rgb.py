@@ -1,4 +1,4 @@
-"""Host restatement of the RGB half of the PNG stage (csrc/tce_rvos_vis.h): the per-row filter choice of
+"""Host restatement of the RGB half of the PNG stage (include/tce_rvos_vis.h): the per-row filter choice of
 tce_png_filter_rgb_u8 and the stream of tce_png_deflate_rows_u8.  The filters are written from section 9 of the PNG specification,
 one byte at a time; the blocks are tests/_png_dyn.py's (strip_block takes a strip's bytes as they are).  It shares nothing with the
 kernel or with tce_rvos_amd/png.py."""

@@ -1,4 +1,4 @@
-"""Host restatement of the overlay rule of tce_vis_overlay_u8 (csrc/tce_rvos_vis.h) in numpy, and the same layers rendered
+"""Host restatement of the overlay rule of tce_vis_overlay_u8 (include/tce_rvos_vis.h) in numpy, and the same layers rendered
 with Pillow the way the reference's --visualize block draws them (ImageDraw.rectangle(width=2), two ImageDraw.line(width=4), the
 numpy blend).  Written from the rule's text; it shares nothing with the kernel or with tce_rvos_amd/vis.py."""
 import numpy as np

@@ -233,11 +233,12 @@ def test_case_table_covers_exactly_the_modelled_entry_points():
         names[c.entry] = names.get(c.entry, 0) + 1
     # the main header's models; the output stages' are held to their kernels by their own tests (test_label_objects_gpu.py,
     # test_a2d_post_gpu.py, test_jf_score_gpu.py, test_a2d_score_gpu.py, test_png_gpu.py, test_png_dyn_gpu.py,
-    # test_a2d_group_post_gpu.py)
+    # test_a2d_group_post_gpu.py, test_vis_overlay_gpu.py, test_png_rgb_gpu.py, test_png_file_gpu.py, test_refexp_gpu.py)
     main = set(hazard.MODELS) & set(_lib.SIGNATURES)
     assert set(hazard.MODELS) - main == {"tce_label_objects_u8", "tce_a2d_masks_u8", "tce_rle_counts_u32", "tce_jf_counts_i32",
                                          "tce_rle_decode_u8", "tce_mask_overlap_i32", "tce_png_deflate_u8", "tce_png_deflate_dyn_u8",
-                                         "tce_a2d_group_masks_u8"}
+                                         "tce_a2d_group_masks_u8", "tce_vis_overlay_u8", "tce_png_filter_rgb_u8",
+                                         "tce_png_deflate_rows_u8", "tce_png_file_u8", "tce_refexp_group_u8", "tce_refexp_giou_f32"}
     assert set(names) == main, (sorted(main - set(names)), sorted(set(names) - main))
     few = {n: k for n, k in names.items() if k < 2}
     assert not few, f"entry points with fewer than two cases: {few}"

@@ -35,6 +35,10 @@ HEADER_CASES = [
      {"tce_jf_ws_bytes", "tce_rle_decode_ws_bytes", "tce_mask_overlap_ws_bytes"}, ("score.hip", "a2d_score.hip")),
     ("tce_rvos_png.h", {"tce_png_stream_bound", "tce_png_ws_bytes", "tce_png_deflate_u8", "tce_png_deflate_dyn_u8"},
      {"tce_png_stream_bound", "tce_png_ws_bytes"}, ("png.hip",)),
+    ("tce_rvos_vis.h", {"tce_vis_overlay_u8", "tce_png_filter_rgb_u8", "tce_png_deflate_rows_u8"}, set(), ("vis.hip", "png.hip")),
+    ("tce_rvos_pngfile.h", {"tce_png_file_bound", "tce_png_file_ws_bytes", "tce_png_file_u8"},
+     {"tce_png_file_bound", "tce_png_file_ws_bytes"}, ("pngfile.hip",)),
+    ("tce_rvos_refexp.h", {"tce_refexp_group_u8", "tce_refexp_giou_f32"}, set(), ("refexp.hip",)),
 ]
 
 
@@ -44,6 +48,7 @@ def test_header_symbols_bound_exported_and_modelled(built_lib, header, symbols, 
     from tce_rvos_amd import _lib, hazard
     from tce_rvos_amd import build as b
     assert [c[0] for c in HEADER_CASES] == list(_lib.HEADERS) and set(os.listdir(os.path.join(ROOT, "include"))) == set(_lib.HEADERS)
+    assert not [f for f in os.listdir(b.CSRC) if re.fullmatch(r"tce_rvos_.*\.h", f)]  # no entry-point header beside the sources
     table, declared = _lib.HEADERS[header], _declared(header)
     assert declared == set(table), declared ^ set(table)
     assert symbols is None or declared == symbols

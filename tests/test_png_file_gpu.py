@@ -1,4 +1,4 @@
-"""PNG-file stage on the GPU: tce_png_file_u8 (csrc/tce_rvos_pngfile.h) byte for byte against its restatement (tests/_png_file.py)
+"""PNG-file stage on the GPU: tce_png_file_u8 (include/tce_rvos_pngfile.h) byte for byte against its restatement (tests/_png_file.py)
 at every length around a piece and a segment, with random, all-zero and all-0xFF data, streams and files off every alignment, one
 long row; png.mask_pngs / label_pngs / rgb_pngs with framing="device" against framing="host" and Pillow; the access model against
 the bytes the launches touch; rejected arguments; the call replayed from a graph."""

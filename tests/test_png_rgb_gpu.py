@@ -1,4 +1,4 @@
-"""RGB half of the PNG stage on the GPU: tce_png_filter_rgb_u8 and tce_png_deflate_rows_u8 (csrc/tce_rvos_vis.h) byte for byte
+"""RGB half of the PNG stage on the GPU: tce_png_filter_rgb_u8 and tce_png_deflate_rows_u8 (include/tce_rvos_vis.h) byte for byte
 against their restatement (tests/_png_rgb.py, the blocks of tests/_png_dyn.py); the all-literal case inside the stream bound, no
 stream above its fixed-code cost; every file decoded by zlib and un-filtering; images encoded together equal images encoded
 alone; images and rows off every alignment; rejected arguments; the access models against the bytes the launches touch."""

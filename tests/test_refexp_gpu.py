@@ -1,4 +1,4 @@
-"""GPU: the RefCOCO evaluation stage (csrc/tce_rvos_refexp.h, ops.refexp_group / ops.refexp_giou, postprocess.PostProcess /
+"""GPU: the RefCOCO evaluation stage (include/tce_rvos_refexp.h, ops.refexp_group / ops.refexp_giou, postprocess.PostProcess /
 PostProcessSegm, refexp_score.RefExpScorer, refexp.run_images) against the reference's own classes (tests/golden/refexp_cases.npz),
 the per-sample masks entry, the tie rule, the candidate cap, a group larger than a launch table, the access models
 (tests/_footprint.py) and, end to end, the one-image path.

@@ -142,30 +142,3 @@ def test_vis_ops_reject_what_is_not_on_the_gpu():
     with pytest.raises(ValueError):
         vis.overlay_objects(f, torch.zeros(2, 4), [[1, 2, 3]])
 
-
-def test_stage_header_symbols_bound_exported_and_modelled():
-    """csrc/tce_rvos_vis.h against its binding table (_lib.STAGE_HEADERS), the built library and the hazard checker's STAGE_MODELS:
-    what tests/test_host_cpu.py holds the headers of include/ to."""
-    import ctypes
-    import re
-    from tce_rvos_amd import _lib, hazard
-    from tce_rvos_amd import build as b
-    lib_path = b.build(verbose=False)
-    assert list(_lib.STAGE_HEADERS) == ["tce_rvos_vis.h"]
-    path = os.path.join(b.CSRC, "tce_rvos_vis.h")
-    declared = set(re.findall(r"\b(tce_[a-z0-9_]+)\s*\(", open(path).read()))
-    table = _lib.STAGE_HEADERS["tce_rvos_vis.h"]
-    assert declared == set(table) == {"tce_vis_overlay_u8", "tce_png_filter_rgb_u8", "tce_png_deflate_rows_u8"}
-    every = set().union(*_lib.HEADERS.values())
-    assert not (declared & every)                                    # a symbol lives in one header and in one table
-    for name in sorted(os.listdir(os.path.join(HERE, "..", "include"))):
-        assert not (declared & set(re.findall(r"\b(tce_[a-z0-9_]+)\s*\(", open(os.path.join(HERE, "..", "include", name)).read())))
-    l, bound = ctypes.CDLL(lib_path), _lib.lib()
-    for name, (res, args) in table.items():
-        assert hasattr(l, name), name
-        fn = getattr(bound, name)
-        assert fn.restype is res and list(fn.argtypes) == args, name
-    assert set(hazard.STAGE_MODELS) == declared                      # every entry of the stage launches and is modelled
-    assert not (set(hazard.STAGE_MODELS) & set(hazard.MODELS)) and not (declared & hazard.NOT_LAUNCHES)
-    assert os.path.realpath(path) in {os.path.realpath(d) for d in b.dependencies()}   # every object is rebuilt when it changes
-    assert "vis.hip" in b.SOURCES and "png.hip" in b.SOURCES

@@ -1,4 +1,4 @@
-"""Overlay stage on the GPU: tce_vis_overlay_u8 (csrc/tce_rvos_vis.h) byte for byte against the Pillow-rendered fixture
+"""Overlay stage on the GPU: tce_vis_overlay_u8 (include/tce_rvos_vis.h) byte for byte against the Pillow-rendered fixture
 (tests/golden/vis_overlay_cases.npz) and against the rule's restatement (tests/_vis.py) where Pillow is not the rule (thin boxes);
 every optional pointer NULL in turn; frames and out off every alignment, W0 = 1 and H0 = 1; rejected arguments; vis.py's two
 functions; the access model against the bytes the launch touches."""

@@ -1,5 +1,5 @@
 """PNG files with the chunk framing and the IDAT's CRC-32 made by the host (framing="host": zlib.crc32 over every IDAT, the join)
-against the same files with both made on the device (framing="device": ops.png_file, csrc/tce_rvos_pngfile.h), on the same GPU in the
+against the same files with both made on the device (framing="device": ops.png_file, include/tce_rvos_pngfile.h), on the same GPU in the
 same process.  The comparison is host framing against device framing, never the code under test against itself.
 
   frames    one chunk of 32 frames at 720 x 1280 and at 480 x 854, tools/vis_bench.py's recipe: smooth noise plus moving blobs plus a
