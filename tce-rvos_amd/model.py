@@ -1455,7 +1455,7 @@ def build_tokenizer(args=None):
 
 
 class _Stub(nn.Module):
-    """Stands where the reference returns its training criterion / COCO post-processors (out of scope)."""
+    """Stands where the reference returns a piece that is out of scope (the post-processor tests use it)."""
 
     def __init__(self, what):
         super().__init__()
@@ -1469,5 +1469,6 @@ def build_model(args):
     """models/__init__.py:4-5 -> tce_rvos.build :638-719.  Returns (model, criterion, postprocessors)."""
     cfg = config_from_args(args)
     model = ReferFormer(cfg, args=args)
+    from .criterion import build_criterion  # models/tce_rvos.py:686-715 (forward values; loads no library until it is called)
     from .postprocess import build_postprocessors  # models/tce_rvos.py:717-719
-    return model, _Stub("SetCriterion"), build_postprocessors(args, getattr(args, "dataset_file", None))
+    return model, build_criterion(args), build_postprocessors(args, getattr(args, "dataset_file", None))
