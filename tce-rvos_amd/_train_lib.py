@@ -33,6 +33,12 @@ TRAIN_SIGNATURES = {
     # parts [B,6] f64, losses [6], B, T, Q, K, h, w, consts (host)
     "tce_criterion_match_losses_f32": (i32, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, i32, i32, i32, i32, i32,
                                              i32, C.POINTER(CriterionConsts), c_f]),
+    # pred, tgt u8, sums f64, st f64, index i32, num_boxes, gl [6], grad [B,T,Q,h,w], B, T, Q, h, w, H, W, alpha
+    "tce_criterion_mask_grad_f32": (i32, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, i32, i32, i32, i32, i32, i32, i32, f32, c_f]),
+    # logits, pred_boxes, visible | NULL, labels i64, boxes, valid i32, index i32, num_boxes, gl [6], g_logits | NULL, g_boxes | NULL,
+    # g_visible | NULL, B, T, Q, K, consts (host)
+    "tce_criterion_head_grads_f32": (i32, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, i32, i32, i32, i32,
+                                           C.POINTER(CriterionConsts), c_f]),
 }
 
 _LIB = None

@@ -1,6 +1,7 @@
-"""The reference's SetCriterion (models/criterion.py) and the one-target matcher it calls (models/matcher.py), forward values only,
-on the GPU: two entry points of libtce_rvos_train.so per decoder layer (train/tce_rvos_train.h).  No gradient of the
-losses is built; an input that requires grad is rejected.  Importing this module loads no library."""
+"""The reference's SetCriterion (models/criterion.py) and the one-target matcher it calls (models/matcher.py) on the GPU: two entry
+points of libtce_rvos_train.so per decoder layer (train/tce_rvos_train.h).  Forward values only by default: an input
+that requires grad is rejected.  With `grad = True` the losses are differentiable with respect to the model's outputs, through two
+more entry points per layer.  Importing this module loads no library."""
 import torch
 from torch import nn
 
@@ -11,6 +12,40 @@ _KEYS = ("pred_logits", "pred_boxes", "pred_masks", "pred_visible")
 _LOSS_KEYS = {"labels": ("loss_ce",), "boxes": ("loss_bbox", "loss_giou"), "masks": ("loss_mask", "loss_dice"),
               "visible": ("loss_vis",)}
 _SLOT = {"loss_ce": 0, "loss_bbox": 1, "loss_giou": 2, "loss_mask": 3, "loss_dice": 4, "loss_vis": 5}  # of the kernel's losses[6]
+
+
+class _LayerLosses(torch.autograd.Function):
+    """losses [6] of one decoder layer as a differentiable function of (pred_logits, pred_boxes, pred_masks | None, pred_visible |
+    None).  Forward: the two forward entry points; backward: entry (c) if pred_masks needs a gradient, entry (d) for the others."""
+
+    @staticmethod
+    def forward(ctx, crit, tg, hw, num_boxes, logits, boxes, masks, visible):
+        out = {"pred_logits": logits.detach(), "pred_boxes": boxes.detach()}
+        if masks is not None:
+            out["pred_masks"] = masks.detach()
+        if visible is not None:
+            out["pred_visible"] = visible.detach()
+        vals = crit._layer(out, tg, hw, num_boxes)
+        ctx.alpha = crit.focal_alpha
+        ctx.save_for_backward(logits, boxes, masks, visible, vals["index"], vals["sums"], vals["st"], num_boxes, tg["labels"],
+                              tg["boxes"], tg["valid"], tg.get("masks"))
+        return vals["losses"]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gl):
+        logits, boxes, masks, visible, index, sums, st, num_boxes, labels, tboxes, valid, tmasks = ctx.saved_tensors
+        need = ctx.needs_input_grad[4:8]
+        gl = gl.detach().to(torch.float32).contiguous()
+        g_masks = None
+        if need[2]:
+            g_masks = train_ops.criterion_mask_grad(masks.detach(), tmasks, sums, st, index, num_boxes, gl, alpha=ctx.alpha)
+        g_logits = g_boxes = g_vis = None
+        if need[0] or need[1] or need[3]:
+            g_logits, g_boxes, g_vis = train_ops.criterion_head_grads(
+                logits.detach(), boxes.detach(), labels, tboxes, valid, index, num_boxes, gl,
+                pred_visible=None if visible is None else visible.detach(), focal_alpha=ctx.alpha, want=(need[0], need[1], need[3]))
+        return None, None, None, None, g_logits, g_boxes, g_masks, g_vis
 
 
 def _stack_outputs(outputs):
@@ -33,11 +68,16 @@ class SetCriterion(nn.Module):
     0-dim float32 device tensor; criterion.matcher(outputs, targets) -> the reference's [(src_idx, tgt_idx)] list.
 
     outputs: the model's dict ([B,T,Q,..] tensors) or a list of per-clip dicts.  targets: B dicts with masks [T,H,W] (bool / uint8 /
-    float 0-1), boxes [T,4] cxcywh, labels [T], valid [T], all on the GPU; all clips of a call share one shape."""
+    float 0-1), boxes [T,4] cxcywh, labels [T], valid [T], all on the GPU; all clips of a call share one shape.
+
+    grad (a plain attribute, False by default): when True, the outputs may require grad and every value of the loss dict carries a
+    grad_fn back to pred_logits, pred_boxes, pred_masks and pred_visible; the targets still may not require grad, and matcher() and
+    layer_values() stay forward only."""
 
     def __init__(self, num_classes, weight_dict, losses, focal_alpha=0.25, eos_coef=0.1, cost_class=2.0, cost_bbox=5.0, cost_giou=2.0,
-                 cost_mask=2.0, cost_dice=5.0, cost_vis=2.0, masks=True, vis=False):
+                 cost_mask=2.0, cost_dice=5.0, cost_vis=2.0, masks=True, vis=False, grad=False):
         super().__init__()
+        self.grad = bool(grad)
         for name in losses:
             if name not in _LOSS_KEYS:
                 raise ValueError(f"SetCriterion: do you really want to compute {name} loss?")  # criterion.py:213
@@ -109,16 +149,19 @@ class SetCriterion(nn.Module):
             train_ops.check_mask_shape("SetCriterion", hw[0], hw[1], H, W)
 
     @staticmethod
-    def _no_grad_on_gpu(named):
+    def _no_grad_on_gpu(named, differentiable=False):
         for name, t in named:  # grad first: it is a property of the call, the device one of the machine
-            if t.requires_grad:
-                raise ValueError(f"SetCriterion: {name} requires grad; the criterion is forward only (its backward is not built) and "
-                                 f"the result would silently cut the graph")
+            if t.requires_grad and differentiable and name.startswith("targets"):
+                raise ValueError(f"SetCriterion: {name} requires grad; the losses are differentiable with respect to the model's "
+                                 f"outputs only")
+            if t.requires_grad and not differentiable:
+                raise ValueError(f"SetCriterion: {name} requires grad; the criterion is forward only unless its grad attribute "
+                                 f"is set, and the result would silently cut the graph")
         for name, t in named:
             if not t.is_cuda:
                 raise ValueError(f"SetCriterion: {name} is a CPU tensor; the criterion runs on the GPU")
 
-    def _prepare(self, outputs, targets):
+    def _prepare(self, outputs, targets, differentiable=False):
         outputs = _stack_outputs(outputs)
         if not isinstance(targets, (list, tuple)) or not targets or not all(isinstance(t, dict) for t in targets):
             raise ValueError("SetCriterion: targets must be a non-empty list of dicts")
@@ -134,7 +177,7 @@ class SetCriterion(nn.Module):
         self._targets(targets, B, T, hw)
         named += [(f"targets[{b}]['{k}']", t[k]) for b, t in enumerate(targets)
                   for k in ("boxes", "labels", "valid") + (("masks",) if hw is not None else ())]
-        self._no_grad_on_gpu(named)
+        self._no_grad_on_gpu(named, differentiable)
         dev = outputs["pred_logits"].device
         tg = {"labels": torch.stack([t["labels"] for t in targets]).to(device=dev, dtype=torch.int64).contiguous(),
               "boxes": torch.stack([t["boxes"] for t in targets]).to(device=dev, dtype=torch.float32).contiguous(),
@@ -184,13 +227,24 @@ class SetCriterion(nn.Module):
         idx = self._layer(layers[0], tg, hw, torch.ones(1, dtype=torch.float32, device=dev))["index"].to(torch.int64)
         return [(idx[b:b + 1], torch.zeros(1, dtype=torch.int64, device=dev)) for b in range(idx.shape[0])]
 
-    @torch.no_grad()
     def forward(self, outputs, targets):
-        layers, tg, hw = self._prepare(outputs, targets)
+        if not self.grad:
+            with torch.no_grad():
+                return self._forward(outputs, targets, False)
+        return self._forward(outputs, targets, True)
+
+    def _forward(self, outputs, targets, differentiable):
+        layers, tg, hw = self._prepare(outputs, targets, differentiable)
         num_boxes = self._num_boxes(targets, layers[0]["pred_logits"].device)
+        need_vis = self.vis or "visible" in self.losses
         losses = {}
         for i, out in enumerate(layers):
-            vals = self._layer(out, tg, hw, num_boxes)["losses"]
+            if differentiable:
+                vals = _LayerLosses.apply(self, tg, hw, num_boxes, out["pred_logits"].contiguous(), out["pred_boxes"].contiguous(),
+                                          out["pred_masks"].contiguous() if hw is not None else None,
+                                          out["pred_visible"].contiguous() if need_vis else None)
+            else:
+                vals = self._layer(out, tg, hw, num_boxes)["losses"]
             suffix = "" if i == 0 else f"_{i - 1}"
             for name in self.losses:
                 for key in _LOSS_KEYS[name]:

@@ -1,6 +1,7 @@
-// The forward values of SetCriterion and of its one-target matcher (train/tce_rvos_train.h): a streaming walk of the mask logits
-// that leaves three fp64 sums per query, and a workgroup per clip that turns them and the few hundred other numbers of a clip into
-// the cost column, the match and the loss parts.  This translation unit is the whole of libtce_rvos_train.so.
+// SetCriterion and its one-target matcher (train/tce_rvos_train.h).  Forward: a streaming walk of the mask logits that leaves three
+// fp64 sums per query, and a workgroup per clip that turns them and the few hundred other numbers of a clip into the cost column,
+// the match and the loss parts.  Backward: one launch that writes the gradient of the mask logits from those sums, one for the three
+// heads.  This translation unit is the whole of libtce_rvos_train.so.
 #define tce_set_error tce_train_set_error  // common.h's macros report into this library's own last-error string
 #include "../csrc/common.h"
 
@@ -280,6 +281,206 @@ __global__ void __launch_bounds__(64) losses_kernel(const double* __restrict__ p
   losses[j] = (float)(j < 5 ? s / (double)num_boxes[0] : s);
 }
 
+// ---- the backward of the losses (header (c), (d)) ---------------------------------------------------------------------------------
+// d f / d v and s * (1 - s) of the header's per-element chain
+__device__ __forceinline__ void focal_grad_terms(const float v, const bool tv, const float alpha, const float one_minus_alpha,
+                                                 float& dfs, float& ds) {
+#pragma clang fp contract(off)
+  const float z = tv ? -v : v;
+  const float e = expf(-fabsf(v));
+  const float r = 1.f / (1.f + e);
+  const float er = e * r;
+  const float s = v >= 0.f ? r : er;
+  const float sc = v >= 0.f ? er : r;
+  const float m = z >= 0.f ? r : er;
+  const float mc = z >= 0.f ? er : r;
+  const float ce = fmaxf(z, 0.f) + log1pf(e);
+  const float df = (tv ? alpha : one_minus_alpha) * ((m * m) * (m + 2.f * (ce * mc)));
+  dfs = tv ? -df : df;
+  ds = s * sc;
+}
+
+struct MaskGradArgs {
+  const float* pred;
+  const uint8_t* tgt;
+  const double *sums, *st;
+  const int32_t* index;
+  const float *num_boxes, *gl;
+  float* grad;
+  int T, Q, h, w, H, W, chunk;
+  float alpha, one_minus_alpha;
+};
+
+// blockIdx = (chunk of the query's T*h*w elements, query, clip); four consecutive elements of one row per thread and step
+// (w % 4 == 0).  PV / GV: 16-byte loads of pred / stores of grad; the arithmetic is the same in all four forms.
+template <bool PV, bool GV>
+__global__ void __launch_bounds__(THREADS) mask_grad_kernel(const MaskGradArgs a) {
+#pragma clang fp contract(off)
+  const int g = blockIdx.x, q = blockIdx.y, b = blockIdx.z;
+  const int hw = a.h * a.w, N = a.T * hw;
+  const int lo = g * a.chunk, hi = min(N, lo + a.chunk);
+  const long long base = ((long long)b * a.T * a.Q + q) * hw, tstride = (long long)a.Q * hw;
+  float* __restrict__ grad = a.grad + base;
+  const int idx = a.index[b];
+  if (q != idx) {
+    for (int e = lo + (int)threadIdx.x * 4; e < hi; e += THREADS * 4) {
+      const int t = e / hw, rem = e - t * hw;
+      float* o = grad + t * tstride + rem;
+      if constexpr (GV) {
+        const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+        *(f32x4*)o = zero;
+      } else {
+        o[0] = 0.f, o[1] = 0.f, o[2] = 0.f, o[3] = 0.f;
+      }
+    }
+    return;
+  }
+  // the block-uniform factors: fp64, rounded once
+  const double* s = a.sums + (long long)b * 3 * a.Q;
+  const double n = (double)a.num_boxes[0];
+  const double D = s[a.Q + idx] + a.st[b] + 1.;
+  const double num = (2. * s[2 * a.Q + idx] + 1.) / (D * D);
+  const double gd = (double)a.gl[4] / n;
+  const float Gm = (float)((double)a.gl[3] / n / (double)N);
+  const float Gd0 = (float)(gd * num), Gd1 = (float)(gd * (num - 2. / D));
+  const float* __restrict__ pred = a.pred + base;
+  const uint8_t* __restrict__ tgt = a.tgt + (long long)b * a.T * a.H * a.W;
+  for (int e = lo + (int)threadIdx.x * 4; e < hi; e += THREADS * 4) {
+    const int t = e / hw, rem = e - t * hw, y = rem / a.w, x = rem - y * a.w;
+    const float* p = pred + t * tstride + rem;
+    float v[4], o4[4];
+    if constexpr (PV) {
+      const f32x4 q4 = *(const f32x4*)p;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[j] = q4[j];
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[j] = p[j];
+    }
+    const int yy = 4 * y + 2;
+    const uint8_t* row = tgt + ((long long)t * a.H + yy) * a.W;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int xx = 4 * (x + j) + 2;
+      const bool tv = (yy < a.H && xx < a.W) ? row[xx] != 0 : false;
+      float dfs, ds;
+      focal_grad_terms(v[j], tv, a.alpha, a.one_minus_alpha, dfs, ds);
+      o4[j] = Gm * dfs + (tv ? Gd1 : Gd0) * ds;
+    }
+    float* o = grad + t * tstride + rem;
+    if constexpr (GV) {
+      const f32x4 r4 = {o4[0], o4[1], o4[2], o4[3]};
+      *(f32x4*)o = r4;
+    } else {
+      o[0] = o4[0], o[1] = o4[1], o[2] = o4[2], o[3] = o4[3];
+    }
+  }
+}
+
+struct HeadGradArgs {
+  const float *logits, *pred_boxes, *visible;
+  const int64_t* labels;
+  const float* boxes;
+  const int32_t *valid, *index;
+  const float *num_boxes, *gl;
+  float *g_logits, *g_boxes, *g_visible;
+  int T, Q, K;
+  float alpha;
+};
+
+// d(1 - giou)/d(cx, cy, w, h) of the predicted box: giou_cxcywh's chain in reverse (header (d))
+__device__ __forceinline__ void giou_loss_grad(const float* p, const float* g, float* d) {
+#pragma clang fp contract(off)
+  const float x0 = p[0] - 0.5f * p[2], y0 = p[1] - 0.5f * p[3], x1 = p[0] + 0.5f * p[2], y1 = p[1] + 0.5f * p[3];
+  const float gx0 = g[0] - 0.5f * g[2], gy0 = g[1] - 0.5f * g[3], gx1 = g[0] + 0.5f * g[2], gy1 = g[1] + 0.5f * g[3];
+  const float wp = x1 - x0, hp = y1 - y0;
+  const float area_p = wp * hp, area_g = (gx1 - gx0) * (gy1 - gy0);
+  const float ax = fminf(x1, gx1) - fmaxf(x0, gx0), ay = fminf(y1, gy1) - fmaxf(y0, gy0);
+  const float iw = fmaxf(ax, 0.f), ih = fmaxf(ay, 0.f);
+  const float inter = iw * ih;
+  const float uni = (area_p + area_g) - inter;
+  const float du = uni + 1e-6f;
+  const float iou = (inter + 1e-6f) / du;
+  const float cx = fmaxf(x1, gx1) - fminf(x0, gx0), cy = fmaxf(y1, gy1) - fminf(y0, gy0);
+  const float ew = fmaxf(cx, 0.f), eh = fmaxf(cy, 0.f);
+  const float area = ew * eh;
+  const float da = area + 1e-6f;
+  const float r2 = ((area - uni) + 1e-6f) / da;
+  // L = 1 - (iou - r2)
+  const float d_area = (1.f - r2) / da;            // r2 = ((area - uni) + eps) / (area + eps)
+  const float d_uni = iou / du - 1.f / da;         // through both quotients
+  const float d_inter = (-1.f / du) - d_uni;       // directly, and through uni = (area_p + area_g) - inter
+  const float d_iw = d_inter * ih, d_ih = d_inter * iw;
+  const float d_ew = d_area * eh, d_eh = d_area * ew;
+  const float d_wp = d_uni * hp, d_hp = d_uni * wp;  // d_area_p = d_uni
+  float d_x0 = -d_wp, d_x1 = d_wp, d_y0 = -d_hp, d_y1 = d_hp;
+  if (ax > 0.f) {  // a clamp at exactly 0 passes nothing; equal arguments: the predicted box's corner takes the whole gradient
+    if (x1 <= gx1) d_x1 += d_iw;
+    if (x0 >= gx0) d_x0 -= d_iw;
+  }
+  if (ay > 0.f) {
+    if (y1 <= gy1) d_y1 += d_ih;
+    if (y0 >= gy0) d_y0 -= d_ih;
+  }
+  if (cx > 0.f) {
+    if (x1 >= gx1) d_x1 += d_ew;
+    if (x0 <= gx0) d_x0 -= d_ew;
+  }
+  if (cy > 0.f) {
+    if (y1 >= gy1) d_y1 += d_eh;
+    if (y0 <= gy0) d_y0 -= d_eh;
+  }
+  d[0] = d_x0 + d_x1, d[1] = d_y0 + d_y1, d[2] = 0.5f * (d_x1 - d_x0), d[3] = 0.5f * (d_y1 - d_y0);
+}
+
+// blockIdx = (slice of the clip's T*Q*K logits, clip); the first T*Q threads of a clip also own a box and a visibility logit
+__global__ void __launch_bounds__(THREADS) head_grads_kernel(const HeadGradArgs a) {
+#pragma clang fp contract(off)
+  const int b = blockIdx.y, T = a.T, Q = a.Q, K = a.K;
+  const int i = blockIdx.x * THREADS + (int)threadIdx.x;
+  const int idx = a.index[b];
+  const double n = (double)a.num_boxes[0];
+  const float oma = 1.f - a.alpha;
+  if (a.g_logits && i < T * Q * K) {
+    const int t = i / (Q * K), r = i - t * (Q * K), q = r / K, k = r - q * K;
+    const long long l = a.labels[b * T + t];
+    const int c = K == 1 ? 0 : (int)(l < 0 ? 0 : (l > K - 1 ? K - 1 : l));
+    const long long at = (long long)b * T * Q * K + i;
+    float dfs, ds;
+    focal_grad_terms(a.logits[at], a.valid[b * T + t] != 0 && q == idx && k == c, a.alpha, oma, dfs, ds);
+    a.g_logits[at] = (float)((double)a.gl[0] / n) * dfs;
+  }
+  if (i < T * Q) {
+    const int t = i / Q, q = i - t * Q;
+    const long long at = (long long)b * T * Q + i;
+    if (a.g_visible) {
+      float dfs = 0.f, ds;
+      if (q == idx) {
+        focal_grad_terms(a.visible[at], a.valid[b * T + t] != 0, a.alpha, oma, dfs, ds);
+        dfs = (float)((double)a.gl[5] * (double)Q / (double)T) * dfs;
+      }
+      a.g_visible[at] = dfs;
+    }
+    if (a.g_boxes) {
+      float o[4] = {0.f, 0.f, 0.f, 0.f};
+      if (q == idx) {
+        const float* p = a.pred_boxes + at * 4;
+        const float* g = a.boxes + ((long long)b * T + t) * 4;
+        const float c1 = (float)((double)a.gl[1] / n), c2 = (float)((double)a.gl[2] / n);
+        float d[4];
+        giou_loss_grad(p, g, d);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const float df = p[j] - g[j];
+          o[j] = c1 * (df > 0.f ? 1.f : (df < 0.f ? -1.f : 0.f)) + c2 * d[j];
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) a.g_boxes[at * 4 + j] = o[j];
+    }
+  }
+}
+
 int sums_groups(long long N) { return tce_cdiv(N, TCE_CRIT_CHUNK); }
 
 }  // namespace
@@ -351,5 +552,61 @@ extern "C" int tce_criterion_match_losses_f32(const float* logits, const float* 
   TCE_CHECK_LAUNCH("tce_criterion_match_losses_f32");
   hipLaunchKernelGGL(losses_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const double*)parts, num_boxes, losses, B);
   TCE_CHECK_LAUNCH("tce_criterion_match_losses_f32");
+  return TCE_OK;
+}
+
+extern "C" int tce_criterion_mask_grad_f32(const float* pred, const uint8_t* tgt, const double* sums, const double* st,
+                                           const int32_t* index, const float* num_boxes, const float* gl, float* grad, int32_t B,
+                                           int32_t T, int32_t Q, int32_t h, int32_t w, int32_t H, int32_t W, float alpha,
+                                           tceStream stream) {
+  TCE_CHECK_ARG(pred && tgt && sums && st && index && num_boxes && gl && grad, "tce_criterion_mask_grad_f32: null pointer");
+  CRIT_CHECK_EXTENTS("tce_criterion_mask_grad_f32");
+  TCE_CHECK_ARG(h >= 1 && w >= 1 && H >= 1 && W >= 1, "tce_criterion_mask_grad_f32: non-positive extent");
+  TCE_CHECK_ARG((long long)T * h * w < (1ll << 30), "tce_criterion_mask_grad_f32: T*h*w must stay below 2^30");
+  TCE_CHECK_ARG(4ll * h == ((long long)H + 31) / 32 * 32 && 4ll * w == ((long long)W + 31) / 32 * 32,
+                "tce_criterion_mask_grad_f32: the mask plane %d x %d is not a quarter of the target %d x %d padded to a multiple of 32",
+                h, w, H, W);
+  TCE_CHECK_ARG(((((uintptr_t)pred) | ((uintptr_t)grad) | ((uintptr_t)index) | ((uintptr_t)num_boxes) | ((uintptr_t)gl)) & 3u) == 0 &&
+                    ((((uintptr_t)sums) | ((uintptr_t)st)) & 7u) == 0,
+                "tce_criterion_mask_grad_f32: pred / grad / index / num_boxes / gl must be 4-byte, sums / st 8-byte aligned");
+  MaskGradArgs a;
+  a.pred = pred, a.tgt = tgt, a.sums = sums, a.st = st, a.index = index, a.num_boxes = num_boxes, a.gl = gl, a.grad = grad;
+  a.T = T, a.Q = Q, a.h = h, a.w = w, a.H = H, a.W = W, a.chunk = TCE_CRIT_CHUNK;
+  a.alpha = alpha, a.one_minus_alpha = 1.f - alpha;
+  const dim3 grid(sums_groups((long long)T * h * w), Q, B), block(THREADS);
+  const bool pv = tce_aligned16(pred), gv = tce_aligned16(grad);  // 4w == ceil32(W): w % 8 == 0, every row starts a 16-byte group
+  if (pv && gv)
+    hipLaunchKernelGGL((mask_grad_kernel<true, true>), grid, block, 0, (hipStream_t)stream, a);
+  else if (pv)
+    hipLaunchKernelGGL((mask_grad_kernel<true, false>), grid, block, 0, (hipStream_t)stream, a);
+  else if (gv)
+    hipLaunchKernelGGL((mask_grad_kernel<false, true>), grid, block, 0, (hipStream_t)stream, a);
+  else
+    hipLaunchKernelGGL((mask_grad_kernel<false, false>), grid, block, 0, (hipStream_t)stream, a);
+  TCE_CHECK_LAUNCH("tce_criterion_mask_grad_f32");
+  return TCE_OK;
+}
+
+extern "C" int tce_criterion_head_grads_f32(const float* logits, const float* pred_boxes, const float* visible, const int64_t* labels,
+                                            const float* boxes, const int32_t* valid, const int32_t* index, const float* num_boxes,
+                                            const float* gl, float* g_logits, float* g_boxes, float* g_visible, int32_t B, int32_t T,
+                                            int32_t Q, int32_t K, const tceCriterionConsts* consts, tceStream stream) {
+  TCE_CHECK_ARG(logits && pred_boxes && labels && boxes && valid && index && num_boxes && gl && consts,
+                "tce_criterion_head_grads_f32: null pointer");
+  TCE_CHECK_ARG(g_logits || g_boxes || g_visible, "tce_criterion_head_grads_f32: no output asked for");
+  TCE_CHECK_ARG(!g_visible || visible, "tce_criterion_head_grads_f32: g_visible without visible");
+  CRIT_CHECK_EXTENTS("tce_criterion_head_grads_f32");
+  TCE_CHECK_ARG(K >= 1 && K <= TCE_CRIT_MAX_K, "tce_criterion_head_grads_f32: 1..%d class logits, got %d", TCE_CRIT_MAX_K, K);
+  TCE_CHECK_ARG(((((uintptr_t)logits) | ((uintptr_t)pred_boxes) | ((uintptr_t)visible) | ((uintptr_t)boxes) | ((uintptr_t)valid) |
+                  ((uintptr_t)index) | ((uintptr_t)num_boxes) | ((uintptr_t)gl) | ((uintptr_t)g_logits) | ((uintptr_t)g_boxes) |
+                  ((uintptr_t)g_visible)) & 3u) == 0 && (((uintptr_t)labels) & 7u) == 0,
+                "tce_criterion_head_grads_f32: misaligned pointer (4 bytes for fp32 / int32, 8 for int64)");
+  HeadGradArgs a;
+  a.logits = logits, a.pred_boxes = pred_boxes, a.visible = visible, a.labels = labels, a.boxes = boxes, a.valid = valid;
+  a.index = index, a.num_boxes = num_boxes, a.gl = gl, a.g_logits = g_logits, a.g_boxes = g_boxes, a.g_visible = g_visible;
+  a.T = T, a.Q = Q, a.K = K, a.alpha = consts->focal_alpha;
+  const int items = g_logits ? T * Q * K : T * Q;  // <= 64 * 1024 * 128
+  hipLaunchKernelGGL(head_grads_kernel, dim3(tce_cdiv(items, THREADS), B), dim3(THREADS), 0, (hipStream_t)stream, a);
+  TCE_CHECK_LAUNCH("tce_criterion_head_grads_f32");
   return TCE_OK;
 }

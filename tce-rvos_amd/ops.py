@@ -13,8 +13,8 @@ from .stage_ops import (A2D_GROUP_MAX, LABEL_MAX_OBJS, PNG_FILE_MAX_HEAD, PNG_FI
                         REFEXP_GROUP_MAX, REFEXP_MAX_CAND, VIS_MAX_LAYERS, a2d_group_masks, a2d_masks, jf_counts, label_objects,
                         mask_overlap, png_deflate, png_deflate_rows, png_file, png_filter_rgb, refexp_giou, refexp_group, rle_counts,
                         rle_decode, select_masks, select_window_masks, vis_overlay)
-# the criterion's two entry points live in the training-side library (train_ops.py; nothing is loaded until one is called)
-from .train_ops import criterion_mask_sums, criterion_match_losses  # noqa: F401
+# the criterion's entry points live in the training-side library (train_ops.py; nothing is loaded until one is called)
+from .train_ops import criterion_head_grads, criterion_mask_grad, criterion_mask_sums, criterion_match_losses  # noqa: F401
 
 ACT_NONE, ACT_RELU, ACT_GELU, ACT_RELU_AFTER_RES = 0, 1, 2, 3
 RES_NONE, RES_ADD, RES_MUL = 0, 1, 2

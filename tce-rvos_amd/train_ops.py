@@ -1,4 +1,4 @@
-"""Thin tensor plumbing over libtce_rvos_train.so (train/tce_rvos_train.h): the criterion's two entry points.  torch owns device
+"""Thin tensor plumbing over libtce_rvos_train.so (train/tce_rvos_train.h): the criterion's entry points, forward and backward.  torch owns device
 memory and streams, the arithmetic is HIP.  Every rejection here is a ValueError raised before anything is launched.  No fallback."""
 import torch
 
@@ -20,8 +20,8 @@ def _dev(t, op, name, dtype, shape=None, device=None):
     if not t.is_cuda:
         raise ValueError(f"{op}: {name} is a CPU tensor; the criterion runs on the GPU")
     if t.requires_grad:
-        raise ValueError(f"{op}: {name} requires grad; the criterion is forward only (its backward is not built) and would "
-                         f"silently cut the graph")
+        raise ValueError(f"{op}: {name} requires grad; the entry points take no part in autograd and would silently cut the "
+                         f"graph (SetCriterion with grad = True is the differentiable form)")
     if t.dtype != dtype or not t.is_contiguous():
         raise ValueError(f"{op}: {name} must be a contiguous {dtype} tensor, got {t.dtype}"
                          + ("" if t.is_contiguous() else " (not contiguous)"))
@@ -119,3 +119,82 @@ def criterion_match_losses(pred_logits, pred_boxes, labels, boxes, valid, num_bo
         valid.data_ptr(), num_boxes.data_ptr(), cost.data_ptr(), index.data_ptr(), parts.data_ptr(), losses.data_ptr(),
         B, T, Q, K, h, w, consts, _stream()), "tce_criterion_match_losses_f32")
     return cost, index, parts, losses
+
+
+def _out(out, op, name, shape, dev):
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=dev)
+    return _dev(out, op, name, torch.float32, shape, dev)
+
+
+def _gl(op, num_boxes, gl, dev):
+    _dev(num_boxes, op, "num_boxes", torch.float32, device=dev)
+    if num_boxes.numel() != 1:
+        raise ValueError(f"{op}: num_boxes must hold one element")
+    _dev(gl, op, "gl", torch.float32, (6,), dev)
+
+
+def criterion_mask_grad(pred_masks, masks, sums, st, index, num_boxes, gl, alpha=0.25, out=None):
+    """d L / d pred_masks of loss_mask and loss_dice (train/tce_rvos_train.h (c)): pred_masks [B,T,Q,h,w] float32, masks [B,T,H,W]
+    uint8, sums [B,3,Q] / st [B] float64 of criterion_mask_sums, index [B] int32 of criterion_match_losses, num_boxes a one-element
+    float32 device tensor, gl [6] float32 = dL/d losses on the device -> grad [B,T,Q,h,w] float32 (`out` if given).  One launch;
+    the planes of the unmatched queries are +0.0."""
+    op = "criterion_mask_grad"
+    if not torch.is_tensor(pred_masks) or pred_masks.dim() != 5:
+        raise ValueError(f"{op}: pred_masks [B,T,Q,h,w] expected, got {tuple(getattr(pred_masks, 'shape', ()))}")
+    B, T, Q, h, w = (int(s) for s in pred_masks.shape)
+    dev = pred_masks.device
+    _dev(pred_masks, op, "pred_masks", torch.float32)
+    if not torch.is_tensor(masks) or masks.dim() != 4 or int(masks.shape[0]) != B or int(masks.shape[1]) != T:
+        raise ValueError(f"{op}: masks [B,T,H,W] = [{B},{T},H,W] expected, got {tuple(getattr(masks, 'shape', ()))}")
+    _dev(masks, op, "masks", torch.uint8, device=dev)
+    H, W = int(masks.shape[2]), int(masks.shape[3])
+    _limits(op, B, T, Q)
+    if min(h, w, H, W) < 1 or T * h * w >= MAX_ELEMS:
+        raise ValueError(f"{op}: limits exceeded: 1 <= T*h*w < 2^30, got {T} x {h} x {w}")
+    check_mask_shape(op, h, w, H, W)
+    _dev(sums, op, "sums", torch.float64, (B, 3, Q), dev)
+    _dev(st, op, "st", torch.float64, (B,), dev)
+    _dev(index, op, "index", torch.int32, (B,), dev)
+    _gl(op, num_boxes, gl, dev)
+    grad = _out(out, op, "out", (B, T, Q, h, w), dev)
+    check(lib().tce_criterion_mask_grad_f32(pred_masks.data_ptr(), masks.data_ptr(), sums.data_ptr(), st.data_ptr(), index.data_ptr(),
+                                            num_boxes.data_ptr(), gl.data_ptr(), grad.data_ptr(), B, T, Q, h, w, H, W, float(alpha),
+                                            _stream()), "tce_criterion_mask_grad_f32")
+    return grad
+
+
+def criterion_head_grads(pred_logits, pred_boxes, labels, boxes, valid, index, num_boxes, gl, pred_visible=None, focal_alpha=0.25,
+                         want=(True, True, False), out=(None, None, None)):
+    """d L / d (pred_logits, pred_boxes, pred_visible) of loss_ce, loss_bbox + loss_giou, loss_vis (train/tce_rvos_train.h (d)).
+    Inputs as criterion_match_losses, index [B] int32 of it, gl [6] float32 on the device.  want: which of the three gradients to
+    compute; out: tensors to write them to -> (g_logits [B,T,Q,K], g_boxes [B,T,Q,4], g_visible [B,T,Q,1]), None where not wanted.
+    One launch."""
+    op = "criterion_head_grads"
+    if not torch.is_tensor(pred_logits) or pred_logits.dim() != 4:
+        raise ValueError(f"{op}: pred_logits [B,T,Q,K] expected, got {tuple(getattr(pred_logits, 'shape', ()))}")
+    B, T, Q, K = (int(s) for s in pred_logits.shape)
+    dev = pred_logits.device
+    _dev(pred_logits, op, "pred_logits", torch.float32)
+    _dev(pred_boxes, op, "pred_boxes", torch.float32, (B, T, Q, 4), dev)
+    if pred_visible is not None:
+        _dev(pred_visible, op, "pred_visible", torch.float32, (B, T, Q, 1), dev)
+    _dev(labels, op, "labels", torch.int64, (B, T), dev)
+    _dev(boxes, op, "boxes", torch.float32, (B, T, 4), dev)
+    _dev(valid, op, "valid", torch.int32, (B, T), dev)
+    _dev(index, op, "index", torch.int32, (B,), dev)
+    _gl(op, num_boxes, gl, dev)
+    _limits(op, B, T, Q, K)
+    want = tuple(bool(x) for x in want)
+    if len(want) != 3 or len(out) != 3 or not any(want):
+        raise ValueError(f"{op}: want and out name the three gradients (logits, boxes, visible), one at least wanted")
+    if want[2] and pred_visible is None:
+        raise ValueError(f"{op}: the gradient of pred_visible without pred_visible")
+    shapes = ((B, T, Q, K), (B, T, Q, 4), (B, T, Q, 1))
+    g = [(_out(o, op, f"out[{i}]", s, dev) if wd else None) for i, (wd, o, s) in enumerate(zip(want, out, shapes))]
+    consts = CriterionConsts(0.0, 0.0, 0.0, 0.0, 0.0, 0.0, float(focal_alpha))
+    check(lib().tce_criterion_head_grads_f32(
+        pred_logits.data_ptr(), pred_boxes.data_ptr(), None if pred_visible is None else pred_visible.data_ptr(), labels.data_ptr(),
+        boxes.data_ptr(), valid.data_ptr(), index.data_ptr(), num_boxes.data_ptr(), gl.data_ptr(),
+        *(None if t is None else t.data_ptr() for t in g), B, T, Q, K, consts, _stream()), "tce_criterion_head_grads_f32")
+    return tuple(g)

@@ -1,5 +1,6 @@
 /* tce_rvos_train.h -- entry points of libtce_rvos_train.so, the training-side sibling of libtce_rvos.so: the forward values of the
- * reference's SetCriterion (models/criterion.py) and of the matcher it calls (models/matcher.py), csrc_train/criterion.hip.
+ * reference's SetCriterion (models/criterion.py) and of the matcher it calls (models/matcher.py), and the gradients of its losses
+ * with respect to the model's outputs ((c), (d) at the end), csrc_train/criterion.hip.
  *
  * The library is separate from the inference one: its own version, its own last-error string, its own binding table
  * (tce_rvos_amd/_train_lib.py TRAIN_SIGNATURES); no name here occurs in a header of include/.
@@ -100,6 +101,54 @@ int tce_criterion_match_losses_f32(const float* logits, const float* pred_boxes,
                                    const float* num_boxes, float* cost /* [B,Q] */, int32_t* index /* [B] */,
                                    double* parts /* [B,6] */, float* losses /* [6] */, int32_t B, int32_t T, int32_t Q, int32_t K,
                                    int32_t h, int32_t w, const tceCriterionConsts* consts /* host */, tceStream stream);
+
+/* ==== The backward of the losses with respect to the model's outputs.  Additions to version 1: nothing above changes.  Both entries
+ * read num_boxes[0] = n and the upstream gradients gl[6] = dL/d losses[j] (the order of losses[6]) from the device; both are one
+ * launch.  index, sums and st are what (a) and (b) left for the same inputs. */
+
+/* ---- (c) d L / d pred of loss_mask and loss_dice, grad [B,T,Q,h,w] fp32, every word written.  Grid (ceil(T*h*w / TCE_CRIT_CHUNK),
+ * Q, B) as (a).  A workgroup with q != index[b] stores +0.0 and reads nothing but index[b].  A workgroup of the matched query reads
+ * pred once and fetches tv as (a) defines it.  With idx = index[b], N = T*h*w, in fp64 and then rounded once to fp32:
+ *   D = S_p[idx] + S_t + 1        Gm  = gl[3] / n / N
+ *   Gd0 = gl[4]/n * (2*S_pt[idx] + 1)/D^2            Gd1 = gl[4]/n * ((2*S_pt[idx] + 1)/D^2 - 2/D)
+ * Per element, fp32, contraction off, with e, r, er = e*r, s, m, ce, z of (a):
+ *   mc = z >= 0 ? er : r                              = 1 - m, NOT formed by subtraction
+ *   sc = v >= 0 ? er : r                              = 1 - s, NOT formed by subtraction
+ *   df = (tv ? alpha : 1 - alpha) * ((m*m) * (m + 2*(ce*mc)))          dfs = tv ? -df : df       = d f / d v
+ *   grad = Gm * dfs + (tv ? Gd1 : Gd0) * (s*sc)
+ * Where e underflows (|v| > 87) the terms are 0 or the saturated slope, never NaN.  pred is read with 16-byte loads when its base is
+ * 16-byte aligned, grad is written with 16-byte stores when its base is; either falls back to one float at a time on its own (any
+ * 4-byte aligned base), with the same bits.  Extents and the shape precondition are those of (a). */
+int tce_criterion_mask_grad_f32(const float* pred /* [B,T,Q,h,w] */, const uint8_t* tgt /* [B,T,H,W] */, const double* sums /* [B,3,Q] */,
+                                const double* st /* [B] */, const int32_t* index /* [B] */, const float* num_boxes, const float* gl /* [6] */,
+                                float* grad /* [B,T,Q,h,w] */, int32_t B, int32_t T, int32_t Q, int32_t h, int32_t w, int32_t H,
+                                int32_t W, float alpha, tceStream stream);
+
+/* ---- (d) d L / d logits, pred_boxes, visible.  Grid (ceil(T*Q*K / 256), B).  An output pointer that is NULL is skipped; one at
+ * least is given; g_visible needs visible.  dfs(v, tv, alpha) is (c)'s, alpha = consts->focal_alpha (the other fields are not read).
+ *   g_logits[b,t,q,k]  = (float)(gl[0]/n) * dfs(logits[b,t,q,k], valid[t] && q == idx && k == c_t)       at every (t,q,k)
+ *   g_visible[b,t,q]   = q == idx ? (float)(gl[5]*Q/T) * dfs(visible[t,idx], valid[t] != 0) : +0.0        for ALL t
+ *   g_boxes[b,t,q,j]   = q == idx ? (float)(gl[1]/n) * sign(p_j - g_j) + (float)(gl[2]/n) * dg_j : +0.0   for ALL t, sign(0) = 0
+ * dg = d(1 - giou)/dp, fp32, the chain of (b)'s giou in reverse (p the predicted box, g the target's, both cxcywh):
+ *   x0 = p0 - 0.5*p2, x1 = p0 + 0.5*p2, y0 = p1 - 0.5*p3, y1 = p1 + 0.5*p3; gx0 .. gy1 the same of g
+ *   wp = x1 - x0, hp = y1 - y0, area_p = wp*hp, area_g = (gx1 - gx0)*(gy1 - gy0)
+ *   ax = min(x1,gx1) - max(x0,gx0), ay likewise; iw = max(ax,0), ih = max(ay,0); inter = iw*ih
+ *   uni = (area_p + area_g) - inter; du = uni + 1e-6; iou = (inter + 1e-6)/du
+ *   cx = max(x1,gx1) - min(x0,gx0), cy likewise; ew = max(cx,0), eh = max(cy,0); area = ew*eh; da = area + 1e-6
+ *   r2 = ((area - uni) + 1e-6)/da
+ *   d_area = (1 - r2)/da;  d_uni = iou/du - 1/da;  d_inter = (-1/du) - d_uni
+ *   d_iw = d_inter*ih, d_ih = d_inter*iw, d_ew = d_area*eh, d_eh = d_area*ew, d_wp = d_uni*hp, d_hp = d_uni*wp
+ *   d_x0 = -d_wp, d_x1 = d_wp; if ax > 0: { if x1 <= gx1: d_x1 += d_iw;  if x0 >= gx0: d_x0 -= d_iw }
+ *                              if cx > 0: { if x1 >= gx1: d_x1 += d_ew;  if x0 <= gx0: d_x0 -= d_ew }      (y likewise)
+ *   dg = (d_x0 + d_x1, d_y0 + d_y1, 0.5*(d_x1 - d_x0), 0.5*(d_y1 - d_y0))
+ * The sub-gradients at the kinks, where torch splits or picks otherwise: min / max of EQUAL arguments hand the whole gradient to the
+ * predicted box's corner (torch halves it); a clamp whose argument is exactly 0 (or negative) passes nothing (torch passes it at 0);
+ * sign(0) = 0 as torch.  Extents as (b). */
+int tce_criterion_head_grads_f32(const float* logits, const float* pred_boxes, const float* visible, const int64_t* labels,
+                                 const float* boxes, const int32_t* valid, const int32_t* index, const float* num_boxes,
+                                 const float* gl /* [6] */, float* g_logits /* [B,T,Q,K] | NULL */, float* g_boxes /* [B,T,Q,4] | NULL */,
+                                 float* g_visible /* [B,T,Q] | NULL */, int32_t B, int32_t T, int32_t Q, int32_t K,
+                                 const tceCriterionConsts* consts /* host */, tceStream stream);
 
 #ifdef __cplusplus
 }
