@@ -159,7 +159,10 @@ int tce_patch_merge_ln_f32(const float* x, const float* gamma, const float* beta
 
 /* Multi-head attention core, head_dim 32, fp32, online softmax:  O = softmax(Q K^T * scale) V per (batch, head).
  * Q [batch][Lq] rows of ldq floats (head h at column h*32), likewise K, V, O.  kmask (optional, uint8
- * [batch, Lk], non-zero = ignore key).  Reference: nn.MultiheadAttention call sites
+ * [batch, Lk], non-zero = ignore key).  "Ignore" holds whatever the key's K row contains (Inf and NaN included: the score is
+ * replaced, not offset); the V rows of ignored keys must be finite (their probability is an exact 0, and 0 * NaN is NaN).
+ * A batch entry whose keys are ALL ignored yields finite zeros in every launch form (the normalisation is
+ * l > 0 ? 1 / l : 0), where torch's softmax over a row of -inf yields NaN.  Reference: nn.MultiheadAttention call sites
  * (tce_deformable_transformer.py:467,482,683; segmentation.py:352,366,459). */
 int tce_mha_f32(const float* Q, const float* K, const float* V, float* O, int32_t batch, int32_t nheads,
                 int32_t Lq, int32_t Lk, int32_t ldq, int32_t ldk, int32_t ldv, int32_t ldo, int64_t sQ, int64_t sK,

@@ -254,7 +254,7 @@ __global__ void __launch_bounds__(64 * NW) mha_mfma_kernel(const float* __restri
     float tmax = -3.0e38f;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      st[r] = fminf(st[r], 3.0e38f) + sM[crow(r, lhi)];
+      st[r] = sM[crow(r, lhi)] < 0.f ? -3.0e38f : fminf(st[r], 3.0e38f);  // a select: whatever the ignored key's K row holds
       tmax = fmaxf(tmax, st[r]);
     }
     tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
@@ -445,7 +445,7 @@ __global__ void __launch_bounds__(64 * NW) mha_f16x3_kernel(const float* __restr
     float tmax = -3.0e38f;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      st[r] = fminf(st[r], 3.0e38f) + sM[crow(r, lhi)];
+      st[r] = sM[crow(r, lhi)] < 0.f ? -3.0e38f : fminf(st[r], 3.0e38f);  // a select: whatever the ignored key's K row holds
       tmax = fmaxf(tmax, st[r]);
     }
     tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));

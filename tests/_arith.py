@@ -30,8 +30,27 @@ DENSE_K = (16, 32, 48, 64, 96, 128, 160, 192, 256, 288, 384, 512, 576, 768, 2048
 PROBE_K = (64, 96, 128, 192, 256, 384, 512, 768, 2048, 2304, 3072)
 
 
+_WHERE = ["cpu"]
+
+
+class on:
+    """`with A.on("cuda"):` -- the bounds inside are evaluated in fp64 on that device (the same formulas; for references whose
+    per-head loop over a few thousand queries x a thousand keys x 128 heads would take the CPU seconds per case)."""
+
+    def __init__(self, device):
+        self.device, self.prev = str(device), None
+
+    def __enter__(self):
+        self.prev, _WHERE[0] = _WHERE[0], self.device
+        return self
+
+    def __exit__(self, *exc):
+        _WHERE[0] = self.prev
+        return False
+
+
 def _d(x):
-    return x.detach().to("cpu", F64)
+    return x.detach().to(_WHERE[0], F64)
 
 
 def delta(x):
@@ -194,11 +213,11 @@ def ffn_probe_operands(which, C, Hd, M, period, ws, as_, seed, launch=0):
     return x, w1, torch.zeros(Hd), w2, torch.zeros(C), c1, c2
 
 
-def softmax_v_bound(p, v, b_score, c):
+def softmax_v_bound(p, v, b_score, c, product=None):
     """softmax(s) @ v with scores off by at most b_score [rows, 1]: 2 max_j(B_score) sum_j p_j |v_j| + bound(p, v).
-    p [rows, L], v [L, D] (so the second product is p @ v = p @ (v.T).T)."""
+    p [rows, L], v [L, D] (so the second product is p @ v = p @ (v.T).T).  product: the second product's bound (bound_split)."""
     p, v = _d(p), _d(v)
-    return 2.0 * b_score * (p @ v.abs()) + bound_split(p, v.T, c)
+    return 2.0 * b_score * (p @ v.abs()) + (product or bound_split)(p, v.T, c)
 
 
 # ---- operands ----

@@ -15,6 +15,7 @@ import torch
 import torch.nn.functional as F
 
 import _arith as A
+from _attn import attention_ref_and_bound
 
 pytestmark = pytest.mark.gpu
 
@@ -540,27 +541,6 @@ def test_patch_embed(ops, T, H, W, C):
 # ---------------------------------------------------------------------------------------------------------------
 # Attention cores (unit scale, composed softmax bound)
 # ---------------------------------------------------------------------------------------------------------------
-def attention_ref_and_bound(q, k, v, scale, add=None, Bq=None, Bk=None, Bv=None):
-    """One head: q [Lq, 32], k / v [Lk, 32] -> softmax(scale q k^T + add) v and its bound (x 2).  The scores carry the product's
-    error and the fp32 roundings of the scaled score, of the added bias / mask, of the subtraction of the row maximum and of its
-    conversion to a base-2 exponent; exp and the normalisation a few ulp of p.  Bq / Bk / Bv: what the operands themselves are off by (fused kernels that project them)."""
-    q64, k64, v64 = q.double() * scale, k.double(), v.double()
-    s = q64 @ k64.T
-    Bs = A.bound_split(q64, k64, A.c_dense(32))
-    if Bq is not None:
-        Bs = Bs + scale * A.chain(Bq, k64) + A.chain(q64.abs(), Bk)
-    if add is not None:
-        s = s + add.double()
-    Bs = Bs + A.EPS_F32 * (3 * s.abs() + 2 * (s - s.amax(1, keepdim=True)).abs())
-    p = torch.softmax(s, -1)
-    bs = Bs.amax(1, keepdim=True)
-    S = p @ v64.abs()
-    B = A.softmax_v_bound(p, v64, bs, A.c_dense(k.shape[0])) + 4 * A.EPS_F32 * S
-    if Bv is not None:
-        B = B + p @ Bv
-    return p @ v64, 2 * B, S
-
-
 def windows_ref_and_bound(qkv_w, nh, bias, mask, Bqkv=None):
     """qkv_w [nW, N, 3C] (windows of q | k | v rows), bias [nh, N, N], mask [nWm, N, N] or None -> ([nW, N, C] ref, bound, S)."""
     nW, N, C3 = qkv_w.shape
