@@ -158,8 +158,10 @@ __device__ __forceinline__ void tce_epi_store_lds(const f32x16& x, float* __rest
       if (ACT == 3) v = fmaxf(v, 0.f);  // ReLU after the residual
       o[c] = v;
     }
-    amax = tce_amax4(amax, o);
     if (row < M) {
+      // only what is stored is reported: a row >= M holds (0 + bias) combined with the LAST valid row's residual, a value that
+      // exists nowhere (columns >= N are 0: zero accumulator, bias and residual)
+      amax = tce_amax4(amax, o);
       if (full) *reinterpret_cast<f32x4*>(C + (long long)row * ldc + n) = o;
       else {
 #pragma unroll
