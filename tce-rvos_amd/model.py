@@ -445,12 +445,6 @@ class ReferFormer(nn.Module):
                             mode = self.mode_of(arith_group_of(pre + tag))
                             with ops.arith(mode):
                                 w[pre + tag + ":" + mode] = ops.ffn_pack(w1, sd[pre + l1[:-len("weight")] + "bias"].detach(), w2)
-                                # FFNs that directly follow a folded cross-attention launch (the frame-token layers' pixel FFN, the
-                                # pixel decoder's VisionLanguageBlocks): the W1 stream in the k order of the attention kernel's
-                                # accumulator registers, for the one-launch chain -- only where both site groups run one arithmetic
-                                xg = ("encoder.ftf_x" if ".ftoken_layers." in pre else "pixel.xattn" if ".cross_attn_" in pre else None)
-                                if xg is not None and tag == ".ffn:pk" and ops.XATTN_FFN_CHAIN and self.mode_of(xg) == mode:
-                                    w[pre + ".ffn:pkc:" + mode] = ops.ffn_pack_chain(w1, sd[pre + ".linear1.bias"].detach(), w2)
             # Swin attention half-block as one launch (csrc/swinattn.hip): per block, Wqkv | Wproj as one fragment stream
             if not cfg.is_resnet and not cfg.video and self._stamp[0] != "f32":
                 mode = self.mode_of("backbone.attn")
@@ -723,7 +717,7 @@ class ReferFormer(nn.Module):
         strings that tokenise to the same length; targets: [{'size': (H, W)}] (one entry, or G equal ones).  Returns a list of G
         output dicts, each what `forward([clip], caption, targets)` returns for that clip (same keys / shapes; values to fp32
         round-off: a launch with more rows may pick another split-K factor).  The clips do NOT interact -- the stages that look
-        across a clip's frames or at its caption are block-diagonal per clip (pipeline._run_clip) -- unlike the reference's own
+        across a clip's frames or at its caption are block-diagonal per clip (pipeline._Clip) -- unlike the reference's own
         batch dimension, which mixes the clips of a batch.  Why: a clip alone leaves the GPU latency-bound for a third
         of its time (Swin stages 3-4 at 4600 rows, the text branch, the token / decoder paths); G clips share those launches:
         DESIGN section 3.10 has the measured clips/s.  Every position of `captions` [G, L] is a token: rows padded to a common

@@ -1269,8 +1269,8 @@ def xattn_pack(k, v, wqT_ext, wo, L, alloc, group=32, batch=1, lens=None):
 # cross-attention and the FFN behind it as ONE launch (tce_xattn_ffn_fused_f32).  Built and measured in round 5: correct (kernel and
 # whole-clip parity green with it on) but not faster -- config 2 B=1 6.37 / 6.41 ms with it against 6.29 / 6.36 ms without, G=8 37.5
 # against 36.8 ms (profiles/r05_round_ab.txt): the launch saved and the [M, 256] re-read avoided (~5 us a site) are less than what
-# the second stage loses to the chain kernel's register pressure (50 spilled VGPRs outside the loops, one resident workgroup).  Off.
-XATTN_FFN_CHAIN = os.environ.get("TCE_XATTN_FFN_CHAIN", "0") != "0"
+# the second stage loses to the chain kernel's register pressure (50 spilled VGPRs outside the loops, one resident workgroup).  The
+# clip's launch program does not use it (its switch, TCE_XATTN_FFN_CHAIN, is gone); the entry point, this wrapper and their test stay.
 
 
 def ffn_pack_chain(w1, b1, w2):

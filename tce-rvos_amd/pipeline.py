@@ -17,7 +17,7 @@ D = 256
 NH = 8
 # Rows from which the fused FFN kernel (one workgroup = 128 tokens x the whole hidden extent, ~150 us at hidden 2048)
 # beats two GEMM launches: it needs about half the chip's CUs busy.
-FFN_FUSED_MIN_ROWS = int(__import__("os").environ.get("TCE_FFN_FUSED_MIN_ROWS", 16000))
+FFN_FUSED_MIN_ROWS = int(os.environ.get("TCE_FFN_FUSED_MIN_ROWS", 16000))
 # Tokens from which the one-launch Swin attention half-block (csrc/swinattn.hip: one workgroup per two 7x7 windows) is used
 SWIN_FUSED_MIN_TOKENS = int(os.environ.get("TCE_SWIN_FUSED_MIN_TOKENS", 2000))
 
@@ -41,8 +41,20 @@ def _lin(A, x, M, K, w, b, N, **kw):
 
 # Environment switches of the launch program, read ONCE at import: they are constants of the process, so every capture of
 # the process is built from the same program (none of them needs to be part of a graph key).
-#   scheduling A/B switches (results identical): TCE_FEWROW, TCE_TEXT_LATE, TCE_TEXT_EARLY_EDGE, TCE_EARLY_PROJ, TCE_TOKFORK, TCE_ENCFORK,
+#   scheduling A/B switches (results identical): TCE_FEWROW, TCE_TEXT_LATE, TCE_EARLY_PROJ, TCE_TOKFORK, TCE_ENCFORK,
 #       TCE_LAT1_AT, TCE_LAT1_CUS; TCE_FEWROW_SITES (bisect aid: which sites take the few-row kernel)
+#   Three paths that shipped switched off were measured not faster and are no longer in the program (the kernels' forms, their
+#   ops wrappers and their tests stay):
+#       TCE_TEXT_EARLY_EDGE: the text branch with a graph edge back to the START of the clip (its nodes still issued after Swin
+#           stage 0's), so that it runs beside stage 0 instead of after it -- SLOWER, 8.09 vs 6.90 ms per clip (A/B twice in one
+#           call, profiles/r04_text_early_edge.txt): its ~150 short launches interleave with stage 0's long ones on the same
+#           hardware queues and stretch the critical path;
+#       TCE_FTF_LN_FUSE: norm1 / norm2 of the frame-token path in the prologue of the few-row launch that follows them (8 launches
+#           fewer per clip) -- 6.055 / 6.047 ms with it against 6.030 / 6.043 without (A/B twice in one call, profiles/
+#           r05_round_ab.txt): every workgroup of the projection recomputes the rows' statistics (two wave reductions per row),
+#           which costs what the LayerNorm launch did;
+#       TCE_XATTN_FFN_CHAIN: the FFN + its norm behind a folded cross-attention in the same launch (ops.xattn_fused(ffn=...)) --
+#           6.37 / 6.41 ms against 6.29 / 6.36 (profiles/r05_round_ab.txt).
 #   DIAGNOSTICS that change what forward() returns -- set by tools/ only, announced with a warning at import:
 #       TCE_ABLATE (tools/ablate_times.py): the named stages are SKIPPED, results are garbage (the time that disappears is
 #           the stage's share of the critical path); model.forward() tags its output dict with out["ablated"];
@@ -52,7 +64,6 @@ TAPS = os.environ.get("TCE_TAPS") == "1"
 FEWROW_OK = os.environ.get("TCE_FEWROW", "1") != "0"
 FEWROW_SITES = os.environ["TCE_FEWROW_SITES"].split(",") if "TCE_FEWROW_SITES" in os.environ else None
 TEXT_LATE = os.environ.get("TCE_TEXT_LATE", "1") != "0"
-TEXT_EARLY_EDGE = os.environ.get("TCE_TEXT_EARLY_EDGE", "0") != "0"
 EARLY_PROJ = os.environ.get("TCE_EARLY_PROJ", "1") != "0"
 TOKFORK = os.environ.get("TCE_TOKFORK", "1") != "0"
 ENCFORK = os.environ.get("TCE_ENCFORK", "1") != "0"
@@ -66,18 +77,12 @@ LAT1_CUS = int(os.environ["TCE_LAT1_CUS"]) if os.environ.get("TCE_LAT1_CUS", "")
 LAT1_CUS_DEFAULT = 64
 LAT1_CUS_MIN_BLOCKS = 563
 SWIN3_FC2_SPLITK = int(os.environ.get("TCE_SWIN3_FC2_SPLITK", 2))
-# norm1 / norm2 of the frame-token path in the prologue of the few-row launch that follows them (8 launches fewer per clip): measured
-# NOT faster -- 6.055 / 6.047 ms with it against 6.030 / 6.043 without (A/B twice in one call, gpurun_out/r6k): every workgroup of the
-# projection recomputes the rows' statistics (two wave reductions per row), which costs what the LayerNorm launch did.  Off.
-FTF_LN_FUSE = os.environ.get("TCE_FTF_LN_FUSE", "0") != "0"
 if ABLATE or TAPS:
     import warnings
     warnings.warn(f"tce_rvos_amd: DIAGNOSTIC launch program (TCE_ABLATE={sorted(ABLATE)}, TCE_TAPS={int(TAPS)}): "
                   + ("stages are skipped, every result of this process is GARBAGE" if ABLATE else "intermediates are copied out"),
                   RuntimeWarning, stacklevel=2)
 
-
-_TAP_FN = None  # TCE_TAPS diagnostic: the current clip's tap(name, tensor), set by _run_clip
 
 # Diagnostic: when set to a list, run_clip appends (stage name, event recorded on the main stream at the END of the
 # stage) -- tools/stage_times.py (eager mode only).
@@ -95,19 +100,13 @@ class _Fork:
     """Runs a block of launches on a side stream (inside hipGraph capture this becomes a parallel graph branch);
     without a side stream it degenerates to in-order execution on the current stream."""
 
-    def __init__(self, side_stream, after=None):
-        """after: an event already recorded on the forking stream -- the branch then depends on the work up to THAT point
-        only, not on everything issued before the fork (its nodes are still captured / submitted here, in program order)."""
+    def __init__(self, side_stream):
         self.side = side_stream
-        self.after = after
         self.ctx = None
 
     def __enter__(self):
         if self.side is not None:
-            if self.after is not None:
-                self.side.wait_event(self.after)
-            else:
-                self.side.wait_stream(torch.cuda.current_stream())
+            self.side.wait_stream(torch.cuda.current_stream())
             self.ctx = torch.cuda.stream(self.side)
             self.ctx.__enter__()
         return self
@@ -194,115 +193,176 @@ def run_clip(model, frames, text, img_h, img_w, ar, side_arena=None, side_stream
                          shared, select, index)
 
 
-def _run_clip(model, frames, text, img_h, img_w, ar, side_arena=None, side_stream=None, clone_outputs=True, fork2=None,
-              fork3=None, valid=None, groups=1, shared=False, select=None, index=None):
-    """text: (last_hidden_state [L,768], pooler_output [768]) or a callable(alloc) returning them (the RoBERTa
-    forward, run as a parallel branch beside the backbone when a side stream is given).
-    side_arena / side_stream: the decoder (~100 latency-bound launches on 25 rows) runs as a parallel branch
-    beside the pixel decoder's large kernels; it needs its own arena because both branches allocate.
-    clone_outputs=False returns views into the arenas (valid until the arenas are used again): the graph path owns its
-    arenas and copies the outputs out once per replay, so a second copy inside the graph would be wasted.
-    fork2 = (arena, stream): a third concurrent branch for the pixel decoder's stride-4 lateral path (see there).
-    fork3 = ((arena, stream), (arena, stream)): two more for its stride-32 / stride-16 lateral paths (_pixel_decoder)."""
-    cfg, w = model.cfg, model._packed
-    dev = frames.device
-    # Clip groups (groups = G > 1): `frames` holds G independent clips of Tc frames each, back to back.  Every per-frame /
-    # per-token stage simply sees T = G * Tc frames (more rows per launch: the latency-bound stages -- Swin stages 3-4, the text
-    # branch, the token and decoder paths -- are shared by the G clips); the stages that look ACROSS a clip's frames or at its
-    # caption are block-diagonal per clip: the frame tokens' self-attention, the IQT self-attention, the VisionLanguageBlocks'
-    # self-attention, every text cross-attention (one folded weight stream per clip), the decoder's start from the clip's
-    # sentence feature.  Each clip's result is the B = 1 forward's (the reference MIXES the clips of a batch, SURVEY 8e).
-    # shared = True: the G clips are ONE clip with G captions (the expressions of a video): `frames` holds its Tc frames once, the
-    # backbone runs once and its maps are repeated G times; everything after it is the group program above.
-    G = int(groups)
-    Tb, _, H0, W0 = frames.shape  # frames the backbone sees
-    T = Tb * G if shared else Tb
-    if T % G and index is None:
-        raise ValueError("clip group: frames must hold `groups` clips of equal length")
-    # select (the A2D / JHMDB single-frame path, tce_rvos.py:233-243): the backbone sees the clip's Tb frames (Video-Swin's
-    # windows span them), every stage after it only frame `select` -- the reference index_selects the features, their masks and
-    # position maps (frame independent here: same padding in every frame) and continues with t = 1
-    # A group with a selection (select = one index per clip): the backbone sees every frame of the G clips (shared: the one clip's
-    # frames, once); after every stage the rows of frame g*Tc + select[g] of each clip are gathered into a dense [G*hw_i, C_i] map
-    # (tce_copy_segments, one segment per clip and level: pick_segments) and the rest is the group program at T = G, Tc = 1.
-    # index (a group over a frame pool, model.forward_indexed): `frames` holds what the backbone must see -- the distinct frames of
-    # the index tuples (Video-Swin: the distinct tuples' frames) -- and after every stage the rows of each slot's frames are gathered
-    # into the dense [G*Tc*hw_i, C_i] map of the group program, with the selection's mechanism: one table per level
-    # (pool_segments), the copy issued in the arena and on the stream of the map's consumer.
-    sel_many = isinstance(select, (tuple, list)) and G > 1
-    seg_table = None
-    gather = index is not None
-    if gather:
-        if select is not None or shared or valid is not None or G < 2:
-            raise ValueError("index: a group of two or more un-padded clips, without valid_indices")
-        index = tuple(tuple(int(v) for v in t) for t in index)
-        if len(index) != G:
-            raise ValueError(f"index: {G} clips but {len(index)} index tuples")
-        bb_frames, seg_table = pool_segments(index, [(1, 1)] * 4, cfg.num_channels, "clip" if cfg.video else "frame")
-        if len(bb_frames) != Tb:
-            raise ValueError(f"index: the backbone needs {len(bb_frames)} frames, `frames` holds {Tb}")
-        T = G * len(index[0])
-        Tcb = len(index[0])  # frames per clip in front of the backbone (Video-Swin's windows)
-        if not seg_table[0]:  # every slot frame distinct and in order: the backbone's maps ARE the group's maps
-            gather, seg_table = False, None
-    if gather:
-        pass  # T and Tcb are the index's
-    elif sel_many:
-        select = tuple(int(v) for v in select)
-        Tcb = Tb if shared else Tb // G  # frames per clip in front of the backbone
-        if len(select) != G or any(not 0 <= v < Tcb for v in select):
-            raise ValueError("valid_indices: one index per clip of the group, each inside its clip")
-        T = G
-    elif select is not None:
-        if isinstance(select, (tuple, list)) and len(select) == 1:
-            select = select[0]
-        if G != 1 or isinstance(select, (tuple, list)) or not 0 <= int(select) < Tb:
-            raise ValueError("valid_indices: one clip per forward, index inside the clip")
-        select = int(select)
-        T = 1
-    Tc = T // G
-    ar.reset()
-    if side_arena is not None:
-        side_arena.reset()
-    A = ar.alloc
-    sc = model._shape_consts(T, H0, W0, dev, valid)
-    lvl_valid = sc["lvl_valid"]  # per-level (rows, columns) that are not padding, or None
-    sizes, lvl_sizes, S, starts = sc["sizes"], sc["lvl_sizes"], sc["S"], sc["starts"]
-    Q = cfg.num_queries
-    ff = cfg.dim_feedforward
+class _Clip:
+    """The clip (or clip group) in flight: what every stage of its launch program reads -- model, packed weights, shape constants,
+    arenas and streams -- and what one stage leaves for a later one: the text stage's products, the gathered maps of a selection,
+    the deferred stage-0 norm, the handle of the stride-4 lateral branch, the taps.  _run_clip builds it and calls the stages in
+    program order; the methods below issue the launches."""
+
+    def __init__(self, model, frames, text, ar, side_arena, side_stream, fork2, fork3, valid, groups, shared, select, index):
+        cfg = model.cfg
+        self.model, self.cfg, self.w, self.dev, self.text_in = model, cfg, model._packed, frames.device, text
+        # Clip groups (groups = G > 1): `frames` holds G independent clips of Tc frames each, back to back.  Every per-frame /
+        # per-token stage simply sees T = G * Tc frames (more rows per launch: the latency-bound stages -- Swin stages 3-4, the text
+        # branch, the token and decoder paths -- are shared by the G clips); the stages that look ACROSS a clip's frames or at its
+        # caption are block-diagonal per clip: the frame tokens' self-attention, the IQT self-attention, the VisionLanguageBlocks'
+        # self-attention, every text cross-attention (one folded weight stream per clip), the decoder's start from the clip's
+        # sentence feature.  Each clip's result is the B = 1 forward's (the reference MIXES the clips of a batch, SURVEY 8e).
+        # shared = True: the G clips are ONE clip with G captions (the expressions of a video): `frames` holds its Tc frames once, the
+        # backbone runs once and its maps are repeated G times; everything after it is the group program above.
+        G = int(groups)
+        Tb, _, H0, W0 = frames.shape  # frames the backbone sees
+        T = Tb * G if shared else Tb
+        if T % G and index is None:
+            raise ValueError("clip group: frames must hold `groups` clips of equal length")
+        # select (the A2D / JHMDB single-frame path, tce_rvos.py:233-243): the backbone sees the clip's Tb frames (Video-Swin's
+        # windows span them), every stage after it only frame `select` -- the reference index_selects the features, their masks and
+        # position maps (frame independent here: same padding in every frame) and continues with t = 1
+        # A group with a selection (select = one index per clip): the backbone sees every frame of the G clips (shared: the one clip's
+        # frames, once); after every stage the rows of frame g*Tc + select[g] of each clip are gathered into a dense [G*hw_i, C_i] map
+        # (tce_copy_segments, one segment per clip and level: pick_segments) and the rest is the group program at T = G, Tc = 1.
+        # index (a group over a frame pool, model.forward_indexed): `frames` holds what the backbone must see -- the distinct frames of
+        # the index tuples (Video-Swin: the distinct tuples' frames) -- and after every stage the rows of each slot's frames are gathered
+        # into the dense [G*Tc*hw_i, C_i] map of the group program, with the selection's mechanism: one table per level
+        # (pool_segments), the copy issued in the arena and on the stream of the map's consumer.
+        sel_many = isinstance(select, (tuple, list)) and G > 1
+        gather = index is not None
+        Tcb = None  # frames per clip in front of the backbone (Video-Swin's windows), where a gather follows it
+        if gather:
+            if select is not None or shared or valid is not None or G < 2:
+                raise ValueError("index: a group of two or more un-padded clips, without valid_indices")
+            index = tuple(tuple(int(v) for v in t) for t in index)
+            if len(index) != G:
+                raise ValueError(f"index: {G} clips but {len(index)} index tuples")
+            bb_frames, unit_table = pool_segments(index, [(1, 1)] * 4, cfg.num_channels, "clip" if cfg.video else "frame")
+            if len(bb_frames) != Tb:
+                raise ValueError(f"index: the backbone needs {len(bb_frames)} frames, `frames` holds {Tb}")
+            T = G * len(index[0])
+            Tcb = len(index[0])
+            if not unit_table[0]:  # every slot frame distinct and in order: the backbone's maps ARE the group's maps
+                gather = False
+        if gather:
+            pass  # T and Tcb are the index's
+        elif sel_many:
+            select = tuple(int(v) for v in select)
+            Tcb = Tb if shared else Tb // G
+            if len(select) != G or any(not 0 <= v < Tcb for v in select):
+                raise ValueError("valid_indices: one index per clip of the group, each inside its clip")
+            T = G
+        elif select is not None:
+            if isinstance(select, (tuple, list)) and len(select) == 1:
+                select = select[0]
+            if G != 1 or isinstance(select, (tuple, list)) or not 0 <= int(select) < Tb:
+                raise ValueError("valid_indices: one clip per forward, index inside the clip")
+            select = int(select)
+            T = 1
+        self.G, self.T, self.Tc, self.Tb, self.Tcb, self.shared = G, T, T // G, Tb, Tcb, shared
+        self.select, self.sel_many, self.gather = select, sel_many, gather
+        self.many = sel_many or gather  # the maps of the group are gathered from the backbone's
+        ar.reset()
+        if side_arena is not None:
+            side_arena.reset()
+        self.ar, self.side_arena, self.side_stream, self.fork3 = ar, side_arena, side_stream, fork3
+        self.ar2, self.stream2 = fork2 if fork2 is not None else (None, None)
+        self.sc = sc = model._shape_consts(T, H0, W0, self.dev, valid)
+        self.lvl_valid = sc["lvl_valid"]  # per-level (rows, columns) that are not padding, or None
+        self.sizes, self.lvl_sizes, self.S, self.starts = sc["sizes"], sc["lvl_sizes"], sc["S"], sc["starts"]
+        sizes = self.sizes
+        self.seg_table = None
+        if sel_many:
+            self.seg_table = pick_segments(G, Tcb, select, sizes, cfg.num_channels, shared)
+        elif gather:
+            self.seg_table = pool_segments(index, sizes, cfg.num_channels, "clip" if cfg.video else "frame")[1]
+        self.picked = [None] * 4  # a group's selection: the gathered map of stage i, once its consumer's branch has made it
+        self.fused_ok = ops.get_gemm_mode() != "f32"  # the fused kernels ARE split-fp16 arithmetic; exact-fp32 mode = GEMM path
+        # ---- text stage: with a side stream it is a parallel graph branch beside the backbone; its buffers live in the side arena
+        # until the end of the clip.  Its products: caption length L, sentence features, (k, v, folded stream or None, key padding
+        # mask or None) of the fusion site and of the pixel decoder's VisionLanguageBlocks.
+        self.tA = (side_arena if side_arena is not None else ar).alloc
+        self.text_fork = _Fork(side_stream)
+        self.L = self.sent = self.fusion = None
+        self.vl_sites = {}
+        # Capture order = submission order of a replay (the graph's nodes are enqueued in the order they were captured): the ~140
+        # few-microsecond launches of the text branch go in AFTER the first Swin stage's, so the backbone (the critical path)
+        # does not queue behind them (TCE_TEXT_LATE=0: text first).
+        self.text_late = TEXT_LATE and not cfg.is_resnet
+        # ---- input_proj + early fusion of a level (:258-307) needs that level's backbone map and the text only: with the extra
+        # branches of fork3 the two large levels start as soon as their Swin stage is done, beside the later stages (which
+        # work on few tokens); the two small ones follow the backbone, each on its own stream.
+        self.early = (fork3 is not None and not cfg.is_resnet and fork3[0][1] is not None and fork3[1][1] is not None and
+                      side_stream is not None and EARLY_PROJ)
+        self.src = self.memory = self.feats = None  # [T, S, 256]: the encoder sequence / its final state; the backbone's maps
+        self.lvl_forks = []
+        # ---- the stride-4 lateral branch (start_lat1): its handle (fork, tgt), the workgroup cap of its two large launches, and
+        # Swin stage 0's output norm, applied at the head of the branch -- where the map's only consumer runs
+        self.lat1 = None
+        self.pending_norm0 = []
+        self.lat1_cap = LAT1_CUS
+        if self.lat1_cap is None:
+            measured = G == 1 and not cfg.is_resnet and not cfg.video and -(-(T * sizes[0][0] * sizes[0][1]) // 128) >= LAT1_CUS_MIN_BLOCKS
+            self.lat1_cap = LAT1_CUS_DEFAULT if measured else 0
+        self.tok_stream = side_stream if TOKFORK else None  # free between the text join and the decoder fork
+        self.taps = self.tap_pool = None  # TCE_TAPS (bisect aid): copies of intermediates ride out with the outputs
+        self.tap_off = 0
+
     # Few-row kernel (csrc/fewrow.hip): the per-token / per-query projections (a few dozen rows, K = 256) as exact-fp32 launches
     # that serve several projections of the same rows at once (TCE_FEWROW=0: tiled GEMMs).  The LayerNorms stay launches of
     # their own: finishing rows in "the last workgroup" needs an agent-scope release / acquire, on this 8-XCD part an L2
     # write-back + invalidate -- 19 us, more than the launch it would save (profiles/r03_fewrow.txt).
-    FR = ops.fewrow_linear
-
-    def few(rows, site=None):  # TCE_FEWROW_SITES: comma list of msda,ftf2,ftf3,dec,text (default: all)
+    def few(self, rows, site=None):  # TCE_FEWROW_SITES: comma list of msda,ftf2,ftf3,dec,text (default: all)
         if FEWROW_SITES is not None and site not in FEWROW_SITES:
             return False
         return FEWROW_OK and rows <= ops.FEWROW_MAX_ROWS
 
-    # ------------------------------------------------------------------ text stage (tce_rvos.py:406-424, FeatureResizer
-    # :616-635) and everything that depends on the text alone: the projected keys / values of the five text
-    # cross-attention sites and their folded weight streams (csrc/ffn.hip, tce_xattn_fused_f32).  With a side stream it
-    # is a parallel graph branch beside the backbone; its buffers live in the side arena until the end of the clip.
-    tA = (side_arena if side_arena is not None else ar).alloc
-    # The text branch needs nothing the backbone produces.  TCE_TEXT_EARLY_EDGE=1 gives it a graph edge back to the START of
-    # the clip (its nodes still issued after Swin stage 0's), so that it runs beside stage 0 instead of after it -- measured
-    # SLOWER, 8.09 vs 6.90 ms per clip (A/B twice in one gpurun call, profiles/r04_text_early_edge.txt): its ~150 short launches
-    # interleave with stage 0's long ones on the same hardware queues and stretch the critical path.  Off by default.
-    clip_start = None
-    if side_stream is not None and TEXT_EARLY_EDGE:
-        clip_start = torch.cuda.Event()
-        clip_start.record()
-    text_fork = _Fork(side_stream, after=clip_start)
-    L = fk = fv = fpk = fkm = sent = None
-    vl_sites = {}
-    text_in = text
+    def ln_(self, x, pre):
+        w = self.w
+        return ops.layernorm(x, w[pre + ".weight"], w[pre + ".bias"], 1e-5, out=x)
 
-    def text_stage():
-        nonlocal L, fk, fv, fpk, fkm, sent
+    def tap(self, name, t):
+        """TCE_TAPS: a copy of `t` rides out in out["taps"] (the pool is set up at the head of the encoder: a branch started before
+        it -- the early stride-4 lateral -- is not tapped)."""
+        if self.taps is not None:
+            n = t.numel()
+            buf = self.tap_pool[self.tap_off:self.tap_off + n]
+            self.tap_off += n
+            self.taps[name] = ops.tile(t.reshape(-1), 1, out=buf).view(t.shape)
+
+    def ffn(self, x, M, pre, l1="linear1", l2="linear2", ar=None, norm=None, group="encoder.ffn"):
+        if "ffn:" + group in ABLATE:
+            return
+        with self.model.arith(group):
+            self._ffn(x, M, pre, l1, l2, self.ar if ar is None else ar, norm)
+
+    def _ffn(self, x, M, pre, l1, l2, ar, norm):
+        """x <- LN_norm?(x + W2 relu(W1 x)) (in place).  Large M: one fused launch, the [M, 2048] hidden stays on chip
+        (csrc/ffn.hip); small M (a workgroup walks the whole hidden extent alone): two GEMMs + LayerNorm."""
+        w, ff = self.w, self.cfg.dim_feedforward
+        pk = w.get(pre + "ffn:pk:" + ops.get_gemm_mode()) if self.fused_ok else None
+        if pk is not None and M >= FFN_FUSED_MIN_ROWS:
+            nws, ncnt = ops.ffn_split_need(M, D, ff, ACT_RELU)
+            m1 = ar.mark()
+            ops.ffn_fused(x, pk, w[pre + l2 + ".bias"], ff, ACT_RELU, M=M,
+                          ln_out=(w[norm + ".weight"], w[norm + ".bias"]) if norm else None,
+                          split=(ar.alloc(nws), ar.alloc_flags(ncnt)) if nws else None)
+            ar.release(m1)
+            return
+        A = ar.alloc
+        m1 = ar.mark()
+        hdn = A(M, ff)
+        gemm_ex(x, w[pre + l1 + ".weight"], hdn, M, ff, D, D, D, ff, bias=w[pre + l1 + ".bias"], act=ACT_RELU)
+        sk = ops.splitk_for(M, D, ff)  # the decoder / frame-token FFNs run on a few dozen rows
+        gemm_ex(hdn, w[pre + l2 + ".weight"], x, M, D, ff, ff, ff, D, bias=w[pre + l2 + ".bias"], res=x, ldres=D,
+                res_mode=RES_ADD, splitk=sk, ws=A(sk * M * D) if sk > 1 else None,
+                ln=(w[norm + ".weight"], w[norm + ".bias"]) if norm else None)  # the norm rides in the split-K reduction
+        ar.release(m1)
+
+    def text_stage(self):
+        """Text stage (tce_rvos.py:406-424, FeatureResizer :616-635) and everything that depends on the text alone: the projected
+        keys / values of the five text cross-attention sites and their folded weight streams (csrc/ffn.hip, tce_xattn_fused_f32)."""
+        model, cfg, w, G, Tc, tA, text_in = self.model, self.cfg, self.w, self.G, self.Tc, self.tA, self.text_in
+        few, FR = self.few, ops.fewrow_linear
         rag = None
-        with text_fork, model.arith("text"):
+        with self.text_fork, model.arith("text"):
             if "text" in ABLATE and callable(text_in):  # diagnostic: the RoBERTa layers skipped (garbage features)
                 text_hidden, text_pooled = tA(32, cfg.text_hidden), tA(cfg.text_hidden)
             else:
@@ -314,21 +374,21 @@ def _run_clip(model, frames, text, img_h, img_w, ar, side_arena=None, side_strea
             GL = text_hidden.shape[0]  # G captions of L tokens, caption-major
             if GL % G:
                 raise ValueError("clip group: the text features must hold `groups` captions of equal length")
-            L = GL // G
+            self.L = L = GL // G
             TH = cfg.text_hidden
             if text_pooled.data_ptr() == text_hidden.data_ptr() + GL * TH * 4 and text_hidden.is_contiguous():
                 # the text plan hands hidden states and pooled vectors over as one [G*L + G, 768] tensor: one resizer launch pair
                 tmp = _lin(tA, text_hidden, GL + G, TH, w["resizer.fc.weight"], w["resizer.fc.bias"], D)
                 both = ops.layernorm(tmp, w["resizer.layer_norm.weight"], w["resizer.layer_norm.bias"], 1e-12, out=tA(GL + G, D))
-                text, sent = both[:GL], both[GL:]
+                text, self.sent = both[:GL], both[GL:]
             else:
                 tmp = _lin(tA, text_hidden, GL, TH, w["resizer.fc.weight"], w["resizer.fc.bias"], D)
                 text = ops.layernorm(tmp, w["resizer.layer_norm.weight"], w["resizer.layer_norm.bias"], 1e-12, out=tA(GL, D))
                 tmp = _lin(tA, text_pooled, G, TH, w["resizer.fc.weight"], w["resizer.fc.bias"], D)
-                sent = ops.layernorm(tmp, w["resizer.layer_norm.weight"], w["resizer.layer_norm.bias"], 1e-12, out=tA(G, D))
+                self.sent = ops.layernorm(tmp, w["resizer.layer_norm.weight"], w["resizer.layer_norm.bias"], 1e-12, out=tA(G, D))
             if rag is None:
                 lens = tkm = None
-                text_pos, pos_rows, pos_stride = model._text_pos(L, dev), L, 0  # one position map shared by the captions
+                text_pos, pos_rows, pos_stride = model._text_pos(L, self.dev), L, 0  # one position map shared by the captions
             else:
                 lens, tkm, text_pos = rag
                 pos_rows, pos_stride = GL, L * D  # each caption's own map (normalised by its length)
@@ -352,88 +412,21 @@ def _run_clip(model, frames, text, img_h, img_w, ar, side_arena=None, side_strea
                         pk = ops.xattn_pack(k, v, w[pre + "q.wT:x"], w[pre + "out_proj.weight"], L, tA, batch=G, lens=lens)
                 return k, v, pk, tkm
 
-            fk, fv, fpk, fkm = text_site("fusion_module.multihead_attn.", Tc * lvl_sizes[0][0] * lvl_sizes[0][1], "input_proj")
+            lvl0 = self.lvl_sizes[0]
+            self.fusion = text_site("fusion_module.multihead_attn.", Tc * lvl0[0] * lvl0[1], "input_proj")
             if cfg.vlblock:
                 for stage in (4, 3, 2, 1):
-                    h_, w_ = sizes[stage - 1]
-                    vl_sites[stage] = text_site(f"pixel_decoder.cross_attn_{stage}.multihead_attn.", Tc * h_ * w_, "pixel.xattn")
+                    h_, w_ = self.sizes[stage - 1]
+                    self.vl_sites[stage] = text_site(f"pixel_decoder.cross_attn_{stage}.multihead_attn.", Tc * h_ * w_, "pixel.xattn")
 
+    def input_level(self, l, feat, A):
+        with self.model.arith("input_proj"):
+            self._input_level(l, feat, A)
 
-    # Capture order = submission order of a replay (the graph's nodes are enqueued in the order they were captured): the ~140
-    # few-microsecond launches of the text branch go in AFTER the first Swin stage's, so the backbone (the critical path)
-    # does not queue behind them (TCE_TEXT_LATE=0: text first).
-    text_late = TEXT_LATE and not cfg.is_resnet
-    if not text_late:
-        text_stage()
-
-    _stage("start")
-    # ------------------------------------------------------------------ backbone
-    def ln_(x, pre):
-        return ops.layernorm(x, w[pre + ".weight"], w[pre + ".bias"], 1e-5, out=x)
-
-    fused_ok = ops.get_gemm_mode() != "f32"  # the fused kernels ARE split-fp16 arithmetic; exact-fp32 mode = GEMM path
-
-    def ffn(x, M, pre, l1="linear1", l2="linear2", ar=ar, norm=None, group="encoder.ffn"):
-        if "ffn:" + group in ABLATE:
-            return
-        with model.arith(group):
-            _ffn(x, M, pre, l1, l2, ar, norm)
-
-    def _ffn(x, M, pre, l1, l2, ar, norm):
-        """x <- LN_norm?(x + W2 relu(W1 x)) (in place).  Large M: one fused launch, the [M, 2048] hidden stays on chip
-        (csrc/ffn.hip); small M (a workgroup walks the whole hidden extent alone): two GEMMs + LayerNorm."""
-        pk = w.get(pre + "ffn:pk:" + ops.get_gemm_mode()) if fused_ok else None
-        if pk is not None and M >= FFN_FUSED_MIN_ROWS:
-            nws, ncnt = ops.ffn_split_need(M, D, ff, ACT_RELU)
-            m1 = ar.mark()
-            ops.ffn_fused(x, pk, w[pre + l2 + ".bias"], ff, ACT_RELU, M=M,
-                          ln_out=(w[norm + ".weight"], w[norm + ".bias"]) if norm else None,
-                          split=(ar.alloc(nws), ar.alloc_flags(ncnt)) if nws else None)
-            ar.release(m1)
-            return
-        A = ar.alloc
-        m1 = ar.mark()
-        hdn = A(M, ff)
-        gemm_ex(x, w[pre + l1 + ".weight"], hdn, M, ff, D, D, D, ff, bias=w[pre + l1 + ".bias"], act=ACT_RELU)
-        sk = ops.splitk_for(M, D, ff)  # the decoder / frame-token FFNs run on a few dozen rows
-        gemm_ex(hdn, w[pre + l2 + ".weight"], x, M, D, ff, ff, ff, D, bias=w[pre + l2 + ".bias"], res=x, ldres=D,
-                res_mode=RES_ADD, splitk=sk, ws=A(sk * M * D) if sk > 1 else None,
-                ln=(w[norm + ".weight"], w[norm + ".bias"]) if norm else None)  # the norm rides in the split-K reduction
-        ar.release(m1)
-
-    def chained_ffn(pre, group, M, norm, A, sMid):
-        """The FFN stage of a cross-attention -> FFN chain launch (ops.xattn_fused(ffn=...)), or None where the two run as two
-        launches: the chain needs the chain-ordered W1 stream (model._pack: both site groups in one arithmetic) and the row count
-        of the fused FFN route.  `mid` (the attention stage's rows, the FFN's residual) is scratch of the caller's arena."""
-        if not (ops.XATTN_FFN_CHAIN and fused_ok and M >= FFN_FUSED_MIN_ROWS) or "ffn:" + group in ABLATE:
-            return None
-        pkc = w.get(pre + "ffn:pkc:" + ops.get_gemm_mode())
-        if pkc is None or model.mode_of(group) != ops.get_gemm_mode():
-            return None
-        return (pkc, w[pre + "linear2.bias"], ff, (w[norm + ".weight"], w[norm + ".bias"]), A(M, D), sMid)
-
-    ffn.chain = chained_ffn  # travels with `ffn` into the pixel decoder's branches
-
-    # input_proj + early fusion of a level (:258-307) needs that level's backbone map and the text only: with the extra
-    # branches of fork3 the two large levels start as soon as their Swin stage is done, beside the later stages (which
-    # work on few tokens); the two small ones follow the backbone, each on its own stream.
-    chs = cfg.num_channels
-    if sel_many:
-        seg_table = pick_segments(G, Tcb, select, sizes, chs, shared)
-    elif gather:
-        seg_table = pool_segments(index, sizes, chs, "clip" if cfg.video else "frame")[1]
-    many = sel_many or gather  # the maps of the group are gathered from the backbone's
-    early = (fork3 is not None and not cfg.is_resnet and fork3[0][1] is not None and fork3[1][1] is not None and
-             side_stream is not None and EARLY_PROJ)
-    src = A(T * S, D) if early else None  # [T, S, 256]: the encoder sequence
-    lvl_forks = []
-
-    def input_level(l, feat, A):
-        with model.arith("input_proj"):
-            _input_level(l, feat, A)
-
-    def _input_level(l, feat, A):
-        h, ww = lvl_sizes[l]
+    def _input_level(self, l, feat, A):
+        w, T, Tc, G, S, sizes, chs, src = self.w, self.T, self.Tc, self.G, self.S, self.sizes, self.cfg.num_channels, self.src
+        fk, fv, fpk, fkm = self.fusion
+        h, ww = self.lvl_sizes[l]
         hw = h * ww
         if l < 3:
             s = _lin(A, feat, T * hw, chs[1 + l], w[f"input_proj.{l}.0.weight"], w[f"input_proj.{l}.0.bias"], D)
@@ -449,170 +442,140 @@ def _run_clip(model, frames, text, img_h, img_w, ar, side_arena=None, side_strea
         s = ops.groupnorm_cl(s, w[f"input_proj.{l}.1.weight"], w[f"input_proj.{l}.1.bias"], T, hw, D, 32, alloc=A)
         if fpk is not None and Tc * hw >= ops.XATTN_MIN_ROWS:
             # src_l = s * MHA(s, text): straight into the level slice of [T, S, 256]; the Tc frames of a clip share its stream
-            ops.xattn_fused(s, fpk, w["fusion_module.multihead_attn.out_proj.bias"], hw, src[starts[l]:], res_mode=RES_MUL,
+            ops.xattn_fused(s, fpk, w["fusion_module.multihead_attn.out_proj.bias"], hw, src[self.starts[l]:], res_mode=RES_MUL,
                             batch=T, sX=hw * D, sRes=hw * D, sOut=S * D, per_batch_weights=G > 1, w_div=Tc)
         else:
+            L = self.L
             q = _lin(A, s, T * hw, D, w["fusion_module.multihead_attn.q.w"], w["fusion_module.multihead_attn.q.b"], D)
             att = A(T * hw, D)
             ops.mha_core(q, fk, fv, G, NH, Tc * hw, L, D, D, D, Tc * hw * D, L * D, L * D, att, D, Tc * hw * D, kmask=fkm)
             # src_l = s * out_proj(att), written straight into the level slice of [T, S, 256]
-            gemm_ex(att, w["fusion_module.multihead_attn.out_proj.weight"], src[starts[l]:], hw, D, D, D, D, D,
+            gemm_ex(att, w["fusion_module.multihead_attn.out_proj.weight"], src[self.starts[l]:], hw, D, D, D, D, D,
                     bias=w["fusion_module.multihead_attn.out_proj.bias"], res=s, ldres=D, res_mode=RES_MUL, batch=T,
                     sA=hw * D, sC=S * D, sRes=hw * D)
 
-    ar2, stream2 = fork2 if fork2 is not None else (None, None)
-    lat1 = None
-    if early:
-        for arx, _ in fork3:
-            arx.reset()
-
-    picked = [None] * 4  # a group's selection: the gathered map of stage i, once its consumer's branch has made it
-
-    def pick(feat, i, alloc=None):
+    def pick(self, feat, i, alloc=None):
         """the selected frame's rows of stage i's map (valid_indices), else the map.  A group's selection is a gather: allocated
         from `alloc` (default: the main arena) and issued on the current stream -- where the map's consumer runs."""
-        if select is None and not gather:
+        select = self.select
+        if select is None and not self.gather:
             return feat
-        hw_i = sizes[i][0] * sizes[i][1]
-        if not many:
+        hw_i = self.sizes[i][0] * self.sizes[i][1]
+        if not self.many:
             return feat[select * hw_i:(select + 1) * hw_i]
-        picked[i] = ops.copy_row_segments(feat, seg_table[i], (alloc or A)(T * hw_i, chs[i]))
-        return picked[i]
+        self.picked[i] = ops.copy_row_segments(feat, self.seg_table[i], (alloc or self.ar.alloc)(self.T * hw_i, self.cfg.num_channels[i]))
+        return self.picked[i]
 
-    lat1_cap = LAT1_CUS
-    if lat1_cap is None:
-        measured = G == 1 and not cfg.is_resnet and not cfg.video and -(-(T * sizes[0][0] * sizes[0][1]) // 128) >= LAT1_CUS_MIN_BLOCKS
-        lat1_cap = LAT1_CUS_DEFAULT if measured else 0
-    pending_norm0 = []  # stage 0's output norm, applied at the head of the stride-4 lateral branch (start_lat1)
-
-    def start_lat1(feat0=None, wait_text=False):
+    def start_lat1(self, wait_text=False):
+        """Starts the stride-4 lateral branch on its own stream and arena (fork2): self.lat1 = (fork, tgt), joined by the pixel
+        decoder when its top-down chain reaches stride 4."""
+        ar2 = self.ar2
         ar2.reset()
-        lat1_fork = _Fork(stream2)
+        lat1_fork = _Fork(self.stream2)
         with lat1_fork:
-            while pending_norm0:
-                pending_norm0.pop()()  # Swin stage 0's output norm, here where its only consumer runs
-            if many and picked[0] is None:  # a group's selection: stage 0's gather, in its consumer's arena and stream
-                if feat0 is None:
-                    feats[0] = pick(feats[0], 0, ar2.alloc)
-                else:
-                    feat0 = pick(feat0, 0, ar2.alloc)
+            while self.pending_norm0:
+                self.pending_norm0.pop()()  # Swin stage 0's output norm, here where its only consumer runs
+            if self.many and self.picked[0] is None:  # a group's selection: stage 0's gather, in its consumer's arena and stream
+                self.feats[0] = self.pick(self.feats[0], 0, ar2.alloc)
             if wait_text:
-                text_fork.join()  # the branch's stream waits for the text branch (the folded stream of its cross-attention)
-            with ops.ffn_wg_cap(lat1_cap):  # its cross-attention fold and its FFN: the only launches of the branch that read the cap
-                return (lat1_fork, _lateral(model, sc, feats if feat0 is None else [feat0], None, vl_sites, T, L, ffn, ln_, 1, ar2, G))
+                self.text_fork.join()  # the branch's stream waits for the text branch (the folded stream of its cross-attention)
+            with ops.ffn_wg_cap(self.lat1_cap):  # its cross-attention fold and its FFN: the only launches of the branch that read the cap
+                self.lat1 = (lat1_fork, _lateral(self, 1, ar2))
 
-    def on_stage(i, feat, finish=None):
-        nonlocal lat1
-        if i == 0 and text_late:
-            text_stage()
+    def on_stage(self, i, feat, finish=None):
+        """_swin_backbone's callback: stage i's map is final, or its output norm is handed over as `finish` (norm_handed_over)."""
+        if i == 0 and self.text_late:
+            self.text_stage()
         if i == 0 and finish is not None:
-            pending_norm0.append(finish)
-        if not many:
-            feat = pick(feat, i)
-        if i == 0 and LAT1_AT == "text" and ar2 is not None and stream2 is not None:
-            lat1 = start_lat1(feat, wait_text=True)  # TCE_LAT1_AT=text: from the text join on, beside Swin stages 1-3
-        if early:
-            if i in (1, 2):
-                    arx, stx = fork3[i - 1]
-                    fk_ = _Fork(stx)
-                    with fk_:
-                        if finish is not None:
-                            finish()  # the stage's output norm, in this branch
-                        if many:
-                            feat = pick(feat, i, arx.alloc)  # this level's gather, in its consumer's arena and stream
-                        text_fork.join()  # this level's stream waits for the text branch (keys / values of the fusion)
-                        input_level(i - 1, feat, arx.alloc)
-                    lvl_forks.append(fk_)
-    if DEFER_OUT_NORM:
-        # stage 0's map is read by the stride-4 lateral branch only (started later, on its own stream); stages 1 / 2 by their
-        # level's early input projection (forked right here); stage 3 by the main stream itself
-        on_stage.defers = lambda i: select is None and not gather and ((i == 0 and ar2 is not None and stream2 is not None) or (i in (1, 2) and early))
-    if cfg.is_resnet:
-        with model.arith("backbone.merge"):  # a ResNet is convolutions only: one site group
-            feats = _resnet_backbone(model, frames, ar, sizes, rep=G if shared and not sel_many else 1)
-    else:
-        feats = _swin_backbone(model, frames, ar, sizes, on_stage, Tb // Tcb if gather else (1 if shared else G),
-                               rep=G if shared and not sel_many else 1)
-    if many:
-        # stages whose consumer's branch has gathered them keep that map; stage 0 waits for the stride-4 lateral branch (start_lat1)
-        # where that branch exists; the others are read by the main stream's own work
-        later0 = ar2 is not None and stream2 is not None
-        feats = [picked[i] if picked[i] is not None else (f if i == 0 and later0 else pick(f, i)) for i, f in enumerate(feats)]
-    else:
-        feats = [pick(f, i) for i, f in enumerate(feats)]
+            self.pending_norm0.append(finish)
+        if not self.many:
+            feat = self.pick(feat, i)
+        if i == 0 and LAT1_AT == "text" and self.ar2 is not None and self.stream2 is not None:
+            self.feats = [feat]  # (stage 0's map is all the branch reads of the backbone)
+            self.start_lat1(wait_text=True)  # TCE_LAT1_AT=text: from the text join on, beside Swin stages 1-3
+        if self.early and i in (1, 2):
+            arx, stx = self.fork3[i - 1]
+            fk_ = _Fork(stx)
+            with fk_:
+                if finish is not None:
+                    finish()  # the stage's output norm, in this branch
+                if self.many:
+                    feat = self.pick(feat, i, arx.alloc)  # this level's gather, in its consumer's arena and stream
+                self.text_fork.join()  # this level's stream waits for the text branch (keys / values of the fusion)
+                self.input_level(i - 1, feat, arx.alloc)
+            self.lvl_forks.append(fk_)
 
-    _stage("backbone")
-    text_fork.join()
-    _stage("text join")
+    def norm_handed_over(self):
+        """The Swin stages whose output norm runs in the consumer's branch instead of on the backbone's stream (TCE_DEFER_OUT_NORM):
+        stage 0's map is read by the stride-4 lateral branch only (started later, on its own stream); stages 1 / 2 by their
+        level's early input projection (forked in on_stage); stage 3 by the main stream itself."""
+        if not DEFER_OUT_NORM or self.select is not None or self.gather:
+            return ()
+        return ((0,) if self.ar2 is not None and self.stream2 is not None else ()) + ((1, 2) if self.early else ())
 
-    # ------------------------------------------------------------------ pixel decoder, stride-4 lateral branch, EARLY
-    # adapter_1 + GroupNorm + VisionLanguageBlock at stride 4 read the backbone's C2 map and the text only -- not the
-    # encoder memory (segmentation.py:187-196 with the backbone feature as the last lateral input) -- so this millisecond
-    # of work is a parallel graph branch, joined when the top-down chain reaches stride 4.
-    # When it starts is a trade: its long kernels (72000-row cross-attention, FFN, GEMMs) slow down whatever runs beside
-    # them, and it must be done when the chain reaches stride 4.  Measured at config 2 (ms per clip): right after Swin
-    # stage 0 8.09, after the backbone 7.44, after encoder layer 0 / 1 / 2 / 3 (of 4) 7.41 / 7.37 / 7.27 / 7.71 ->
-    # one encoder layer before the end ("backbone" / "encN" override for experiments).
-    # With its two 72000-row launches capped to a few dozen CUs (lat1_cap: one persistent workgroup per CU, the other CUs stay free
-    # for the short critical kernels) the trade changes: started right after the backbone it runs beside the whole encoder, and
-    # the clip goes 6.19 -> 5.97 ms at 64 CUs (start x cap table and confirmation pairs: profiles/r10_lat1_capped.txt).
-    lat1_when = LAT1_AT or (f"enc{cfg.enc_layers - 2}" if cfg.enc_layers >= 2 and lat1_cap <= 0 else "backbone")
-    if ar2 is not None and stream2 is not None and lat1 is None and lat1_when in ("backbone", "text"):
-        lat1 = start_lat1()  # ("text" without a Swin stage callback -- a ResNet backbone -- starts here too)
-    # ------------------------------------------------------------------ input_proj + early fusion (:258-307)
-    # The four levels are independent (they write disjoint slices of src).  Without the early start: level 0 on the main
-    # stream, levels 1-3 as one parallel branch on the side stream (idle here: the text branch has joined, the decoder
-    # branch has not started).  No buffer is released before the branches have joined.
-    if src is None:
-        src = A(T * S, D)
-    m_levels = ar.mark()
-    if early:
-        todo = ((2, side_stream), (3, None))
-    else:
-        todo = ((1, side_stream), (2, side_stream), (3, side_stream), (0, None))
-    for l, lvl_stream in todo:
-        fk_ = _Fork(lvl_stream)
-        lvl_forks.append(fk_)
-        with fk_:
-            input_level(l, feats[min(1 + l, 3)], A)
-    for fk_ in lvl_forks:
-        fk_.join()
-    ar.release(m_levels)
+    def backbone(self, frames):
+        model, cfg, G, shared = self.model, self.cfg, self.G, self.shared
+        self.src = self.ar.alloc(self.T * self.S, D) if self.early else None
+        if self.early:
+            for arx, _ in self.fork3:
+                arx.reset()
+        rep = G if shared and not self.sel_many else 1
+        if cfg.is_resnet:
+            with model.arith("backbone.merge"):  # a ResNet is convolutions only: one site group
+                feats = _resnet_backbone(model, frames, self.ar, self.sizes, rep=rep)
+        else:
+            feats = _swin_backbone(model, frames, self.ar, self.sizes, self.on_stage, self.Tb // self.Tcb if self.gather else (1 if shared else G),
+                                   rep=rep, norm_handed_over=self.norm_handed_over())
+        if self.many:
+            # stages whose consumer's branch has gathered them keep that map; stage 0 waits for the stride-4 lateral branch (start_lat1)
+            # where that branch exists; the others are read by the main stream's own work
+            later0 = self.ar2 is not None and self.stream2 is not None
+            picked = self.picked
+            self.feats = [picked[i] if picked[i] is not None else (f if i == 0 and later0 else self.pick(f, i)) for i, f in enumerate(feats)]
+        else:
+            self.feats = [self.pick(f, i) for i, f in enumerate(feats)]
 
-    _stage("input_proj + fusion")
-    # ------------------------------------------------------------------ encoder (:611-627)
-    lvl_pos, enc_ref = sc["lvl_pos"], sc["enc_ref"]
-    Fk = cfg.f_token
-    if Fk > 0:
-        token = ops.tile(w["transformer.encoder.memory_bus"], T, out=A(T * Fk, D))
-        tpos = w["transformer.encoder.memory_pos"]
-        # norm1 / norm2 of the frame-token layer ride in the prologue of the few-row launch that follows them (qk|v of the token
-        # self-attention; k|v of the pixel <- token attention): the normalised rows ping-pong between two buffers (a prologue
-        # cannot normalise in place: other workgroups still read the rows).  2 launches fewer per layer on the path between layers.
-        ftf_fuse_ln = FTF_LN_FUSE and D == 256 and all(few(T * Fk, site) for site in ("msda", "ftf2", "ftf3"))
-        token_alt = A(T * Fk, D) if ftf_fuse_ln else None
-    # free between the text join and the decoder fork
-    tok_stream = side_stream if TOKFORK else None
+    def input_levels(self):
+        """input_proj + early fusion (:258-307).  The four levels are independent (they write disjoint slices of src).  Without the
+        early start: level 0 on the main stream, levels 1-3 as one parallel branch on the side stream (idle here: the text branch
+        has joined, the decoder branch has not started).  No buffer is released before the branches have joined."""
+        ar, side_stream = self.ar, self.side_stream
+        if self.src is None:
+            self.src = ar.alloc(self.T * self.S, D)
+        m_levels = ar.mark()
+        if self.early:
+            todo = ((2, side_stream), (3, None))
+        else:
+            todo = ((1, side_stream), (2, side_stream), (3, side_stream), (0, None))
+        for l, lvl_stream in todo:
+            fk_ = _Fork(lvl_stream)
+            self.lvl_forks.append(fk_)
+            with fk_:
+                self.input_level(l, self.feats[min(1 + l, 3)], ar.alloc)
+        for fk_ in self.lvl_forks:
+            fk_.join()
+        ar.release(m_levels)
 
-    def msda(pre, query, q_rows, q_per_frame, q_pos, q_pos_shared, value_src, ref, ref_dim, ref_per_frame, resid,
-             ar=ar, norm=None, small_fork=None, group="encoder.msda", defer_norm=False):
-        with model.arith(group):
-            _msda(pre, query, q_rows, q_per_frame, q_pos, q_pos_shared, value_src, ref, ref_dim, ref_per_frame, resid, ar, norm,
-                  small_fork, defer_norm)
+    def msda(self, pre, query, q_rows, q_per_frame, q_pos, q_pos_shared, value_src, ref, ref_dim, ref_per_frame, resid,
+             ar=None, norm=None, small_fork=None, group="encoder.msda"):
+        with self.model.arith(group):
+            self._msda(pre, query, q_rows, q_per_frame, q_pos, q_pos_shared, value_src, ref, ref_dim, ref_per_frame, resid,
+                       self.ar if ar is None else ar, norm, small_fork)
 
-    def _msda(pre, query, q_rows, q_per_frame, q_pos, q_pos_shared, value_src, ref, ref_dim, ref_per_frame, resid,
-              ar, norm, small_fork, defer_norm=False):
+    def _msda(self, pre, query, q_rows, q_per_frame, q_pos, q_pos_shared, value_src, ref, ref_dim, ref_per_frame, resid,
+              ar, norm, small_fork):
         """resid <- LN_norm?(resid + output_proj(MSDA(query + q_pos, ref, value_proj(value_src)))).  query [T*q_per_frame, D].
         ref: the reference points, or (W, b) of the Linear whose sigmoid gives them (evaluated beside value_proj when
         small_fork is a _Fork: the few-row projections of the frame-token path run as a parallel branch next to the large
         value projection)."""
+        w, T, S, lvl_sizes, lvl_valid, FR = self.w, self.T, self.S, self.lvl_sizes, self.lvl_valid, ops.fewrow_linear
         A = ar.alloc
         m1 = ar.mark()
         proj = A(q_rows, 384)
         vw = w[pre + "value_proj.weight"]
         # a few queries per frame (frame tokens, decoder queries): "sample, then project" (csrc/msda.hip, msda_fewq_raw_kernel)
         use_raw = ops.MSDA_RAW and q_per_frame <= 64 and T * q_per_frame * NH <= 65536 and vw.is_contiguous()
-        if few(q_rows, "msda") and q_pos_shared and norm:
+        if self.few(q_rows, "msda") and q_pos_shared and norm:
             # a few dozen queries: offsets|weights (+ the reference points' Linear + sigmoid) in one launch
             ref_t = ref
             segs = [(w[pre + "offaw.weight"], w[pre + "offaw.bias"], proj, 384, 384, True, ops.FR_NONE)]
@@ -635,8 +598,7 @@ def _run_clip(model, frames, text, img_h, img_w, ar, side_arena=None, side_strea
                                       out=A(q_rows, D), valid_hw=lvl_valid)
             FR(samp, q_rows, D, [(w[pre + "output_proj.weight"], w[pre + "output_proj.bias"], resid, D, D, False, ops.FR_NONE)],
                res=resid, ldres=D)
-            if not defer_norm:  # (deferred: the LayerNorm rides in the prologue of the next few-row launch on these rows)
-                ln_(resid, norm)
+            self.ln_(resid, norm)
             ar.release(m1)
             return
         if isinstance(ref, tuple):
@@ -680,140 +642,124 @@ def _run_clip(model, frames, text, img_h, img_w, ar, side_arena=None, side_strea
                     res=resid, ldres=D, res_mode=RES_ADD)
         ar.release(m1)
 
-    taps = {} if TAPS else None  # bisect aid: copies of intermediates ride out with the outputs
-
-    tap_pool = A(cfg.enc_layers * (16 * T * max(Fk, 1) * D + 3 * T * S * D) + cfg.dec_layers * T * Q * D +
-                 2 * T * sum(h_ * w_ for h_, w_ in sizes) * D) if taps is not None else None  # persistent (base level)
-    tap_off = [0]
-
-    def tap(name, t):
-        if taps is not None:
-            n = t.numel()
-            buf = tap_pool[tap_off[0]:tap_off[0] + n]
-            tap_off[0] += n
-            taps[name] = ops.tile(t.reshape(-1), 1, out=buf).view(t.shape)
-
-    global _TAP_FN  # module-level functions (_lateral) tap through it; diagnostic runs only
-    _TAP_FN = tap if taps is not None else None
-
-    for i in range(cfg.enc_layers):
-        lp = f"transformer.encoder.layers.{i}."
-        if Fk > 0:
-            fp = lp + "ftoken_layers."
-            m0 = ar.mark()
-            # The token path is ~16 launches on T*F (= 40) rows, each a kernel boundary long and on the critical path
-            # between two encoder layers: independent ones run as parallel graph branches (tok_stream).
-            # (1) tokens gather from their frame by MSDA (:447-454); reference points / offsets beside value_proj
-            token_ref = (w[fp + "reference_points.weight"], w[fp + "reference_points.bias"])
+    def frame_token_layer(self, i, fp, token, tpos, src):
+        """FrameTokenLayer i (tce_deformable_transformer.py:443-491) on the frame tokens [T*F, D] and the encoder sequence `src`.
+        The token path is ~16 launches on T*F (= 40) rows, each a kernel boundary long and on the critical path between two
+        encoder layers: independent ones run as parallel graph branches (tok_stream)."""
+        model, w, ar, T, Tc, G, S, tok_stream = self.model, self.w, self.ar, self.T, self.Tc, self.G, self.S, self.tok_stream
+        few, tap, FR, A, Fk = self.few, self.tap, ops.fewrow_linear, ar.alloc, self.cfg.f_token
+        lvl_pos = self.sc["lvl_pos"]
+        m0 = ar.mark()
+        # (1) tokens gather from their frame by MSDA (:447-454); reference points / offsets beside value_proj
+        token_ref = (w[fp + "reference_points.weight"], w[fp + "reference_points.bias"])
+        if "ftf_tok" not in ABLATE:
+            self.msda(fp + "token_frame_atten.", token, T * Fk, Fk, tpos, True, src, token_ref, 2, True, token,
+                      norm=fp + "norm1", small_fork=_Fork(tok_stream))
+        tap(f"L{i}.token1", token)
+        # (2) all T*F tokens attend to each other (:463-469)
+        with model.arith("encoder.ftf"):
+            R = T * Fk
             if "ftf_tok" not in ABLATE:
-                msda(fp + "token_frame_atten.", token, T * Fk, Fk, tpos, True, src, token_ref, 2, True, token,
-                     norm=fp + "norm1", small_fork=_Fork(tok_stream), defer_norm=ftf_fuse_ln)
-            if not ftf_fuse_ln:
-                tap(f"L{i}.token1", token)
-            # (2) all T*F tokens attend to each other (:463-469)
-            with model.arith("encoder.ftf"):
-                R = T * Fk
-                if "ftf_tok" not in ABLATE:
-                    pre = fp + "token_self_atten."
-                    qk = A(R, 2 * D)
-                    if few(R, "ftf2"):  # q|k (token + position) and v in one launch
-                        v = A(R, D)
-                        segs = [(w[pre + "qk.w"], w[pre + "qk.b"], qk, 2 * D, 2 * D, True, ops.FR_NONE),
-                                (w[pre + "v.w"], w[pre + "v.b"], v, D, D, False, ops.FR_NONE)]
-                        if ftf_fuse_ln:  # token <- norm1(token) in this launch's prologue
-                            FR(token, R, D, segs, a2=tpos, lda2=D, a2_rows=Fk, ln_in=(w[fp + "norm1.weight"], w[fp + "norm1.bias"]),
-                               xn_out=token_alt)
-                            token, token_alt = token_alt, token
-                            tap(f"L{i}.token1", token)
-                        else:
-                            FR(token, R, D, segs, a2=tpos, lda2=D, a2_rows=Fk)
-                    else:
-                        fk_v = _Fork(tok_stream)
-                        with fk_v:
-                            v = _lin(A, token, R, D, w[pre + "v.w"], w[pre + "v.b"], D)
-                        gemm_ex(token, w[pre + "qk.w"], qk, Fk, 2 * D, D, D, D, 2 * D, bias=w[pre + "qk.b"], a2=tpos, lda2=D,
-                                batch=T, sA=Fk * D, sA2=0, sC=Fk * 2 * D)
-                        fk_v.join()
-                    att = A(R, D)
-                    tap(f"L{i}.qk2", qk)
-                    tap(f"L{i}.v2", v)
-                    Rc = Tc * Fk  # a clip's tokens attend to each other (:463-469), never to another clip's
-                    ops.mha_core(qk, qk[:, D:], v, G, NH, Rc, Rc, 2 * D, 2 * D, D, Rc * 2 * D, Rc * 2 * D, Rc * D, att, D, Rc * D)
-                    tap(f"L{i}.att2", att)
-                    if few(R, "ftf2"):
-                        FR(att, R, D, [(w[pre + "out_proj.weight"], w[pre + "out_proj.bias"], token, D, D, False, ops.FR_NONE)],
-                           res=token, ldres=D)
-                    else:
-                        gemm_ex(att, w[pre + "out_proj.weight"], token, R, D, D, D, D, D, bias=w[pre + "out_proj.bias"],
-                                res=token, ldres=D, res_mode=RES_ADD)
-                    if not ftf_fuse_ln:
-                        ln_(token, fp + "norm2")
-                if not ftf_fuse_ln:
-                    tap(f"L{i}.token2", token)
-                # (3) every pixel attends to the F tokens of its own frame (:480-484)
-                pre = fp + "frame_token_atten."
-                k = A(R, D)
-                if few(R, "ftf3"):
+                pre = fp + "token_self_atten."
+                qk = A(R, 2 * D)
+                if few(R, "ftf2"):  # q|k (token + position) and v in one launch
                     v = A(R, D)
-                    segs = [(w[pre + "k.w"], w[pre + "k.b"], k, D, D, True, ops.FR_NONE),
-                            (w[pre + "v.w"], w[pre + "v.b"], v, D, D, False, ops.FR_NONE)]
-                    if ftf_fuse_ln and "ftf_tok" not in ABLATE:  # token <- norm2(token) in this launch's prologue
-                        FR(token, R, D, segs, a2=tpos, lda2=D, a2_rows=Fk, ln_in=(w[fp + "norm2.weight"], w[fp + "norm2.bias"]),
-                           xn_out=token_alt)
-                        token, token_alt = token_alt, token
-                        tap(f"L{i}.token2", token)
-                    else:
-                        FR(token, R, D, segs, a2=tpos, lda2=D, a2_rows=Fk)
+                    FR(token, R, D, [(w[pre + "qk.w"], w[pre + "qk.b"], qk, 2 * D, 2 * D, True, ops.FR_NONE),
+                                     (w[pre + "v.w"], w[pre + "v.b"], v, D, D, False, ops.FR_NONE)], a2=tpos, lda2=D, a2_rows=Fk)
                 else:
                     fk_v = _Fork(tok_stream)
                     with fk_v:
                         v = _lin(A, token, R, D, w[pre + "v.w"], w[pre + "v.b"], D)
-                    gemm_ex(token, w[pre + "k.w"], k, Fk, D, D, D, D, D, bias=w[pre + "k.b"], a2=tpos, lda2=D, batch=T,
-                            sA=Fk * D, sA2=0, sC=Fk * D)
+                    gemm_ex(token, w[pre + "qk.w"], qk, Fk, 2 * D, D, D, D, 2 * D, bias=w[pre + "qk.b"], a2=tpos, lda2=D,
+                            batch=T, sA=Fk * D, sA2=0, sC=Fk * 2 * D)
                     fk_v.join()
-            tap(f"L{i}.k3", k)
-            tap(f"L{i}.v3", v)
-            chained = None
-            with model.arith("encoder.ftf_x"):
-                if Fk == 8 and fused_ok and T * S >= ops.XATTN_MIN_ROWS:
-                    # q-proj -> attention over the frame's 8 tokens -> out-proj -> + src -> norm3 in one token-stationary
-                    # launch (the keys / values differ per frame: one folded weight stream per frame)
-                    pk = ops.xattn_pack(k, v, w[pre + "q.wT:x"], w[pre + "out_proj.weight"], Fk, A, group=8, batch=T)
-                    chained = chained_ffn(fp, "encoder.ffn", T * S, fp + "norm4", A, S * D)
-                    ops.xattn_fused(src, pk, w[pre + "out_proj.bias"], S, src, a2=lvl_pos,
-                                    ln_out=(w[fp + "norm3.weight"], w[fp + "norm3.bias"]), batch=T, sX=S * D, sOut=S * D,
-                                    group=8, per_batch_weights=True, ffn=chained)
+                att = A(R, D)
+                tap(f"L{i}.qk2", qk)
+                tap(f"L{i}.v2", v)
+                Rc = Tc * Fk  # a clip's tokens attend to each other (:463-469), never to another clip's
+                ops.mha_core(qk, qk[:, D:], v, G, NH, Rc, Rc, 2 * D, 2 * D, D, Rc * 2 * D, Rc * 2 * D, Rc * D, att, D, Rc * D)
+                tap(f"L{i}.att2", att)
+                if few(R, "ftf2"):
+                    FR(att, R, D, [(w[pre + "out_proj.weight"], w[pre + "out_proj.bias"], token, D, D, False, ops.FR_NONE)],
+                       res=token, ldres=D)
                 else:
-                    q = A(T * S, D)
-                    gemm_ex(src, w[pre + "q.w"], q, S, D, D, D, D, D, bias=w[pre + "q.b"], a2=lvl_pos, lda2=D, batch=T,
-                            sA=S * D, sA2=0, sC=S * D)
-                    att = A(T * S, D)
-                    ops.mha_core(q, k, v, T, NH, S, Fk, D, D, D, S * D, Fk * D, Fk * D, att, D, S * D)
-                    _proj_res_ln(att, w[pre + "out_proj.weight"], w[pre + "out_proj.bias"], src, T * S, w[fp + "norm3.weight"],
-                                 w[fp + "norm3.bias"])
-            tap(f"L{i}.src3", src if chained is None else chained[4])
-            ar.release(m0)
-            # (4) FFN over all pixels (:489-491)
-            if chained is None:
-                ffn(src, T * S, fp, norm=fp + "norm4")
-            tap(f"L{i}.src4", src)
-        if "enc_msda" not in ABLATE:
-            # the offsets|weights projection (src + pos) and the value projection (src) are independent 24100-row GEMMs of 1.1 and
-            # 0.74 workgroup rounds: side by side they pack into 1.9 rounds instead of 3 (TCE_ENCFORK=0: one after the other)
-            msda(lp + "self_attn.", src, T * S, S, lvl_pos, True, src, enc_ref, 2, False, src, norm=lp + "norm1",
-                 small_fork=_Fork(tok_stream) if ENCFORK else None)
-        ffn(src, T * S, lp, norm=lp + "norm2")
-        tap(f"L{i}.src6", src)
-        if ar2 is not None and stream2 is not None and lat1_when == f"enc{i}":
-            lat1 = start_lat1()
-    memory = src
+                    gemm_ex(att, w[pre + "out_proj.weight"], token, R, D, D, D, D, D, bias=w[pre + "out_proj.bias"],
+                            res=token, ldres=D, res_mode=RES_ADD)
+                self.ln_(token, fp + "norm2")
+            tap(f"L{i}.token2", token)
+            # (3) every pixel attends to the F tokens of its own frame (:480-484)
+            pre = fp + "frame_token_atten."
+            k = A(R, D)
+            if few(R, "ftf3"):
+                v = A(R, D)
+                FR(token, R, D, [(w[pre + "k.w"], w[pre + "k.b"], k, D, D, True, ops.FR_NONE),
+                                 (w[pre + "v.w"], w[pre + "v.b"], v, D, D, False, ops.FR_NONE)], a2=tpos, lda2=D, a2_rows=Fk)
+            else:
+                fk_v = _Fork(tok_stream)
+                with fk_v:
+                    v = _lin(A, token, R, D, w[pre + "v.w"], w[pre + "v.b"], D)
+                gemm_ex(token, w[pre + "k.w"], k, Fk, D, D, D, D, D, bias=w[pre + "k.b"], a2=tpos, lda2=D, batch=T,
+                        sA=Fk * D, sA2=0, sC=Fk * D)
+                fk_v.join()
+        tap(f"L{i}.k3", k)
+        tap(f"L{i}.v3", v)
+        with model.arith("encoder.ftf_x"):
+            if Fk == 8 and self.fused_ok and T * S >= ops.XATTN_MIN_ROWS:
+                # q-proj -> attention over the frame's 8 tokens -> out-proj -> + src -> norm3 in one token-stationary
+                # launch (the keys / values differ per frame: one folded weight stream per frame)
+                pk = ops.xattn_pack(k, v, w[pre + "q.wT:x"], w[pre + "out_proj.weight"], Fk, A, group=8, batch=T)
+                ops.xattn_fused(src, pk, w[pre + "out_proj.bias"], S, src, a2=lvl_pos,
+                                ln_out=(w[fp + "norm3.weight"], w[fp + "norm3.bias"]), batch=T, sX=S * D, sOut=S * D,
+                                group=8, per_batch_weights=True)
+            else:
+                q = A(T * S, D)
+                gemm_ex(src, w[pre + "q.w"], q, S, D, D, D, D, D, bias=w[pre + "q.b"], a2=lvl_pos, lda2=D, batch=T,
+                        sA=S * D, sA2=0, sC=S * D)
+                att = A(T * S, D)
+                ops.mha_core(q, k, v, T, NH, S, Fk, D, D, D, S * D, Fk * D, Fk * D, att, D, S * D)
+                _proj_res_ln(att, w[pre + "out_proj.weight"], w[pre + "out_proj.bias"], src, T * S, w[fp + "norm3.weight"],
+                             w[fp + "norm3.bias"])
+        tap(f"L{i}.src3", src)
+        ar.release(m0)
+        # (4) FFN over all pixels (:489-491)
+        self.ffn(src, T * S, fp, norm=fp + "norm4")
+        tap(f"L{i}.src4", src)
 
-    _stage("encoder")
-    # ------------------------------------------------------------------ decoder (:721-790) + heads (:330-365)
-    nl = cfg.dec_layers
-    dar = side_arena if side_arena is not None else ar
+    def encoder(self, lat1_when):
+        """Encoder (:611-627): per layer the frame-token layer, deformable self-attention and the FFN, in place on src; leaves
+        self.memory.  lat1_when = "encN": the stride-4 lateral branch starts after layer N."""
+        cfg, w, sc, ar, T, S = self.cfg, self.w, self.sc, self.ar, self.T, self.S
+        A, src = ar.alloc, self.src
+        lvl_pos, enc_ref = sc["lvl_pos"], sc["enc_ref"]
+        Fk = cfg.f_token
+        if Fk > 0:
+            token = ops.tile(w["transformer.encoder.memory_bus"], T, out=A(T * Fk, D))
+            tpos = w["transformer.encoder.memory_pos"]
+        if TAPS:
+            self.taps = {}
+            self.tap_pool = A(cfg.enc_layers * (16 * T * max(Fk, 1) * D + 3 * T * S * D) + cfg.dec_layers * T * cfg.num_queries * D +
+                              2 * T * sum(h_ * w_ for h_, w_ in self.sizes) * D)  # persistent (base level)
+        for i in range(cfg.enc_layers):
+            lp = f"transformer.encoder.layers.{i}."
+            if Fk > 0:
+                self.frame_token_layer(i, lp + "ftoken_layers.", token, tpos, src)
+            if "enc_msda" not in ABLATE:
+                # the offsets|weights projection (src + pos) and the value projection (src) are independent 24100-row GEMMs of 1.1 and
+                # 0.74 workgroup rounds: side by side they pack into 1.9 rounds instead of 3 (TCE_ENCFORK=0: one after the other)
+                self.msda(lp + "self_attn.", src, T * S, S, lvl_pos, True, src, enc_ref, 2, False, src, norm=lp + "norm1",
+                          small_fork=_Fork(self.tok_stream) if ENCFORK else None)
+            self.ffn(src, T * S, lp, norm=lp + "norm2")
+            self.tap(f"L{i}.src6", src)
+            if self.ar2 is not None and self.stream2 is not None and lat1_when == f"enc{i}":
+                self.start_lat1()
+        self.memory = src
 
-    def decoder_branch():
+    def decoder_branch(self):
+        """Decoder (:721-790) + heads (:330-365) in the decoder's arena: (hs, boxes, mask reference points, their width, logits,
+        visibility logits or None), each [layers, T*Q, .]."""
+        cfg, w, T, Tc, G, memory = self.cfg, self.w, self.T, self.Tc, self.G, self.memory
+        few, FR, Q = self.few, ops.fewrow_linear, cfg.num_queries
+        dar = self.side_arena if self.side_arena is not None else self.ar
         A = dar.alloc
         nl = cfg.dec_layers
         hs = A(nl, T * Q, D)
@@ -831,7 +777,7 @@ def _run_clip(model, frames, text, img_h, img_w, ar, side_arena=None, side_strea
         init_ref = ops.tile(r, T, out=A(T * Q, 2))
         tgt = A(T * Q, D)  # every (frame, query) of a clip starts from the clip's sentence feature
         for g_ in range(G):
-            ops.tile(sent[g_], Tc * Q, out=tgt[g_ * Tc * Q:(g_ + 1) * Tc * Q])
+            ops.tile(self.sent[g_], Tc * Q, out=tgt[g_ * Tc * Q:(g_ + 1) * Tc * Q])
         ref, ref_dim = init_ref, 2
         for lid in range(0 if "decoder" not in ABLATE else nl, nl):
             lp = f"transformer.decoder.layers.{lid}."
@@ -864,10 +810,10 @@ def _run_clip(model, frames, text, img_h, img_w, ar, side_arena=None, side_strea
             else:
                 gemm_ex(att, w[pre + "out_proj.weight"], tgt, T * Q, D, D, D, D, D, bias=w[pre + "out_proj.bias"], res=prev,
                         ldres=D, res_mode=RES_ADD)
-            ln_(tgt, lp + "norm2")
-            msda(lp + "cross_attn.", tgt, T * Q, Q, qpos, True, memory, ref, ref_dim, True, tgt, ar=dar, norm=lp + "norm1",
-                 group="decoder")
-            ffn(tgt, T * Q, lp, ar=dar, norm=lp + "norm3", group="decoder")
+            self.ln_(tgt, lp + "norm2")
+            self.msda(lp + "cross_attn.", tgt, T * Q, Q, qpos, True, memory, ref, ref_dim, True, tgt, ar=dar, norm=lp + "norm1",
+                      group="decoder")
+            self.ffn(tgt, T * Q, lp, ar=dar, norm=lp + "norm3", group="decoder")
             if cfg.with_box_refine:
                 bp = f"bbox_embed.{lid}.layers."
                 t1, t2 = A(T * Q, D), A(T * Q, D)
@@ -916,91 +862,145 @@ def _run_clip(model, frames, text, img_h, img_w, ar, side_arena=None, side_strea
         ops.box_refine(t3, refs2, out=inter_ref)
         return hs, inter_ref, refs2, 2, logits, vis
 
-    npar = cfg.num_gen_params
-    dec_fork = _Fork(side_stream if side_arena is not None else None)
-    with dec_fork, model.arith("decoder"):
-        hs, boxes, mask_refs, ref_ld, logits, vis = decoder_branch()
-        tap("dec.hs", hs)
-        # controller MLP + parameter packing of the dynamic mask head (:371-373, 536-559): depend on hs only, so they
-        # ride in the decoder branch instead of the main chain's tail
-        dA = dar.alloc
-        c1 = dA(nl * T * Q, D)
-        c2 = dA(nl * T * Q, D)
-        if few(nl * T * Q, "dec"):
-            params = dA(nl * T * Q, npar)
-            FR(hs, nl * T * Q, D, [(w["controller.layers.0.weight"], w["controller.layers.0.bias"], c1, D, D, False, ops.FR_RELU)])
-            FR(c1, nl * T * Q, D, [(w["controller.layers.1.weight"], w["controller.layers.1.bias"], c2, D, D, False, ops.FR_RELU)])
-            FR(c2, nl * T * Q, D, [(w["controller.layers.2.weight"], w["controller.layers.2.bias"], params, npar, npar, False,
-                                    ops.FR_NONE)])
+    def mask_params(self, hs):
+        """Controller MLP + parameter packing of the dynamic mask head (:371-373, 536-559): depend on hs only, so they ride in
+        the decoder branch instead of the main chain's tail.  Returns (first-layer weights [T, nl*Q*8, mask_dim], the packed
+        tail, the contrastive scores or None)."""
+        cfg, w, T, S, FR = self.cfg, self.w, self.T, self.S, ops.fewrow_linear
+        dA = (self.side_arena if self.side_arena is not None else self.ar).alloc
+        R, npar = cfg.dec_layers * T * cfg.num_queries, cfg.num_gen_params
+        c1 = dA(R, D)
+        c2 = dA(R, D)
+        if self.few(R, "dec"):
+            params = dA(R, npar)
+            FR(hs, R, D, [(w["controller.layers.0.weight"], w["controller.layers.0.bias"], c1, D, D, False, ops.FR_RELU)])
+            FR(c1, R, D, [(w["controller.layers.1.weight"], w["controller.layers.1.bias"], c2, D, D, False, ops.FR_RELU)])
+            FR(c2, R, D, [(w["controller.layers.2.weight"], w["controller.layers.2.bias"], params, npar, npar, False, ops.FR_NONE)])
         else:
-            gemm_ex(hs, w["controller.layers.0.weight"], c1, nl * T * Q, D, D, D, D, D, bias=w["controller.layers.0.bias"],
-                    act=ACT_RELU)
-            gemm_ex(c1, w["controller.layers.1.weight"], c2, nl * T * Q, D, D, D, D, D, bias=w["controller.layers.1.bias"],
-                    act=ACT_RELU)
-            params = _lin(dA, c2, nl * T * Q, D, w["controller.layers.2.weight"], w["controller.layers.2.bias"], npar)
-        w0f = dA(T, nl * Q * 8, cfg.mask_dim)
-        tail = dA(nl, T * Q, 112)
-        ops.mask_pack(params, nl, T, Q, cfg.mask_dim, w0f, tail)
+            gemm_ex(hs, w["controller.layers.0.weight"], c1, R, D, D, D, D, D, bias=w["controller.layers.0.bias"], act=ACT_RELU)
+            gemm_ex(c1, w["controller.layers.1.weight"], c2, R, D, D, D, D, D, bias=w["controller.layers.1.bias"], act=ACT_RELU)
+            params = _lin(dA, c2, R, D, w["controller.layers.2.weight"], w["controller.layers.2.bias"], npar)
+        w0f = dA(T, cfg.dec_layers * cfg.num_queries * 8, cfg.mask_dim)
+        tail = dA(cfg.dec_layers, T * cfg.num_queries, 112)
+        ops.mask_pack(params, cfg.dec_layers, T, cfg.num_queries, cfg.mask_dim, w0f, tail)
         contrast = None
         if cfg.contrastive:  # contrastive_cal (tce_rvos.py:512-521): cos(mean over the S positions of a frame's memory, sentence feature)
             contrast = dA(T)
-            ops.contrastive(memory, sent, T, S, D, Tc, contrast, dA(T * 32 * D))
+            ops.contrastive(self.memory, self.sent, T, S, D, self.Tc, contrast, dA(T * 32 * D))
+        return w0f, tail, contrast
 
+    def mask_head(self, mask_feats, w0f, tail, mask_refs, ref_ld, img_h, img_w):
+        """Dynamic mask head (:371-380, 426-510): masks [layers, T, Q, h4, w4] in the main arena."""
+        cfg, T, A = self.cfg, self.T, self.ar.alloc
+        nl, Q = cfg.dec_layers, cfg.num_queries
+        h4, w4 = self.sizes[0]
+        gmat = A(T, h4 * w4, nl * Q * 8)
+        with self.model.arith("mask_head"):
+            ops.gemm_batched(mask_feats.view(T, h4 * w4, cfg.mask_dim), w0f, gmat)
+        masks = A(nl, T, Q, h4, w4)
+        ops.mask_tail(gmat, tail, mask_refs, ref_ld, masks, nl, T, Q, h4, w4, img_h, img_w, 4)
+        return masks
+
+    def outputs(self, logits, boxes, masks, vis, contrast, mask_refs, ref_ld, clone_outputs):
+        """The output dict (:360-393): clones that leave the arenas, or views into them (clone_outputs=False)."""
+        cfg, T, S = self.cfg, self.T, self.S
+        Q, K, nl = cfg.num_queries, cfg.num_classes, cfg.dec_layers
+        h4, w4 = self.sizes[0]
+        keep = (lambda t: t.clone()) if clone_outputs else (lambda t: t)
+        out = {
+            "pred_logits": keep(logits[-1].reshape(1, T, Q, K)),
+            "pred_boxes": keep(boxes[-1].reshape(1, T, Q, 4)),
+            "pred_masks": keep(masks[-1].reshape(1, T, Q, h4, w4)),
+        }
+        if vis is not None:
+            out["pred_visible"] = keep(vis[-1].reshape(1, T, Q, 1))
+        if contrast is not None:
+            out["contrastive"] = keep(contrast.reshape(1, T))  # [b, t] (a clip group: the clips' frames back to back, like every output)
+        if cfg.aux_loss:
+            out["aux_outputs"] = [{"pred_logits": keep(logits[i].reshape(1, T, Q, K)),
+                                   "pred_boxes": keep(boxes[i].reshape(1, T, Q, 4)),
+                                   "pred_masks": keep(masks[i].reshape(1, T, Q, h4, w4))} for i in range(nl - 1)]
+            if vis is not None:  # _set_aux_loss with outputs_visible (tce_rvos.py:396-404)
+                for i in range(nl - 1):
+                    out["aux_outputs"][i]["pred_visible"] = keep(vis[i].reshape(1, T, Q, 1))
+        if not self.model.training:
+            out["reference_points"] = keep(mask_refs[-2].reshape(1, T, Q, ref_ld)[..., :2])
+        out["memory"] = keep(self.memory.reshape(T, S, D))
+        if self.taps:
+            out["taps"] = [{k_: keep(v_) for k_, v_ in self.taps.items()}]
+        return out
+
+
+def _run_clip(model, frames, text, img_h, img_w, ar, side_arena=None, side_stream=None, clone_outputs=True, fork2=None,
+              fork3=None, valid=None, groups=1, shared=False, select=None, index=None):
+    """text: (last_hidden_state [L,768], pooler_output [768]) or a callable(alloc) returning them (the RoBERTa
+    forward, run as a parallel branch beside the backbone when a side stream is given).
+    side_arena / side_stream: the decoder (~100 latency-bound launches on 25 rows) runs as a parallel branch
+    beside the pixel decoder's large kernels; it needs its own arena because both branches allocate.
+    clone_outputs=False returns views into the arenas (valid until the arenas are used again): the graph path owns its
+    arenas and copies the outputs out once per replay, so a second copy inside the graph would be wasted.
+    fork2 = (arena, stream): a third concurrent branch for the pixel decoder's stride-4 lateral path (see there).
+    fork3 = ((arena, stream), (arena, stream)): two more for its stride-32 / stride-16 lateral paths (_pixel_decoder).
+    The program is the stage order below; the stages are _Clip's methods and share their state through it."""
+    c = _Clip(model, frames, text, ar, side_arena, side_stream, fork2, fork3, valid, groups, shared, select, index)
+    cfg = c.cfg
+    if not c.text_late:
+        c.text_stage()  # (else: after Swin stage 0's launches, from on_stage)
+    _stage("start")
+    c.backbone(frames)
+    _stage("backbone")
+    c.text_fork.join()
+    _stage("text join")
+    # ------------------------------------------------------------------ pixel decoder, stride-4 lateral branch, EARLY
+    # adapter_1 + GroupNorm + VisionLanguageBlock at stride 4 read the backbone's C2 map and the text only -- not the
+    # encoder memory (segmentation.py:187-196 with the backbone feature as the last lateral input) -- so this millisecond
+    # of work is a parallel graph branch, joined when the top-down chain reaches stride 4.
+    # When it starts is a trade: its long kernels (72000-row cross-attention, FFN, GEMMs) slow down whatever runs beside
+    # them, and it must be done when the chain reaches stride 4.  Measured at config 2 (ms per clip): right after Swin
+    # stage 0 8.09, after the backbone 7.44, after encoder layer 0 / 1 / 2 / 3 (of 4) 7.41 / 7.37 / 7.27 / 7.71 ->
+    # one encoder layer before the end ("backbone" / "encN" override for experiments).
+    # With its two 72000-row launches capped to a few dozen CUs (lat1_cap: one persistent workgroup per CU, the other CUs stay free
+    # for the short critical kernels) the trade changes: started right after the backbone it runs beside the whole encoder, and
+    # the clip goes 6.19 -> 5.97 ms at 64 CUs (start x cap table and confirmation pairs: profiles/r10_lat1_capped.txt).
+    lat1_when = LAT1_AT or (f"enc{cfg.enc_layers - 2}" if cfg.enc_layers >= 2 and c.lat1_cap <= 0 else "backbone")
+    if c.ar2 is not None and c.stream2 is not None and c.lat1 is None and lat1_when in ("backbone", "text"):
+        c.start_lat1()  # ("text" without a Swin stage callback -- a ResNet backbone -- starts here too)
+    c.input_levels()
+    _stage("input_proj + fusion")
+    c.encoder(lat1_when)
+    _stage("encoder")
+    dec_fork = _Fork(side_stream if side_arena is not None else None)
+    with dec_fork, model.arith("decoder"):
+        hs, boxes, mask_refs, ref_ld, logits, vis = c.decoder_branch()
+        c.tap("dec.hs", hs)
+        w0f, tail, contrast = c.mask_params(hs)
     _stage("decoder fork")
     # ------------------------------------------------------------------ pixel decoder (segmentation.py:175-296)
-    while pending_norm0:  # (the stride-4 lateral branch was never started: its input's norm runs here, before the decoder reads it)
-        pending_norm0.pop()()
-    if many and picked[0] is None:  # (and a group's selection of stage 0 with it)
-        feats[0] = pick(feats[0], 0)
-    mask_feats = _pixel_decoder(model, ar, sc, feats, memory, vl_sites, T, L, ffn, ln_, lat1=lat1, par=fork3, G=G)
+    while c.pending_norm0:  # (the stride-4 lateral branch was never started: its input's norm runs here, before the decoder reads it)
+        c.pending_norm0.pop()()
+    if c.many and c.picked[0] is None:  # (and a group's selection of stage 0 with it)
+        c.feats[0] = c.pick(c.feats[0], 0)
+    mask_feats = _pixel_decoder(c)
     dec_fork.join()
-
     _stage("pixel decoder")
-    # ------------------------------------------------------------------ dynamic mask head (:371-380, 426-510)
-    h4, w4 = sizes[0]
     m0 = ar.mark()
-    gmat = A(T, h4 * w4, nl * Q * 8)  # (not `G`: the closures above read the clip-group count G late-bound)
-    with model.arith("mask_head"):
-        ops.gemm_batched(mask_feats.view(T, h4 * w4, cfg.mask_dim), w0f, gmat)
-    masks = A(nl, T, Q, h4, w4)
-    ops.mask_tail(gmat, tail, mask_refs, ref_ld, masks, nl, T, Q, h4, w4, img_h, img_w, 4)
-
+    masks = c.mask_head(mask_feats, w0f, tail, mask_refs, ref_ld, img_h, img_w)
     _stage("mask head (+ decoder join)")
-    # ------------------------------------------------------------------ output dict (:360-393); leave the arena
-    K = cfg.num_classes
-    keep = (lambda t: t.clone()) if clone_outputs else (lambda t: t)
-    out = {
-        "pred_logits": keep(logits[-1].reshape(1, T, Q, K)),
-        "pred_boxes": keep(boxes[-1].reshape(1, T, Q, 4)),
-        "pred_masks": keep(masks[-1].reshape(1, T, Q, h4, w4)),
-    }
-    if vis is not None:
-        out["pred_visible"] = keep(vis[-1].reshape(1, T, Q, 1))
-    if contrast is not None:
-        out["contrastive"] = keep(contrast.reshape(1, T))  # [b, t] (a clip group: the clips' frames back to back, like every output)
-    if cfg.aux_loss:
-        out["aux_outputs"] = [{"pred_logits": keep(logits[i].reshape(1, T, Q, K)),
-                               "pred_boxes": keep(boxes[i].reshape(1, T, Q, 4)),
-                               "pred_masks": keep(masks[i].reshape(1, T, Q, h4, w4))} for i in range(nl - 1)]
-        if vis is not None:  # _set_aux_loss with outputs_visible (tce_rvos.py:396-404)
-            for i in range(nl - 1):
-                out["aux_outputs"][i]["pred_visible"] = keep(vis[i].reshape(1, T, Q, 1))
-    if not model.training:
-        out["reference_points"] = keep(mask_refs[-2].reshape(1, T, Q, ref_ld)[..., :2])
-    out["memory"] = keep(memory.reshape(T, S, D))
-    if taps:
-        out["taps"] = [{k_: keep(v_) for k_, v_ in taps.items()}]
+    out = c.outputs(logits, boxes, masks, vis, contrast, mask_refs, ref_ld, clone_outputs)  # leaves the arena
     ar.release(m0)
     return out
 
 
-def _swin_backbone(model, frames, ar, sizes, on_stage=None, G=1, rep=1):
+
+
+def _swin_backbone(model, frames, ar, sizes, on_stage=None, G=1, rep=1, norm_handed_over=()):
     """swin_transformer.py:595-617: returns the four normed stage maps, token-major [T*h*w, C_i].
     Video-Swin (video_swin_transformer.py:678-697): same program with the 3-D window kernel, the (1,4,4) patch
     conv applied per frame, stage outputs taken before the merge and WITHOUT an output norm.
     G > 1 (a clip group): the 2-D windows never leave a frame, so the G clips are simply more frames; the 3-D windows span a
     clip's frames, so the 3-D window kernel is launched once per clip on that clip's rows.
-    rep > 1 (one clip, `rep` captions): every returned map holds the stage's map `rep` times, back to back."""
+    rep > 1 (one clip, `rep` captions): every returned map holds the stage's map `rep` times, back to back.
+    norm_handed_over: the stages whose output norm is not applied here but handed to on_stage as `finish`."""
     cfg, w = model.cfg, model._packed
     A = ar.alloc
     T = frames.shape[0]
@@ -1094,9 +1094,7 @@ def _swin_backbone(model, frames, ar, sizes, on_stage=None, G=1, rep=1):
                 if rep > 1:
                     ops.tile(out_i[:ntok], rep - 1, out=out_i[ntok:])
             # a consumer that runs as a parallel branch applies it there (off the backbone's critical path: 8-10 us per stage)
-            if on_stage is not None and getattr(on_stage, "defers", None) is not None and on_stage.defers(i):
-                pass
-            else:
+            if on_stage is None or i not in norm_handed_over:
                 finish()
                 finish = None
             feats.append(out_i)
@@ -1158,12 +1156,12 @@ def _resnet_backbone(model, frames, ar, sizes, rep=1):
     return full
 
 
-def _lateral(model, sc, feats, memory, vl_sites, T, L, ffn, ln_, stage, arx, G=1):
+def _lateral(c, stage, arx):
     """Lateral branch of one FPN level (segmentation.py:187-196,326-377): 1x1 adapter + GroupNorm(8) + VisionLanguageBlock.
     Returns tgt [T*hw, 256] allocated in `arx` (temporaries released, tgt stays).  Stage 1 reads the backbone map
-    (memory may be None), stages 2-4 the encoder memory."""
-    cfg, w = model.cfg, model._packed
-    sizes, S, starts = sc["sizes"], sc["S"], sc["starts"]
+    (c.memory may be None), stages 2-4 the encoder memory."""
+    model, cfg, w, sc, T, G, L = c.model, c.cfg, c.w, c.sc, c.T, c.G, c.L
+    sizes, S, starts = c.sizes, c.S, c.starts
     pd = "pixel_decoder."
     A = arx.alloc
     h, ww = sizes[stage - 1]
@@ -1174,11 +1172,11 @@ def _lateral(model, sc, feats, memory, vl_sites, T, L, ffn, ln_, stage, arx, G=1
     with model.arith("pixel.conv"):
         if stage > 1:
             l = stage - 2  # encoder level index: stage 4 <-> level 2 (32x)
-            gemm_ex(memory[starts[l]:], w[f"{pd}adapter_{stage}.weight"], vis, hw, D, D, D, D, D, batch=T, sA=S * D,
+            gemm_ex(c.memory[starts[l]:], w[f"{pd}adapter_{stage}.weight"], vis, hw, D, D, D, D, D, batch=T, sA=S * D,
                     sC=hw * D)
         else:
             c0 = cfg.num_channels[0]
-            gemm_ex(feats[0], w[f"{pd}adapter_1.weight"], vis, T * hw, D, c0, c0, c0, D)
+            gemm_ex(c.feats[0], w[f"{pd}adapter_1.weight"], vis, T * hw, D, c0, c0, c0, D)
     m1 = arx.mark()
     tgt = ops.groupnorm_cl(vis, w[f"{pd}adapter_{stage}.norm.weight"], w[f"{pd}adapter_{stage}.norm.bias"], T, hw, D, 8,
                            out=vis, alloc=A)
@@ -1220,21 +1218,19 @@ def _lateral(model, sc, feats, memory, vl_sites, T, L, ffn, ln_, stage, arx, G=1
                     ldres=D, res_mode=RES_ADD)
         arx.release(m1)
     if not normed:
-        ln_(tgt, bp + "norm1")
+        c.ln_(tgt, bp + "norm1")
     # text cross-attention (:366-371)
     pre = bp + "multihead_attn."
     with model.arith("pixel.xattn"):
         m1 = arx.mark()
-        tk, tv, pk, tkm = vl_sites[stage]
+        tk, tv, pk, tkm = c.vl_sites[stage]
         Mc = (T // G) * hw  # rows of one clip
-        chained = None
         if pk is not None:
             # q-proj -> attention over the text keys -> out-proj -> + tgt -> norm2 in one token-stationary launch (one batch entry
-            # and one folded weight stream per clip); with the FFN + norm3 behind it in the same launch where chained_ffn allows
-            chained = ffn.chain(bp, "pixel.ffn", T * hw, bp + "norm3", A, Mc * D)
+            # and one folded weight stream per clip)
             ops.xattn_fused(tgt, pk, w[pre + "out_proj.bias"], Mc, tgt, a2=pos, a2_rows=hw,
                             ln_out=(w[bp + "norm2.weight"], w[bp + "norm2.bias"]), batch=G, sX=Mc * D, sOut=Mc * D,
-                            per_batch_weights=G > 1, ffn=chained)
+                            per_batch_weights=G > 1)
         else:
             q = A(T * hw, D)
             gemm_ex(tgt, w[pre + "q.w"], q, hw, D, D, D, D, D, bias=w[pre + "q.b"], a2=pos, lda2=D, batch=T, sA=hw * D,
@@ -1244,54 +1240,47 @@ def _lateral(model, sc, feats, memory, vl_sites, T, L, ffn, ln_, stage, arx, G=1
             _proj_res_ln(att, w[pre + "out_proj.weight"], w[pre + "out_proj.bias"], tgt, T * hw, w[bp + "norm2.weight"],
                          w[bp + "norm2.bias"])
         arx.release(m1)
-    if chained is None:
-        ffn(tgt, T * hw, bp, norm=bp + "norm3", ar=arx, group="pixel.ffn")
-    if _TAP_FN is not None:
-        _TAP_FN(f"vl{stage}", tgt)  # the VisionLanguageBlock's output (segmentation.py:326-377)
+    c.ffn(tgt, T * hw, bp, norm=bp + "norm3", ar=arx, group="pixel.ffn")
+    c.tap(f"vl{stage}", tgt)  # the VisionLanguageBlock's output (segmentation.py:326-377)
     return tgt
 
 
-
-def _pixel_decoder(model, ar, sc, feats, memory, vl_sites, T, L, ffn, ln_, lat1=None, par=None, G=1):
+def _pixel_decoder(c):
     """CrossModalFPNDecoder.forward: top-down FPN with a VisionLanguageBlock at every level.
 
     The lateral branch of a level (_lateral) depends only on its input map and the text; only the top-down merge + 3x3
-    convolution chain is sequential (stage 4 -> 1).  lat1 = (fork, tgt) is the stride-4 lateral branch started early by
-    run_clip as a parallel graph branch; it is joined when the chain reaches stride 4.  par = ((arena, stream),
+    convolution chain is sequential (stage 4 -> 1).  c.lat1 = (fork, tgt) is the stride-4 lateral branch started early by
+    run_clip as a parallel graph branch; it is joined when the chain reaches stride 4.  c.fork3 = ((arena, stream),
     (arena, stream)): the stride-32 lateral + the chain down to stride 16 and the stride-16 lateral run as two more
     parallel branches beside the stride-8 lateral (the largest of the three) on the main stream."""
-    cfg, w = model.cfg, model._packed
+    model, w, ar, T, sizes, lat1, par = c.model, c.w, c.ar, c.T, c.sizes, c.lat1, c.fork3
     A = ar.alloc
-    sizes = sc["sizes"]
     pd = "pixel_decoder."
 
-    pending = {}  # id of a y buffer that holds the RAW convolution output of its stage -> that stage (its GroupNorm is still due)
-
-    def merge_conv(tgt, stage, y, y_hw, arx, y_new):
+    def merge_conv(tgt, stage, y, y_hw, due, arx, y_new):
         """top-down merge (nearest up-sampling to the exact finer size) + 3x3 conv + GN(8) + ReLU -> y_new.  The GroupNorm + ReLU
         of a stage whose output only feeds the next merge (stages 4..2) is not applied here: y_new then holds the raw convolution
         output and the NEXT merge applies it while it up-samples and adds (ops.groupnorm_up_add: one apply pass instead of an
-        apply pass and a merge pass).  Stage 1's output feeds the mask_features convolution: normalised here."""
+        apply pass and a merge pass).  Stage 1's output feeds the mask_features convolution: normalised here.
+        due: the stage whose GroupNorm + ReLU is still due on y (None: y is normalised).  Returns the same for y_new."""
         h, ww = sizes[stage - 1]
         if y is not None:
-            prev = pending.pop(id(y), None)
-            if prev is not None:
-                ops.groupnorm_up_add(y, w[f"{pd}layer_{prev}.norm.weight"], w[f"{pd}layer_{prev}.norm.bias"], T, y_hw[0], y_hw[1], h, ww,
+            if due is not None:
+                ops.groupnorm_up_add(y, w[f"{pd}layer_{due}.norm.weight"], w[f"{pd}layer_{due}.norm.bias"], T, y_hw[0], y_hw[1], h, ww,
                                      D, 8, add=tgt, out=tgt, relu=True, alloc=arx.alloc)
             else:
                 ops.resize_nearest(y, T, y_hw[0], y_hw[1], h, ww, D, add=tgt, out=tgt)
         if ops.GN_UP_FUSE and stage > 1:
             with model.arith("pixel.conv"):
                 ops.conv2d_cl(tgt, w[f"{pd}layer_{stage}.weight:cl"], T, h, ww, D, 3, 3, 1, 1, out=y_new, alloc=arx.alloc)
-            pending[id(y_new)] = stage
-            return
+            return stage
         with model.arith("pixel.conv"):
             conv, _, _ = ops.conv2d_cl(tgt, w[f"{pd}layer_{stage}.weight:cl"], T, h, ww, D, 3, 3, 1, 1, alloc=arx.alloc)
         ops.groupnorm_cl(conv, w[f"{pd}layer_{stage}.norm.weight"], w[f"{pd}layer_{stage}.norm.bias"], T, h * ww, D, 8,
                          relu=True, out=y_new, alloc=arx.alloc)
+        return None
 
-    y = None
-    y_hw = None
+    y = y_hw = due = None
     stages = (4, 3, 2, 1)
     if par is not None and par[0][1] is not None and par[1][1] is not None:
         (ar3, st3), (ar4, st4) = par
@@ -1299,21 +1288,21 @@ def _pixel_decoder(model, ar, sc, feats, memory, vl_sites, T, L, ffn, ln_, lat1=
         ar4.reset()
         fk_l3 = _Fork(st4)
         with fk_l3:
-            tgt3 = _lateral(model, sc, feats, memory, vl_sites, T, L, ffn, ln_, 3, ar4, G)
+            tgt3 = _lateral(c, 3, ar4)
         fk_c = _Fork(st3)
         with fk_c:
             (h4, w4), (h3, w3) = sizes[3], sizes[2]
             y4, y3 = ar3.alloc(T * h4 * w4, D), ar3.alloc(T * h3 * w3, D)
-            tgt4 = _lateral(model, sc, feats, memory, vl_sites, T, L, ffn, ln_, 4, ar3, G)
-            merge_conv(tgt4, 4, None, None, ar3, y4)
+            tgt4 = _lateral(c, 4, ar3)
+            due = merge_conv(tgt4, 4, None, None, None, ar3, y4)
             fk_l3.join()  # this branch waits for the stride-16 lateral
-            merge_conv(tgt3, 3, y4, (h4, w4), ar3, y3)
+            due = merge_conv(tgt3, 3, y4, (h4, w4), due, ar3, y3)
         h, ww = sizes[1]
         y2 = A(T * h * ww, D)
         m0 = ar.mark()
-        tgt2 = _lateral(model, sc, feats, memory, vl_sites, T, L, ffn, ln_, 2, ar, G)
+        tgt2 = _lateral(c, 2, ar)
         fk_c.join()
-        merge_conv(tgt2, 2, y3, (h3, w3), ar, y2)
+        due = merge_conv(tgt2, 2, y3, (h3, w3), due, ar, y2)
         ar.release(m0)
         y, y_hw = y2, (h, ww)
         stages = (1,)
@@ -1326,10 +1315,11 @@ def _pixel_decoder(model, ar, sc, feats, memory, vl_sites, T, L, ffn, ln_, lat1=
             lat1[0].join()
             tgt = lat1[1]
         else:
-            tgt = _lateral(model, sc, feats, memory, vl_sites, T, L, ffn, ln_, stage, ar, G)
-        merge_conv(tgt, stage, y, y_hw, ar, y_new)
+            tgt = _lateral(c, stage, ar)
+        due = merge_conv(tgt, stage, y, y_hw, due, ar, y_new)
         ar.release(m0)
         y, y_hw = y_new, (h, ww)
+    assert due is None, f"pixel decoder: the GroupNorm + ReLU of stage {due} was never applied to the map mask_features reads"
     h, ww = sizes[0]
     with model.arith("pixel.conv"):
         out_final, _, _ = ops.conv2d_cl(y, w[pd + "mask_features.weight:cl"], T, h, ww, D, 3, 3, 1, 1,

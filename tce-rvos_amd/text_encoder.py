@@ -55,7 +55,7 @@ class TextPlan:
         """ids int64 [G, L] on the GPU (G captions of equal length: one per clip of a clip group; G = 1 for a single clip);
         A = arena allocator.  lens: int32 [G] on the GPU (ragged clip groups: the captions are right-padded to L and caption g's
         keys are its first lens[g] tokens, HF's attention_mask; every row, pad rows included, is computed -- ops.caption_lens).  Returns (last_hidden_state [G*L, C] caption-major, pooler_output [C] for G = 1, [G, C] otherwise);
-        the two live in ONE [G*L + G, C] buffer, so the resizer takes them as one tensor (pipeline.text_stage).
+        the two live in ONE [G*L + G, C] buffer, so the resizer takes them as one tensor (pipeline._Clip.text_stage).
         (The few-row kernel of csrc/fewrow.hip was tried for the dense layers and is slower at K = 768 / 3072 than the
         split-K GEMM: 12.7 vs 9.8 us, profiles/r03_fewrow.txt.)"""
         sd, C = self.sd, self.C
