@@ -10,7 +10,8 @@ import os
 import types
 import math
 from collections import OrderedDict
-from typing import List, Optional
+from itertools import accumulate
+from typing import Any, List, NamedTuple, Optional
 
 import torch
 from torch import nn
@@ -74,7 +75,6 @@ def nested_tensor_from_videos_list(videos_list: List[torch.Tensor], size_divisib
 # never replayed) executable alive here.  The list is bounded by a per-process capture budget: once it is spent,
 # shapes that are not cached run eagerly.
 _ALL_GRAPHS = []
-GRAPH_BUDGET = int(__import__("os").environ.get("TCE_GRAPH_BUDGET", 512))
 _BUDGET_WARNED = False
 # Side streams of the capture branches, shared by every capture of a (device, slot): a stream only shapes the fork / join
 # topology while a graph is being captured, so captures need not own theirs (one set per capture stranded 4 streams with
@@ -95,7 +95,40 @@ def _side_streams(device, slot, n=4):
 # built from explicitly added nodes holds no reference to the capture's streams, so it can be destroyed when its cache entry is
 # evicted and the capture budget above no longer applies to it.  TCE_GRAPH_OWN_EXEC=0 restores the never-destroy path.
 GRAPH_OWN_EXEC = os.environ.get("TCE_GRAPH_OWN_EXEC", "1") != "0"
+# The other switches of capture and replay, read ONCE at import like pipeline.py's: they are constants of the process, so every
+# capture of the process is built from the same program (none of them needs to be part of a graph key).  The per-model knobs
+# (TCE_GRAPH, TCE_GRAPH_CACHE, TCE_GRAPH_CACHE_GB, TCE_GRAPH_AFTER, TCE_TEXT_CACHE) are instance attributes set in __init__.
+GRAPH_BUDGET = int(os.environ.get("TCE_GRAPH_BUDGET", 512))  # captures of the never-destroy path (_ALL_GRAPHS) per process
+KEEP_GRAPHS = os.environ.get("TCE_KEEP_GRAPHS", "0") == "1"   # keep the hipGraph_t beside the executable (tools/pair_graph_probe.py)
+FORK2 = os.environ.get("TCE_FORK2", "1") != "0"               # A/B: 0 = no parallel branch for the stride-4 lateral path
+FORK3 = os.environ.get("TCE_FORK3", "1") != "0"               # A/B: 0 = none for the stride-32 / stride-16 lateral paths
+COPYPLAN = os.environ.get("TCE_COPYPLAN", "1") != "0"         # A/B: 0 = per-tensor output clones after a replay
 _OWNED_LIVE = [0, 0]  # [alive now, destroyed so far]
+
+
+class _Resources(NamedTuple):
+    """What one capture runs on (_branch_resources): the main arena and one arena per parallel branch that allocates; the
+    streams are the (device, slot)'s shared set."""
+    arena: Any
+    side_arena: Any
+    side_stream: Any
+    arena2: Any
+    stream2: Any
+    arena3: Any
+    stream3: Any
+    arena4: Any
+    stream4: Any
+
+
+class _Entry(NamedTuple):
+    """One captured launch program in a model's graph cache.  statics[0] is the backbone's frame buffer, statics[1:] the
+    program's other inputs (token ids, or text_hidden and text_pooled); out is the output dict living in `res`'s arenas."""
+    exe: Any        # _OwnedExec, or a torch.cuda.CUDAGraph of the never-destroy path
+    statics: list
+    out: dict
+    res: _Resources
+    nbytes: int     # of the arenas: what the cache's byte bound counts
+    plan: Any       # ops.CopyPlan of the outputs, or None (per-tensor clones)
 
 
 class _OwnedExec:
@@ -278,7 +311,6 @@ class ReferFormer(nn.Module):
         # of varying length / size / caption length (inference_ytvos.py:278-295), so the cache is an LRU bounded in
         # entries AND bytes, and a shape is only captured once it comes back (the first `graph_after` sightings run
         # eagerly: capturing costs an eager warm-up, a device sync and the capture itself).
-        import os
         self.use_graph = os.environ.get("TCE_GRAPH", "1") != "0"
         self._graphs = OrderedDict()
         self._sightings = OrderedDict()
@@ -334,8 +366,8 @@ class ReferFormer(nn.Module):
         if getattr(self, "_graphs", None) or getattr(self, "_arenas", None):
             torch.cuda.synchronize()  # a replay / eager clip may still be running on these buffers
         for ent in (getattr(self, "_graphs", None) or {}).values():
-            if isinstance(ent[0], _OwnedExec):
-                ent[0].destroy()
+            if isinstance(ent.exe, _OwnedExec):
+                ent.exe.destroy()
         self._graphs = OrderedDict()
         self._sightings = OrderedDict()
         self._text_cache = OrderedDict()
@@ -655,31 +687,56 @@ class ReferFormer(nn.Module):
         cached = self._text_lookup(ids, ids_host, frames.device)
         if cached is not None:  # text features of this expression are cached: the clip runs from them
             out = self.forward_features(frames, cached[0], cached[1], img_h, img_w, slot=slot, valid_hw=valid, select=select)
-        else:
+        else:  # one hipGraph per input shape: RoBERTa runs as a parallel branch beside the backbone, the decoder beside the pixel decoder
             ids = ids.to(frames.device)
             key = ("clip", tuple(frames.shape), tuple(ids.shape), img_h, img_w, self.training, int(slot), self._stamp, valid, select)
-            if not self._want_graph(key):
-                out = self._run(frames, lambda alloc: self._text_plan().forward(ids, alloc), img_h, img_w, None, slot, valid=valid,
-                                select=select)
-            else:
-                # one hipGraph per input shape: RoBERTa runs as a parallel branch beside the backbone, the decoder
-                # beside the pixel decoder
-                ent = self._graphs.get(key)
-                if ent is None:
-                    st = (frames.clone(), ids.clone())
-
-                    def text_fn(alloc):
-                        return self._text_plan().forward(st[1], alloc)
-
-                    ent = self._capture(key, st, lambda res: self._run(st[0], text_fn, img_h, img_w, res, valid=valid, select=select),
-                                        frames, slot, text=(1, ids.shape[1]))
-                if ent is None:  # the capture's arenas did not fit this shape's fallback kernels: eager from now on
-                    out = self._run(frames, lambda alloc: self._text_plan().forward(ids, alloc), img_h, img_w, None, slot,
-                                    valid=valid, select=select)
-                else:
-                    out = self._replay(key, ent, (frames, ids))
+            out = self._dispatch(key, [frames], (ids,), self._group_text, img_h, img_w, (1, ids.shape[1]), slot,
+                                 valid=valid, select=select)
         ops.range_snapshot_async(frames.device)
         return self._tag_diagnostics(out)
+
+    # ---------------------------------------------------------------- eager launches, capture or replay: one place
+    def _program(self, text_of, img_h, img_w, slot, kw):
+        """run(frames, inputs, res=None): one pass of a launch program over the backbone's frame buffer `frames` and the non-frame
+        inputs (live tensors or a capture's statics) -- eagerly on the slot's arena, or on a capture's resources `res`.  text_of
+        maps the inputs to the `text` argument of _run, kw are _run's keywords (valid, groups, shared, select, index)."""
+        def run(frames, inputs, res=None):
+            return self._run(frames, text_of(*inputs), img_h, img_w, res, slot, **kw)
+        return run
+
+    @staticmethod
+    def _like(frames, groups=1, shared=False, index=None, **_):
+        """What _branch_resources sizes a capture by, from the backbone's frame buffer and _run's keywords: the frames the stages
+        after the backbone see (a shared group: the one clip G times; an indexed group: G*Tc gathered frames, gather=True)."""
+        rows = len(index) * len(index[0]) if index is not None else int(frames.shape[0]) * (groups if shared else 1)
+        return types.SimpleNamespace(shape=(rows,) + tuple(frames.shape[1:]), device=frames.device, gather=index is not None)
+
+    def _dispatch(self, key, sources, inputs, text_of, img_h, img_w, text_shape, slot=0, **kw):
+        """The output dict of one launch program, from eager launches or from the replay of its captured graph (_want_graph).
+        sources: the tensors whose rows, back to back, are the backbone's frame buffer (one clip, the clips of a group, the runs of
+        a pool); inputs: the other input tensors; text_of, kw: see _program; text_shape = (captions, tokens each) of the text branch
+        (_text_arena_extra).  A replay stages every source and input into the graph's statics with ONE copy launch: the sources go
+        straight into their rows of the static frame buffer."""
+        run = self._program(text_of, img_h, img_w, slot, kw)
+
+        def frames_now():  # may alias the caller's tensor (one source) or be a fresh tensor (several)
+            if len(sources) == 1:
+                return sources[0].to(torch.float32).contiguous()
+            return torch.cat([s.to(torch.float32) for s in sources], 0)
+
+        if self._want_graph(key):
+            ent = self._graphs.get(key)
+            if ent is None:
+                frames = frames_now().clone() if len(sources) == 1 else frames_now()
+                st = [frames] + [t.clone() for t in inputs]
+                ent = self._capture(key, st, lambda res: run(st[0], st[1:], res), self._like(frames, **kw), slot, text=text_shape)
+            if ent is not None:
+                buf, ends = ent.statics[0], accumulate(s.shape[0] for s in sources)
+                # one source fills the buffer (no view to make on the per-clip path); several: their rows, back to back
+                dsts = [buf] if len(sources) == 1 else [buf[e - s.shape[0]:e] for s, e in zip(sources, ends)]
+                return self._replay(key, ent, dsts + ent.statics[1:], list(sources) + list(inputs))
+            # the capture's arenas did not fit this shape's fallback kernels: eager from now on
+        return run(frames_now(), inputs)
 
     def _pad_id(self):
         return int(getattr(getattr(self.text_encoder, "config", None), "pad_token_id", 1) or 1)
@@ -695,8 +752,8 @@ class ReferFormer(nn.Module):
         if int(L) > limit:
             raise ValueError(caption_too_long(int(L), limit))
 
-    def _group_text(self, ids, ragged):
-        """The text callable of a clip group's launch program.  Ragged: the captions' lengths, key padding mask and position table
+    def _group_text(self, ids, ragged=False):
+        """The text callable of a launch program that starts from token ids (a clip or a clip group).  Ragged: the captions' lengths, key padding mask and position table
         come from the ids on the device in the same program (ops.caption_lens), so a captured graph follows the lengths that its
         static id buffer holds at each replay -- nothing about them is baked in at capture time."""
         if not ragged:
@@ -745,86 +802,81 @@ class ReferFormer(nn.Module):
         A shared group (the same tensor G times) runs the backbone once; the indices may differ per caption.  Targets of which some
         carry 'valid_indices' and others do not raise ValueError, an index outside the clip IndexError."""
         G = len(clips)
-        if ragged:
-            pad_id = self._pad_id()
-            if isinstance(captions, (list, tuple)):
-                captions, _ = pad_captions([self._tokenise([c], clips[0].device)[0] for c in captions], pad_id)
-            elif torch.is_tensor(captions) and not captions.is_cuda:
-                caption_lengths(captions, pad_id)  # validation only: the device derives the lengths itself
-        if G == 1:
-            cap = captions[:1] if torch.is_tensor(captions) else [captions[0]]
-            if ragged and torch.is_tensor(cap):  # one caption: no padding needed (its length on the host: one read-back)
-                cap = cap[:, :caption_lengths(cap.cpu(), self._pad_id())[0]]
-            return [self.forward([clips[0]], cap, targets[:1], slot=slot)]
-        # the captions first (tokenised on the host): one beyond the text encoder's limit is refused before anything else is looked at
-        if isinstance(captions, (list, tuple)):
-            rows = [self._tokenise([c], clips[0].device)[0] for c in captions]
-            self._check_caption_tokens(max(int(r.shape[1]) for r in rows))
-            if len({int(r.shape[1]) for r in rows}) != 1:
-                raise ValueError("clip groups: the captions must tokenise to one length")
-            ids = torch.cat(rows, 0)
-        else:
-            ids = captions
-            if ids.dim() == 2:
-                self._check_caption_tokens(ids.shape[1])
+        ids, single = self._group_captions(captions, G, ragged, clips[0].device, "clip groups")
+        if single is not None:
+            return [self.forward([clips[0]], single, targets[:1], slot=slot)]
         shp = tuple(clips[0].shape)
         if any(tuple(c.shape) != shp or not c.is_cuda for c in clips) or len(shp) != 4:
             raise ValueError("clip groups: G CUDA tensors [T,3,H,W] of one shape")
         if ids.dim() != 2 or ids.shape[0] != G or G > 64:
             raise ValueError("clip groups: token ids [G, L], G <= 64")
-        size = targets[0]["size"]
-        img_h, img_w = float(size[0]), float(size[1])
-        if any((float(t["size"][0]), float(t["size"][1])) != (img_h, img_w) for t in targets[1:]):
-            raise ValueError("clip groups: the clips of a group share one target size")
+        img_h, img_w = self._group_size(targets, "clip groups")
         sel = self._group_select(targets, G, shp[0])
         self._ensure_packed()
         ops.range_poll(clips[0].device)
-        Tc = shp[0]
-        dev = clips[0].device
-        ids = ids.to(dev)
+        ids = ids.to(clips[0].device)
         # one clip, G captions (the expressions of a video: the SAME tensor G times): the backbone runs once
         shared = all(c is clips[0] for c in clips[1:])
-        srcs = [clips[0]] if shared else list(clips)
         if ragged:
             ids = ids.to(torch.int64).contiguous()
         # ragged: the flag, never the lengths (they live in the static id buffer)
         key = ("group", G, shared, shp, tuple(ids.shape), img_h, img_w, self.training, int(slot), self._stamp) + (("ragged",) if ragged else ())
         if sel is not None:  # the selection's source addresses are arguments of the captured copy launches: one graph per index tuple
             key += (("select", sel),)
-
-        def frames_now():
-            return srcs[0].to(torch.float32).contiguous() if shared else torch.cat([c.to(torch.float32) for c in srcs], 0)
-
-        def eager():
-            return self._run(frames_now(), self._group_text(ids, ragged), img_h, img_w, None, slot, groups=G, shared=shared, select=sel)
-
-        if not ragged and key not in self._group_checked:
-            self._group_checked.add(key)
-            # a [G, L] id tensor built by PADDING G captions to one length would silently differ from each clip's B = 1 forward
-            # (the text kernels take every position as a token; the reference masks pads through attention_mask /
-            # key_padding_mask): checked ONCE per group shape, on its first sighting (a device read-back; ADVICE r4)
-            pad_id = int(getattr(getattr(self.text_encoder, "config", None), "pad_token_id", 1) or 1)
-            if bool((ids == pad_id).any()):
-                raise ValueError(f"clip groups: token ids contain the pad id ({pad_id}): padded captions are not supported -- "
-                                 f"group captions of equal token length (every position of [G, L] is taken as a token)")
-        if not self._want_graph(key):
-            out = eager()
-        else:
-            ent = self._graphs.get(key)
-            if ent is None:
-                st = (frames_now().clone() if shared else frames_now(), ids.clone())
-                text_fn = self._group_text(st[1], ragged)
-                like = types.SimpleNamespace(shape=(G * Tc,) + shp[1:], device=dev)  # arenas are sized for the whole group
-                ent = self._capture(key, st, lambda res: self._run(st[0], text_fn, img_h, img_w, res, groups=G, shared=shared, select=sel),
-                                    like, slot, text=(G, ids.shape[1]))
-            if ent is None:
-                out = eager()
-            else:  # the clips go straight into their slices of the graph's static frame buffer (one copy launch)
-                n = len(srcs)
-                statics = [ent[1][0][g * Tc:(g + 1) * Tc] for g in range(n)] + [ent[1][1]]
-                out = self._replay(key, (ent[0], statics) + tuple(ent[2:]), srcs + [ids])
+        if not ragged:
+            self._refuse_pad_ids(key, ids, "clip groups", "padded captions are not supported -- group captions of equal token "
+                                                          "length (every position of [G, L] is taken as a token)")
+        out = self._dispatch(key, clips[:1] if shared else list(clips), (ids,), lambda i: self._group_text(i, ragged), img_h, img_w,
+                             (G, ids.shape[1]), slot, groups=G, shared=shared, select=sel)
         ops.range_snapshot_async(clips[0].device)
-        return self._split_group(out, G, Tc if sel is None else 1)
+        return self._split_group(out, G, shp[0] if sel is None else 1)
+
+    def _group_captions(self, captions, G, ragged, device, what, one_length_hint=""):
+        """The captions of a group boundary (`what` names it in the messages), normalised on the host and before any launch:
+        (token ids [G, L], None) -- or, for G = 1, (None, the caption to hand to `forward`).  Strings are tokenised as `forward`
+        tokenises them.  A caption beyond the text encoder's limit is refused first.  ragged: strings are right-padded with the
+        pad id to the longest, host ids are validated as right-padded (caption_lengths); not ragged: strings must tokenise to one
+        length."""
+        rows = None
+        if isinstance(captions, (list, tuple)):
+            rows = [self._tokenise([c], device)[0] for c in captions]
+            self._check_caption_tokens(max(int(r.shape[1]) for r in rows))
+        elif captions.dim() == 2:
+            self._check_caption_tokens(captions.shape[1])
+        if ragged:
+            if rows is not None:
+                captions, _ = pad_captions(rows, self._pad_id())
+            elif not captions.is_cuda:
+                caption_lengths(captions, self._pad_id())  # validation only: the device derives the lengths itself
+        if G == 1:
+            cap = captions[:1] if torch.is_tensor(captions) else [captions[0]]
+            if ragged and torch.is_tensor(cap):  # one caption: no padding needed (its length on the host: one read-back)
+                cap = cap[:, :caption_lengths(cap.cpu(), self._pad_id())[0]]
+            return None, cap
+        if torch.is_tensor(captions):
+            return captions, None
+        if len({int(r.shape[1]) for r in rows}) != 1:
+            raise ValueError(f"{what}: the captions must tokenise to one length{one_length_hint}")
+        return torch.cat(rows, 0), None
+
+    @staticmethod
+    def _group_size(targets, what):
+        """(img_h, img_w) of a group's targets: one entry, or G equal ones."""
+        size = targets[0]["size"]
+        img_h, img_w = float(size[0]), float(size[1])
+        if any((float(t["size"][0]), float(t["size"][1])) != (img_h, img_w) for t in targets[1:]):
+            raise ValueError(f"{what}: the clips of a group share one target size")
+        return img_h, img_w
+
+    def _refuse_pad_ids(self, key, ids, what, advice):
+        """A [G, L] id tensor built by PADDING G captions to one length would silently differ from each clip's B = 1 forward in a
+        group that is not ragged (the text kernels take every position as a token; the reference masks pads through attention_mask
+        / key_padding_mask): checked ONCE per group shape `key`, on its first sighting (a device read-back)."""
+        if key not in self._group_checked:
+            self._group_checked.add(key)
+            pad_id = self._pad_id()
+            if bool((ids == pad_id).any()):
+                raise ValueError(f"{what}: token ids contain the pad id ({pad_id}): {advice}")
 
     def _pool_plan(self, index, F):
         """(index as a tuple of G int tuples, the pool frames the backbone runs over in its row order) of an indexed group over a
@@ -871,44 +923,20 @@ class ReferFormer(nn.Module):
             raise ValueError(f"indexed groups: {G} index tuples but "
                              f"{len(captions) if isinstance(captions, (list, tuple)) else int(captions.shape[0])} captions")
         dev = pool.device
-        rows = None
-        if isinstance(captions, (list, tuple)):  # tokenised on the host: a caption beyond the text encoder's limit is an argument error
-            rows = [self._tokenise([c], dev)[0] for c in captions]
-            self._check_caption_tokens(max(int(r.shape[1]) for r in rows))
-        elif captions.dim() == 2:
-            self._check_caption_tokens(captions.shape[1])
+        ids, single = self._group_captions(captions, G, ragged, dev, "indexed groups", " (or ragged=True)")
         if not pool.is_cuda:
             raise RuntimeError("inputs must be on the GPU: this path has no CPU implementation")
-        if ragged:
-            pad_id = self._pad_id()
-            if rows is not None:
-                captions, _ = pad_captions(rows, pad_id)
-            elif not captions.is_cuda:
-                caption_lengths(captions, pad_id)  # validation only: the device derives the lengths itself
-        if G == 1:
-            cap = captions[:1] if torch.is_tensor(captions) else [captions[0]]
-            if ragged and torch.is_tensor(cap):
-                cap = cap[:, :caption_lengths(cap.cpu(), self._pad_id())[0]]
-            return [self.forward([pool[list(index[0])]], cap, targets[:1], slot=slot)]
-        if isinstance(captions, (list, tuple)):
-            if len({int(r.shape[1]) for r in rows}) != 1:
-                raise ValueError("indexed groups: the captions must tokenise to one length (or ragged=True)")
-            ids = torch.cat(rows, 0)
-        else:
-            ids = captions
+        if single is not None:
+            return [self.forward([pool[list(index[0])]], single, targets[:1], slot=slot)]
         if ids.dim() != 2:
             raise ValueError("indexed groups: token ids [G, L]")
-        size = targets[0]["size"]
-        img_h, img_w = float(size[0]), float(size[1])
-        if any((float(t["size"][0]), float(t["size"][1])) != (img_h, img_w) for t in targets[1:]):
-            raise ValueError("indexed groups: the clips of a group share one target size")
+        img_h, img_w = self._group_size(targets, "indexed groups")
         self._ensure_packed()
         ops.range_poll(dev)
         ids = ids.to(dev)
         if ragged:
             ids = ids.to(torch.int64).contiguous()
-        shp = tuple(pool.shape)
-        key = ("indexed", G, shp, tuple(ids.shape), img_h, img_w, self.training, int(slot), self._stamp) + \
+        key = ("indexed", G, tuple(pool.shape), tuple(ids.shape), img_h, img_w, self.training, int(slot), self._stamp) + \
             (("ragged",) if ragged else ()) + (("index", index),)
         # the backbone's frames as runs of consecutive pool frames: [first pool frame, frames]
         runs = []
@@ -917,39 +945,10 @@ class ReferFormer(nn.Module):
                 runs[-1][1] += 1
             else:
                 runs.append([f, 1])
-        whole = len(runs) == 1 and runs[0][1] == shp[0]  # the backbone sees the pool as it is
-
-        def frames_now():
-            if whole:
-                return pool.to(torch.float32).contiguous()
-            return torch.cat([pool[a:a + n].to(torch.float32) for a, n in runs], 0)
-
-        def eager():
-            return self._run(frames_now(), self._group_text(ids, ragged), img_h, img_w, None, slot, groups=G, index=index)
-
-        if not ragged and key[:-1] not in self._group_checked:  # padded captions in an un-ragged group: see forward_group
-            self._group_checked.add(key[:-1])
-            pad_id = self._pad_id()
-            if bool((ids == pad_id).any()):
-                raise ValueError(f"indexed groups: token ids contain the pad id ({pad_id}): padded captions need ragged=True")
-        if not self._want_graph(key):
-            out = eager()
-        else:
-            ent = self._graphs.get(key)
-            if ent is None:
-                st = (frames_now().clone() if whole else frames_now(), ids.clone())
-                text_fn = self._group_text(st[1], ragged)
-                like = types.SimpleNamespace(shape=(G * Tc,) + shp[1:], device=dev, gather=True)
-                ent = self._capture(key, st, lambda res: self._run(st[0], text_fn, img_h, img_w, res, groups=G, index=index), like, slot,
-                                    text=(G, ids.shape[1]))
-            if ent is None:
-                out = eager()
-            else:  # the pool's runs go straight into their rows of the graph's static frame buffer (one copy launch)
-                at, statics = 0, []
-                for _, n in runs:
-                    statics.append(ent[1][0][at:at + n])
-                    at += n
-                out = self._replay(key, (ent[0], statics + [ent[1][1]]) + tuple(ent[2:]), [pool[a:a + n] for a, n in runs] + [ids])
+        if not ragged:  # once per group shape, whatever the index
+            self._refuse_pad_ids(key[:-1], ids, "indexed groups", "padded captions need ragged=True")
+        out = self._dispatch(key, [pool[a:a + n] for a, n in runs], (ids,), lambda i: self._group_text(i, ragged), img_h, img_w,
+                             (G, ids.shape[1]), slot, groups=G, index=index)
         ops.range_snapshot_async(dev)
         return self._split_group(out, G, Tc)
 
@@ -1033,7 +1032,7 @@ class ReferFormer(nn.Module):
             self._sightings.popitem(last=False)
         if n < self.graph_after:
             return False
-        if len(_ALL_GRAPHS) >= GRAPH_BUDGET and not (GRAPH_OWN_EXEC and os.environ.get("TCE_KEEP_GRAPHS", "0") != "1"):
+        if len(_ALL_GRAPHS) >= GRAPH_BUDGET and not (GRAPH_OWN_EXEC and not KEEP_GRAPHS):
             global _BUDGET_WARNED
             if not _BUDGET_WARNED:
                 _BUDGET_WARNED = True
@@ -1108,11 +1107,10 @@ class ReferFormer(nn.Module):
             else:
                 ar = self._get_arena(T * (groups if shared else 1), H0, W0, frames.device, slot)
             return run_clip(self, frames, text, img_h, img_w, ar, valid=valid, groups=groups, shared=shared, select=select, index=index)
-        arena, side_arena, side_stream, arena2, stream2, arena3, stream3, arena4, stream4 = res
-        return run_clip(self, frames, text, img_h, img_w, arena, side_arena, side_stream, clone_outputs=False, valid=valid,
+        return run_clip(self, frames, text, img_h, img_w, res.arena, res.side_arena, res.side_stream, clone_outputs=False, valid=valid,
                         groups=groups, shared=shared, select=select, index=index,
-                        fork2=(arena2, stream2) if os.environ.get("TCE_FORK2", "1") != "0" else None,
-                        fork3=((arena3, stream3), (arena4, stream4)) if os.environ.get("TCE_FORK3", "1") != "0" else None)
+                        fork2=(res.arena2, res.stream2) if FORK2 else None,
+                        fork3=((res.arena3, res.stream3), (res.arena4, res.stream4)) if FORK3 else None)
 
     def _text_arena_extra(self, text):
         """Bytes the text branch of text = (G captions, L tokens each) needs in its arena beyond the flat allowance of
@@ -1127,7 +1125,7 @@ class ReferFormer(nn.Module):
         return int(text[0]) * int(text[1]) * 4 * (5 * C + ff + max(ff, 3 * C) + 16 * self.cfg.hidden_dim) + (8 << 20)
 
     def _branch_resources(self, like, slot=0, text=None):
-        """(arena, side arena, side stream, arena2, stream2, arena3, stream3, arena4, stream4) of one capture: the main arena
+        """The _Resources of one capture, sized by `like` (_like): the main arena
         and one arena per parallel branch that allocates; the side streams are the (device, slot)'s shared set.  like.gather (an
         indexed group): T frames' maps are gathered from the backbone's -- room for each in the arena of the branch that consumes it
         (stage 0: the stride-4 lateral branch, stages 1 / 2: the early input projections) and for all of them in the main arena."""
@@ -1135,7 +1133,8 @@ class ReferFormer(nn.Module):
         tok0 = T * ((H0 + 3) // 4) * ((W0 + 3) // 4)
         st = _side_streams(like.device, slot)
         gb = self._gather_bytes(T, H0, W0) if getattr(like, "gather", False) else [0, 0, 0, 0]
-        return (ops.Arena(like.device, self._arena_bytes(T, H0, W0) + sum(gb)),
+        return _Resources(  # constructed in field order
+                ops.Arena(like.device, self._arena_bytes(T, H0, W0) + sum(gb)),
                 ops.Arena(like.device, T * self._tokens_per_frame(H0, W0) * 256 * 4 * 4 + (32 << 20) + self._text_arena_extra(text)),
                 st[0],
                 # third branch: the pixel decoder's stride-4 lateral path (tgt + its self-attention / FFN temporaries)
@@ -1174,16 +1173,13 @@ class ReferFormer(nn.Module):
         T, _, H0, W0 = frames.shape
         img_h, img_w = (float(H0), float(W0)) if img_hw is None else (float(img_hw[0]), float(img_hw[1]))
         self._ensure_packed()
-        if index is not None:
-            like = types.SimpleNamespace(shape=(groups * len(index[0]), 3, H0, W0), device=frames.device, gather=True)
-        else:
-            like = types.SimpleNamespace(shape=(T * (groups if shared else 1), 3, H0, W0), device=frames.device)
-        res = self._branch_resources(like, slot, text=(groups, ids.shape[1]))
-        st = (frames.clone(), ids.to(frames.device).clone())
         if select is not None:
             select = int(select) if groups == 1 and not isinstance(select, (tuple, list)) else tuple(int(v) for v in select)
-        run = lambda: self._run(st[0], self._group_text(st[1], ragged), img_h, img_w, res, valid=valid, shared=shared,  # noqa: E731
-                                groups=groups, select=select, index=index)
+        kw = dict(valid=valid, groups=groups, shared=shared, select=select, index=index)
+        res = self._branch_resources(self._like(frames, **kw), slot, text=(groups, ids.shape[1]))
+        st = (frames.clone(), ids.to(frames.device).clone())
+        program = self._program(lambda i: self._group_text(i, ragged), img_h, img_w, slot, kw)
+        run = lambda: program(st[0], st[1:], res)  # noqa: E731
         main = torch.cuda.Stream(device=frames.device)  # like a capture: never the legacy default stream (it syncs with all)
         main.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(main):
@@ -1217,9 +1213,8 @@ class ReferFormer(nn.Module):
             warnings.warn(f"tce_rvos_amd: graph capture of {key[:2]} skipped ({e}); this shape runs eagerly", RuntimeWarning)
             return None
         torch.cuda.synchronize()
-        keep = os.environ.get("TCE_KEEP_GRAPHS", "0") == "1"  # keep the hipGraph_t beside the executable (clip groups)
-        own = GRAPH_OWN_EXEC and not keep
-        graph = torch.cuda.CUDAGraph(keep_graph=True) if (keep or own) else torch.cuda.CUDAGraph()
+        own = GRAPH_OWN_EXEC and not KEEP_GRAPHS
+        graph = torch.cuda.CUDAGraph(keep_graph=True) if (KEEP_GRAPHS or own) else torch.cuda.CUDAGraph()
         # capture_error_mode="thread_local": under the default ("global") mode ANY thread's event query is an error while this
         # thread captures -- and torch.distributed's RCCL watchdog thread polls the events of in-flight collectives (bench.py keeps
         # the previous step's all-gather in flight): it then dies with "operation not permitted when stream is capturing" and takes
@@ -1238,23 +1233,23 @@ class ReferFormer(nn.Module):
             else:  # a node kind the re-creation does not know (none in the shipped program): the legacy, never-destroyed path
                 own = False
                 graph.instantiate()
-        elif keep:
+        elif KEEP_GRAPHS:
             graph.instantiate()
         if not own:
             _ALL_GRAPHS.append(graph)  # legacy executables outlive their cache entry (see _ALL_GRAPHS)
         try:
-            plan = ops.CopyPlan(_flat_outputs(out)) if os.environ.get("TCE_COPYPLAN", "1") != "0" else None
+            plan = ops.CopyPlan(_flat_outputs(out)) if COPYPLAN else None
         except ValueError:  # an output the segment copy cannot express: per-tensor clones
             plan = None
-        ent = (graph, statics, out, res, sum(r.buf.numel() for r in res if isinstance(r, ops.Arena)), plan)
+        ent = _Entry(graph, statics, out, res, sum(r.buf.numel() for r in res if isinstance(r, ops.Arena)), plan)
         self._graphs[key] = ent
         # LRU bound (entries and bytes); the entry just captured always stays.  Eviction returns the arenas.
         while len(self._graphs) > 1 and (len(self._graphs) > self.max_graphs or
-                                         sum(e[4] for e in self._graphs.values()) > self.max_graph_bytes):
+                                         sum(e.nbytes for e in self._graphs.values()) > self.max_graph_bytes):
             torch.cuda.synchronize()  # the evicted graph may still be replaying
             _, old = self._graphs.popitem(last=False)
-            if isinstance(old[0], _OwnedExec):
-                old[0].destroy()  # owned executables go with their entry (legacy ones stay in _ALL_GRAPHS)
+            if isinstance(old.exe, _OwnedExec):
+                old.exe.destroy()  # owned executables go with their entry (legacy ones stay in _ALL_GRAPHS)
         return ent
 
     @staticmethod
@@ -1266,17 +1261,16 @@ class ReferFormer(nn.Module):
             n += h * w
         return n + ((h + 1) // 2) * ((w + 1) // 2)
 
-    def _replay(self, key, ent, inputs):
+    def _replay(self, key, ent, dsts, srcs):
+        """dsts: views of ent.statics, one per tensor of srcs."""
         self._graphs.move_to_end(key)
-        graph, statics, out = ent[0], ent[1], ent[2]
-        ops.copy_many(statics, inputs)  # one launch stages the inputs ...
-        graph.replay()
-        plan = ent[5]
-        if plan is None:
+        ops.copy_many(dsts, srcs)  # one launch stages the inputs ...
+        ent.exe.replay()
+        if ent.plan is None:
             return {k: (v.clone() if torch.is_tensor(v) else [{kk: vv.clone() for kk, vv in a.items()} for a in v])
-                    for k, v in out.items()}
-        it = iter(plan.clone())  # ... and one hands back fresh output tensors (same order as _flat_outputs)
-        return {k: (next(it) if torch.is_tensor(v) else [{kk: next(it) for kk in a} for a in v]) for k, v in out.items()}
+                    for k, v in ent.out.items()}
+        it = iter(ent.plan.clone())  # ... and one hands back fresh output tensors (same order as _flat_outputs)
+        return {k: (next(it) if torch.is_tensor(v) else [{kk: next(it) for kk in a} for a in v]) for k, v in ent.out.items()}
 
     @torch.no_grad()
     def forward_text_encoder(self, captions, device):
@@ -1308,19 +1302,8 @@ class ReferFormer(nn.Module):
         select = None if select is None else int(select)
         key = ("feat", tuple(frames.shape), int(text_hidden.shape[0]), float(img_h), float(img_w), self.training, int(slot),
                self._stamp, valid_hw, select)
-        if not self._want_graph(key):
-            return self._tag_diagnostics(self._run(frames, (text_hidden, text_pooled), img_h, img_w, None, slot, valid=valid_hw,
-                                                   select=select))
-        ent = self._graphs.get(key)
-        if ent is None:
-            st = (frames.clone(), text_hidden.clone(), text_pooled.clone())
-            ent = self._capture(key, st, lambda res: self._run(st[0], (st[1], st[2]), img_h, img_w, res, valid=valid_hw, select=select),
-                                frames, slot, text=(1, text_hidden.shape[0]))
-            if ent is None:
-                return self._tag_diagnostics(self._run(frames, (text_hidden, text_pooled), img_h, img_w, None, slot, valid=valid_hw,
-                                                       select=select))
-        return self._tag_diagnostics(self._replay(key, ent, (frames, text_hidden, text_pooled)))
-
+        return self._tag_diagnostics(self._dispatch(key, [frames], (text_hidden, text_pooled), lambda hid, pooled: (hid, pooled),
+                                                    img_h, img_w, (1, text_hidden.shape[0]), slot, valid=valid_hw, select=select))
 
     def _forward_features_group(self, frames, text_hidden, text_pooled, img_h, img_w, slot, valid_hw, select, G, shared):
         if valid_hw is not None and (int(valid_hw[0]), int(valid_hw[1])) != (int(frames.shape[-2]), int(frames.shape[-1])):
@@ -1344,20 +1327,8 @@ class ReferFormer(nn.Module):
         text_hidden, text_pooled = text_hidden.contiguous(), text_pooled.contiguous()
         key = ("featgroup", G, shared, tuple(frames.shape), int(text_hidden.shape[0]), float(img_h), float(img_w), self.training,
                int(slot), self._stamp, sel)
-
-        def eager():
-            return self._run(frames, (text_hidden, text_pooled), img_h, img_w, None, slot, groups=G, shared=shared, select=sel)
-
-        if not self._want_graph(key):
-            out = eager()
-        else:
-            ent = self._graphs.get(key)
-            if ent is None:
-                st = (frames.clone(), text_hidden.clone(), text_pooled.clone())
-                like = types.SimpleNamespace(shape=(G * Tc,) + tuple(frames.shape[1:]), device=frames.device)
-                ent = self._capture(key, st, lambda res: self._run(st[0], (st[1], st[2]), img_h, img_w, res, groups=G, shared=shared,
-                                                                   select=sel), like, slot, text=(G, text_hidden.shape[0] // G))
-            out = eager() if ent is None else self._replay(key, ent, (frames, text_hidden, text_pooled))
+        out = self._dispatch(key, [frames], (text_hidden, text_pooled), lambda hid, pooled: (hid, pooled), img_h, img_w,
+                             (G, text_hidden.shape[0] // G), slot, groups=G, shared=shared, select=sel)
         return self._split_group(out, G, Tc if sel is None else 1)
 
 

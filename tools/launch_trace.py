@@ -1,7 +1,9 @@
 """The clip's launch program as text, for diffing two trees: per case and topology (the capture topology through
 model.hazard_check, the eager single-arena one through forward_features / forward_group / forward_indexed inside
 hazard.recording()) one line per recorded launch -- entry point, stream, vector clock (streams as ordinals by first appearance:
-this pins every fork / join edge), read and write sets -- then the recorder's edges and host syncs.  An interval inside one of the
+this pins every fork / join edge), read and write sets -- then the recorder's edges and host syncs.  A third recording per case,
+" / replay", is one call of the public entry point that replays the case's captured graph: the launches around the graph launch
+(inputs staged in, outputs copied out).  An interval inside one of the
 pass's arenas prints as arena:offset+length (equal runs at one stride as arena:offset+length*count/stride); everything else
 (weights, inputs: addresses differ between processes) as its total length.  Launch.site is left out.
     python tools/launch_trace.py [--root TREE] [--digest] [--only SUBSTRING] > trace.txt
@@ -35,6 +37,7 @@ def fmt_set(iv, arenas):
                 inside.append((k, l2 - b, h2 - l2))
                 ext -= h2 - l2
         ext += hi - lo
+    inside.sort()  # by arena ordinal, then offset: not by where the allocator happened to place the arenas
     parts, i = [], 0
     while i < len(inside):  # equal runs at one stride -> one term
         k, off, n = inside[i]
@@ -119,7 +122,10 @@ def model_of(backbone, flags, mode):
 
 
 def eager(model, name, T, H, W, x, ids, kw):
-    """the same case through the public eager path (use_graph off): one warm-up pass, one recorded pass, the slot's arena"""
+    """the same case through the public entry point: eagerly (use_graph off: one warm-up pass, one recorded pass, the slot's
+    arena), then as a graph replay (graph_after = 1: the third call replays; the fourth is recorded).  tce_graph_launch is no
+    launch to the recorder, so the replay's recording is what a replay launches OUTSIDE the graph -- the staging copy in, the
+    output copy out -- with byte counts only (the graph's arenas are not listed)."""
     tgt = [{"size": torch.tensor([H, W])}]
     G = kw.get("groups", 1)
     if "index" in kw:
@@ -142,6 +148,15 @@ def eager(model, name, T, H, W, x, ids, kw):
     finally:
         model.use_graph = True
     dump(name + " / eager", rec, [model._arenas[0].buf])
+    n_graphs, model.graph_after = len(model._graphs), 1
+    for _ in range(3):
+        run()
+    torch.cuda.synchronize()
+    assert len(model._graphs) == n_graphs + 1, "the case was not captured: its fourth call would not be a replay"
+    with hazard.recording(tables=[sd["embeddings.word_embeddings.weight"], sd["embeddings.position_embeddings.weight"]]) as rec:
+        run()
+    torch.cuda.synchronize()
+    dump(name + " / replay", rec, [])
 
 
 with torch.no_grad():
