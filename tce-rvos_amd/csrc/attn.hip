@@ -3,8 +3,10 @@
 // latency/LDS-oriented VALU kernels: one query row per lane (q and the output row live in registers), K/V
 // tiles staged in LDS and read back as wave-uniform (broadcast) ds_read_b128, scores of a whole tile kept
 // in registers so softmax needs one rescale per tile and no cross-lane traffic.
+// The pieces the kernels share (fragment loads, the products, the softmax tile step, merge, store, window geometry): attn_tile.h.
 #include <type_traits>
 #include "common.h"
+#include "attn_tile.h"
 #include "../../include/tce_rvos.h"
 #include "../../include/tce_rvos_debug.h"
 
@@ -17,12 +19,10 @@
 
 namespace {
 
-constexpr int HD = 32;  // head dim
-
 // ---------------------------------------------------------------------------------------------------
 // Swin window attention.  One wavefront per (frame, window, head); lanes 0..48 own the 49 query tokens.
 // The zero-padding to a multiple of 7, the cyclic shift, window partition/reverse and the final crop are
-// pure index arithmetic here (no torch.roll / F.pad / window_partition copies).
+// pure index arithmetic here (no torch.roll / F.pad / window_partition copies): Win2D.
 // ---------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) window_attn_kernel(const float* __restrict__ qkv,
                                                           const float* __restrict__ qkv_bias,
@@ -36,7 +36,6 @@ __global__ void __launch_bounds__(256) window_attn_kernel(const float* __restric
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const long long item = (long long)blockIdx.x * 4 + wave;  // ((t*nWy + wy)*nWx + wx)*nH + h
   const bool active = item < total;
-  const int Hp = nWy * WS, Wp = nWx * WS;
   int h = 0, wx = 0, wy = 0, t = 0;
   if (active) {
     long long r = item;
@@ -45,24 +44,16 @@ __global__ void __launch_bounds__(256) window_attn_kernel(const float* __restric
     wy = (int)(r % nWy); r /= nWy;
     t = (int)r;
   }
+  const Win2D g{wy, wx, shift, nWy * WS, nWx * WS, H, W};
   const int C3 = 3 * C;
   if (active) {
     // stage K and V of the window's 49 tokens (padded tokens: the qkv bias), and this head's bias column
     for (int i = lane; i < NT * 8; i += 64) {
       const int j = i >> 3, d4 = i & 7;
-      const int yy = wy * WS + j / WS, xx = wx * WS + j % WS;      // shifted-frame coordinates
-      int ys = yy + shift, xs = xx + shift;                        // source (un-shifted, padded) coordinates
-      if (ys >= Hp) ys -= Hp;
-      if (xs >= Wp) xs -= Wp;
+      int ys, xs;
+      const bool real = g.src(j, ys, xs);
       f32x4 kv, vv;
-      if (ys < H && xs < W) {
-        const float* p = qkv + (((long long)t * H + ys) * W + xs) * C3 + h * HD + d4 * 4;
-        kv = *reinterpret_cast<const f32x4*>(p + C);
-        vv = *reinterpret_cast<const f32x4*>(p + 2 * C);
-      } else {
-        kv = *reinterpret_cast<const f32x4*>(qkv_bias + C + h * HD + d4 * 4);
-        vv = *reinterpret_cast<const f32x4*>(qkv_bias + 2 * C + h * HD + d4 * 4);
-      }
+      load_kv(qkv, qkv_bias, real, ((long long)t * H + ys) * W + xs, C, h * HD + d4 * 4, kv, vv);
       *reinterpret_cast<f32x4*>(&sK[wave][j * HD + d4 * 4]) = kv;
       *reinterpret_cast<f32x4*>(&sV[wave][j * HD + d4 * 4]) = vv;
     }
@@ -72,29 +63,14 @@ __global__ void __launch_bounds__(256) window_attn_kernel(const float* __restric
   if (!active || lane >= NT) return;
 
   const int iy = lane / WS, ix = lane % WS;
-  const int yy = wy * WS + iy, xx = wx * WS + ix;
-  int ys = yy + shift, xs = xx + shift;
-  if (ys >= Hp) ys -= Hp;
-  if (xs >= Wp) xs -= Wp;
-  const bool real = (ys < H && xs < W);
+  int ys, xs;
+  const bool real = g.src(lane, ys, xs);
   const float scale = 0.17677669529663687f;  // 32^-0.5
   float q[HD];
-  {
-    const float* p = real ? qkv + (((long long)t * H + ys) * W + xs) * C3 + h * HD : qkv_bias + h * HD;
-#pragma unroll
-    for (int d4 = 0; d4 < 8; ++d4) {
-      const f32x4 v = *reinterpret_cast<const f32x4*>(p + d4 * 4);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) q[d4 * 4 + j] = v[j] * scale;
-    }
-  }
+  load_q_row(real ? qkv + (((long long)t * H + ys) * W + xs) * C3 + h * HD : qkv_bias + h * HD, scale, q);
   // region id of the -100 shift mask (built on the padded, shifted grid)
   int rid = 0;
-  if (shift > 0) {
-    const int ry = yy < Hp - WS ? 0 : (yy < Hp - shift ? 1 : 2);
-    const int rx = xx < Wp - WS ? 0 : (xx < Wp - shift ? 1 : 2);
-    rid = ry * 3 + rx;
-  }
+  if (shift > 0) rid = g.region(iy, ix);
   float s[NT];
   float mx = -3.0e38f;
 #pragma unroll
@@ -111,12 +87,7 @@ __global__ void __launch_bounds__(256) window_attn_kernel(const float* __restric
     }
     const int jy = j / WS, jx = j % WS;
     a += sB[wave][(iy - jy + WS - 1) * (2 * WS - 1) + (ix - jx + WS - 1)];
-    if (shift > 0) {
-      const int y2 = wy * WS + jy, x2 = wx * WS + jx;
-      const int ry = y2 < Hp - WS ? 0 : (y2 < Hp - shift ? 1 : 2);
-      const int rx = x2 < Wp - WS ? 0 : (x2 < Wp - shift ? 1 : 2);
-      if (ry * 3 + rx != rid) a += -100.0f;
-    }
+    if (shift > 0 && g.region(jy, jx) != rid) a += -100.0f;
     s[j] = a;
     mx = fmaxf(mx, a);
   }
@@ -163,9 +134,9 @@ __global__ void __launch_bounds__(256) window_attn_kernel(const float* __restric
 // keys crow(r,0) / crow(r,1) = the two lane halves of accumulator register r) -- no LDS round trip, no transposes.
 // K rows are padded to 33 floats (the A-operand read walks keys across lanes), V rows are read 32 consecutive
 // floats per half-wave.  Exact fp32 arithmetic (fmaf chains), online softmax with one rescale per 32-key tile.
+// This kernel keeps its own copies of the Q load, the score / PV loops, the softmax step (= online_update, attn_tile.h) and the store:
+// on the helpers its output bits were the same but its time moved by 0.5 to 1.5 % (profiles/r32_attn_ab.txt).
 // ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int crow(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
-
 template <int NW>
 __global__ void __launch_bounds__(64 * NW) mha_mfma_kernel(const float* __restrict__ Q, const float* __restrict__ K,
                                                        const float* __restrict__ V, float* __restrict__ O, int nheads,
@@ -296,32 +267,14 @@ __global__ void __launch_bounds__(64 * NW) mha_mfma_kernel(const float* __restri
 // O^T = V^T P^T if the k order inside a 16-key step is (j&3) + 8(j>>2) + 4*half -- V^T is written to LDS so that the
 // A operand of that order is two 8-byte reads.  Planes are rows of 32 halfs at an 80-byte pitch (conflict-free for the
 // row-per-lane 16-byte reads).  mode 2 (tce_set_gemm_mode): one MFMA per product on nearest-rounded operands.
+// SINGLE: that mode as a COMPILE-TIME parameter of the split-fp16 attention kernels (attn_tile.h).
 // ---------------------------------------------------------------------------------------------------
-typedef _Float16 ah16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 ah16x4 __attribute__((ext_vector_type(4)));
-typedef __fp16 afp16x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ void attn_split2(const float a, const float b, unsigned& hi, unsigned& lo, const int single) {
-  if (single) {
-    hi = __builtin_bit_cast(unsigned, afp16x2{(__fp16)a, (__fp16)b});
-    lo = 0u;
-    return;
-  }
-  const afp16x2 h = __builtin_amdgcn_cvt_pkrtz(a, b);
-  hi = __builtin_bit_cast(unsigned, h);
-  lo = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(a - (float)h[0], b - (float)h[1]));
-}
-
-// SINGLE: the arithmetic mode (tce_set_gemm_mode(2) = one MFMA per product) as a COMPILE-TIME parameter of the split-fp16 attention
-// kernels: as a run-time flag it put uniform branches around every hi / lo split and in front of the lo-term MFMAs, and the
-// basic-block boundaries kept the scheduler from overlapping the softmax arithmetic with the MFMAs (see ffn_fused_kernel).
 template <int NW, bool KSPLIT, bool SINGLE>
 __global__ void __launch_bounds__(64 * NW) mha_f16x3_kernel(const float* __restrict__ Q, const float* __restrict__ K,
                                                             const float* __restrict__ V, float* __restrict__ O, int nheads,
                                                             int Lq, int Lk, int ldq, int ldk, int ldv, int ldo, long long sQ,
                                                             long long sK, long long sV, long long sO,
                                                             const uint8_t* __restrict__ kmask, float scale) {
-  constexpr int single = SINGLE;
   // KSPLIT: the NW waves of a workgroup own the SAME 32 queries and a quarter of the keys each (private K/V tiles, no
   // workgroup barrier inside the loop), partial (max, sum, O) merged through LDS at the end -- for long key sequences
   // with too few query tiles to fill the chip a wave's serial chain of key tiles is what bounds the launch.
@@ -354,25 +307,8 @@ __global__ void __launch_bounds__(64 * NW) mha_f16x3_kernel(const float* __restr
     if (KSPLIT) __builtin_amdgcn_wave_barrier();  // wave-private tiles: a wave's LDS operations execute in order
     else __syncthreads();
   };
-  // B operand of S^T = K Q^T: lane (query, half) holds Q[q][16s + 8*half + 0..7] * scale for the two k-steps
-  typedef unsigned au32x4 __attribute__((ext_vector_type(4)));
-  typedef unsigned au32x2 __attribute__((ext_vector_type(2)));
-  ah16x8 qh[2], ql[2];
-  {
-    const float* p = Qb + (long long)min(qi, Lq - 1) * ldq;
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      const f32x4 a = *reinterpret_cast<const f32x4*>(p + 16 * s + 8 * lhi);
-      const f32x4 c = *reinterpret_cast<const f32x4*>(p + 16 * s + 8 * lhi + 4);
-      unsigned hw[4], lw[4];
-      attn_split2(a[0] * scale, a[1] * scale, hw[0], lw[0], single);
-      attn_split2(a[2] * scale, a[3] * scale, hw[1], lw[1], single);
-      attn_split2(c[0] * scale, c[1] * scale, hw[2], lw[2], single);
-      attn_split2(c[2] * scale, c[3] * scale, hw[3], lw[3], single);
-      qh[s] = __builtin_bit_cast(ah16x8, au32x4{hw[0], hw[1], hw[2], hw[3]});
-      ql[s] = __builtin_bit_cast(ah16x8, au32x4{lw[0], lw[1], lw[2], lw[3]});
-    }
-  }
+  h16x8 qh[2], ql[2];
+  load_q_split<SINGLE>(Qb + (long long)min(qi, Lq - 1) * ldq, scale, lhi, qh, ql);
   f32x16 o;
 #pragma unroll
   for (int r = 0; r < 16; ++r) o[r] = 0.f;
@@ -406,86 +342,35 @@ __global__ void __launch_bounds__(64 * NW) mha_f16x3_kernel(const float* __restr
       f32x4 kv = kreg[u], vv = vreg[u];
       if (!ok) kv = vv = f32x4{0.f, 0.f, 0.f, 0.f};
       unsigned h0, l0, h1, l1;
-      attn_split2(kv[0], kv[1], h0, l0, single);
-      attn_split2(kv[2], kv[3], h1, l1, single);
-      *reinterpret_cast<au32x2*>(sKh + j * PITCH + d4 * 8) = au32x2{h0, h1};  // K[key j][4 d4 .. +3]
-      *reinterpret_cast<au32x2*>(sKl + j * PITCH + d4 * 8) = au32x2{l0, l1};
-      // V transposed: Vt[d][key j]
-      attn_split2(vv[0], vv[1], h0, l0, single);
-      attn_split2(vv[2], vv[3], h1, l1, single);
-      unsigned short* const vh = reinterpret_cast<unsigned short*>(sVh + (d4 * 4) * PITCH) + j;
-      unsigned short* const vl = reinterpret_cast<unsigned short*>(sVl + (d4 * 4) * PITCH) + j;
-      vh[0] = (unsigned short)(h0 & 0xffffu);
-      vh[PITCH / 2] = (unsigned short)(h0 >> 16);
-      vh[2 * (PITCH / 2)] = (unsigned short)(h1 & 0xffffu);
-      vh[3 * (PITCH / 2)] = (unsigned short)(h1 >> 16);
-      vl[0] = (unsigned short)(l0 & 0xffffu);
-      vl[PITCH / 2] = (unsigned short)(l0 >> 16);
-      vl[2 * (PITCH / 2)] = (unsigned short)(l1 & 0xffffu);
-      vl[3 * (PITCH / 2)] = (unsigned short)(l1 >> 16);
+      split2(kv[0], kv[1], h0, l0, SINGLE);
+      split2(kv[2], kv[3], h1, l1, SINGLE);
+      *reinterpret_cast<u32x2*>(sKh + j * PITCH + d4 * 8) = u32x2{h0, h1};  // K[key j][4 d4 .. +3]
+      *reinterpret_cast<u32x2*>(sKl + j * PITCH + d4 * 8) = u32x2{l0, l1};
+      split2(vv[0], vv[1], h0, l0, SINGLE);
+      split2(vv[2], vv[3], h1, l1, SINGLE);
+      scatter_vt(sVh, sVl, PITCH / 2, j, d4, h0, h1, l0, l1);  // V transposed: Vt[d][key j]
     }
     for (int j = ltid; j < KT; j += NLOAD)
       sM[j] = (j < kn && !(kmask && kmask[(long long)b * Lk + k0 + j])) ? 0.f : -3.0e38f;
     if (t + 1 < t_end) fetch(k0 + KT);
     tile_sync();
-    // S^T[key][q]: A = K[key = l31][16s + 8*half + 0..7]
+    h16x8 kh[2], kl[2];
+    load_k_frags(sKh + l31 * PITCH, sKl + l31 * PITCH, lhi, kh, kl);
     f32x16 st;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) st[r] = 0.f;
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      const ah16x8 ah = *reinterpret_cast<const ah16x8*>(sKh + l31 * PITCH + (16 * s + 8 * lhi) * 2);
-      const ah16x8 al = *reinterpret_cast<const ah16x8*>(sKl + l31 * PITCH + (16 * s + 8 * lhi) * 2);
-      if (!single) {
-        st = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, ql[s], st, 0, 0, 0);
-        st = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, qh[s], st, 0, 0, 0);
-      }
-      st = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, qh[s], st, 0, 0, 0);
-    }
-    float tmax = -3.0e38f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      st[r] = sM[crow(r, lhi)] < 0.f ? -3.0e38f : fminf(st[r], 3.0e38f);  // a select: whatever the ignored key's K row holds
-      tmax = fmaxf(tmax, st[r]);
-    }
-    tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-    const float mnew = fmaxf(m, tmax);
-    const float corr = __expf(m - mnew);
-    l *= corr;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      o[r] *= corr;
-      const float pj = (st[r] > -1.0e38f) ? __expf(st[r] - mnew) : 0.f;
-      st[r] = pj;
-      l += pj;
-    }
-    // O^T[d][q] += V^T[d][key] P^T[key][q]; k-step s, element j <-> accumulator register 8s + j <-> key crow(8s + j, half)
+    scores_split<SINGLE>(kh, kl, qh, ql, st);
+    // a select: whatever the ignored key's K row holds
+    online_update(st, m, l, o, [&](const int r, const float s) { return sM[crow(r, lhi)] < 0.f ? -3.0e38f : fminf(s, 3.0e38f); });
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
-      unsigned ph[4], pl[4];
-#pragma unroll
-      for (int q2 = 0; q2 < 4; ++q2) attn_split2(st[8 * s + 2 * q2], st[8 * s + 2 * q2 + 1], ph[q2], pl[q2], single);
-      const ah16x8 bh_ = __builtin_bit_cast(ah16x8, au32x4{ph[0], ph[1], ph[2], ph[3]});
-      const ah16x8 bl_ = __builtin_bit_cast(ah16x8, au32x4{pl[0], pl[1], pl[2], pl[3]});
-      // keys of elements 0..3: 16s + 4*half + 0..3; of elements 4..7: 16s + 8 + 4*half + 0..3
-      const int kb = (16 * s + 4 * lhi) * 2;
-      const au32x2 h0 = *reinterpret_cast<const au32x2*>(sVh + l31 * PITCH + kb);
-      const au32x2 h1 = *reinterpret_cast<const au32x2*>(sVh + l31 * PITCH + kb + 16);
-      const au32x2 l0 = *reinterpret_cast<const au32x2*>(sVl + l31 * PITCH + kb);
-      const au32x2 l1 = *reinterpret_cast<const au32x2*>(sVl + l31 * PITCH + kb + 16);
-      const ah16x8 vh_ = __builtin_bit_cast(ah16x8, au32x4{h0[0], h0[1], h1[0], h1[1]});
-      const ah16x8 vl_ = __builtin_bit_cast(ah16x8, au32x4{l0[0], l0[1], l1[0], l1[1]});
-      if (!single) {
-        o = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh_, bl_, o, 0, 0, 0);
-        o = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl_, bh_, o, 0, 0, 0);
-      }
-      o = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh_, bh_, o, 0, 0, 0);
+      h16x8 ph, pl;
+      p_frag<SINGLE>(st, s, ph, pl);
+      mma3(o, load_vt_frag(sVh + l31 * PITCH, s, lhi), load_vt_frag(sVl + l31 * PITCH, s, lhi), ph, pl, SINGLE);
     }
-    m = mnew;
   }
   l += __shfl_xor(l, 32, 64);
   if (KSPLIT) {
-    // merge the NW partial results of these 32 queries: O = sum_w O_w e^(m_w - m*), l likewise
+    // merge the NW partial results of these 32 queries: O = sum_w O_w e^(m_w - m*), l likewise.  Kept here (= ksplit_merge, then
+    // store_o): through the helpers the merge no longer fuses with the store, and this form took 1 to 1.7 % longer
     __shared__ float sO[NW][HD][33];
     __shared__ float sML[NW][2][32];
 #pragma unroll
@@ -548,24 +433,16 @@ __global__ void __launch_bounds__(256) mha_planes_kernel(const float* __restrict
     kv = *reinterpret_cast<const f32x4*>(K + b * sK + (long long)key * ldk + h * HD + d4 * 4);
     vv = *reinterpret_cast<const f32x4*>(V + b * sV + (long long)key * ldv + h * HD + d4 * 4);
   }
-  typedef unsigned au32x2 __attribute__((ext_vector_type(2)));
   unsigned h0, l0, h1, l1;
-  attn_split2(kv[0], kv[1], h0, l0, single);
-  attn_split2(kv[2], kv[3], h1, l1, single);
+  split2(kv[0], kv[1], h0, l0, single);
+  split2(kv[2], kv[3], h1, l1, single);
   unsigned char* const Kh = ws + (long long)bh * Lkp * 64;
   unsigned char* const Kl = Kh + plane;
-  *reinterpret_cast<au32x2*>(Kh + (long long)key * 64 + d4 * 8) = au32x2{h0, h1};
-  *reinterpret_cast<au32x2*>(Kl + (long long)key * 64 + d4 * 8) = au32x2{l0, l1};
-  attn_split2(vv[0], vv[1], h0, l0, single);
-  attn_split2(vv[2], vv[3], h1, l1, single);
-  tvh[4 * d4 + 0][j] = (unsigned short)(h0 & 0xffffu);
-  tvh[4 * d4 + 1][j] = (unsigned short)(h0 >> 16);
-  tvh[4 * d4 + 2][j] = (unsigned short)(h1 & 0xffffu);
-  tvh[4 * d4 + 3][j] = (unsigned short)(h1 >> 16);
-  tvl[4 * d4 + 0][j] = (unsigned short)(l0 & 0xffffu);
-  tvl[4 * d4 + 1][j] = (unsigned short)(l0 >> 16);
-  tvl[4 * d4 + 2][j] = (unsigned short)(l1 & 0xffffu);
-  tvl[4 * d4 + 3][j] = (unsigned short)(l1 >> 16);
+  *reinterpret_cast<u32x2*>(Kh + (long long)key * 64 + d4 * 8) = u32x2{h0, h1};
+  *reinterpret_cast<u32x2*>(Kl + (long long)key * 64 + d4 * 8) = u32x2{l0, l1};
+  split2(vv[0], vv[1], h0, l0, single);
+  split2(vv[2], vv[3], h1, l1, single);
+  scatter_vt(tvh, tvl, 36, j, d4, h0, h1, l0, l1);
   __syncthreads();
   // thread (d = tid >> 3, k4 = tid & 7): 4 consecutive keys of channel d -> 8 bytes
   const int d = tid >> 3, k4 = tid & 7;
@@ -574,10 +451,10 @@ __global__ void __launch_bounds__(256) mha_planes_kernel(const float* __restrict
   unsigned char* const Vl = Vh + plane;
   const unsigned short* rh = &tvh[d][4 * k4];
   const unsigned short* rl = &tvl[d][4 * k4];
-  *reinterpret_cast<au32x2*>(Vh + d * 64 + 8 * k4) =
-      au32x2{(unsigned)rh[0] | ((unsigned)rh[1] << 16), (unsigned)rh[2] | ((unsigned)rh[3] << 16)};
-  *reinterpret_cast<au32x2*>(Vl + d * 64 + 8 * k4) =
-      au32x2{(unsigned)rl[0] | ((unsigned)rl[1] << 16), (unsigned)rl[2] | ((unsigned)rl[3] << 16)};
+  *reinterpret_cast<u32x2*>(Vh + d * 64 + 8 * k4) =
+      u32x2{(unsigned)rh[0] | ((unsigned)rh[1] << 16), (unsigned)rh[2] | ((unsigned)rh[3] << 16)};
+  *reinterpret_cast<u32x2*>(Vl + d * 64 + 8 * k4) =
+      u32x2{(unsigned)rl[0] | ((unsigned)rl[1] << 16), (unsigned)rl[2] | ((unsigned)rl[3] << 16)};
 }
 
 template <bool KSPLIT, bool SINGLE>
@@ -585,7 +462,6 @@ __global__ void __launch_bounds__(256) mha_presplit_kernel(const float* __restri
                                                            float* __restrict__ O, int nheads, int Lq, int Lk, int Lkp, int ldq,
                                                            int ldo, long long sQ, long long sO, long long plane,
                                                            const uint8_t* __restrict__ kmask, float scale) {
-  constexpr int single = SINGLE;
   constexpr int KT = 32, NW = 4;
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
@@ -600,24 +476,8 @@ __global__ void __launch_bounds__(256) mha_presplit_kernel(const float* __restri
   const unsigned char* const Kl = Kh + plane;
   const unsigned char* const Vh = ws + 2 * plane + (long long)bh * (Lkp / 32) * 2048;
   const unsigned char* const Vl = Vh + plane;
-  typedef unsigned au32x4 __attribute__((ext_vector_type(4)));
-  typedef unsigned au32x2 __attribute__((ext_vector_type(2)));
-  ah16x8 qh[2], ql[2];
-  {
-    const float* p = Qb + (long long)min(qi, Lq - 1) * ldq;
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      const f32x4 a = *reinterpret_cast<const f32x4*>(p + 16 * s + 8 * lhi);
-      const f32x4 c = *reinterpret_cast<const f32x4*>(p + 16 * s + 8 * lhi + 4);
-      unsigned hw[4], lw[4];
-      attn_split2(a[0] * scale, a[1] * scale, hw[0], lw[0], single);
-      attn_split2(a[2] * scale, a[3] * scale, hw[1], lw[1], single);
-      attn_split2(c[0] * scale, c[1] * scale, hw[2], lw[2], single);
-      attn_split2(c[2] * scale, c[3] * scale, hw[3], lw[3], single);
-      qh[s] = __builtin_bit_cast(ah16x8, au32x4{hw[0], hw[1], hw[2], hw[3]});
-      ql[s] = __builtin_bit_cast(ah16x8, au32x4{lw[0], lw[1], lw[2], lw[3]});
-    }
-  }
+  h16x8 qh[2], ql[2];
+  load_q_split<SINGLE>(Qb + (long long)min(qi, Lq - 1) * ldq, scale, lhi, qh, ql);
   f32x16 o;
 #pragma unroll
   for (int r = 0; r < 16; ++r) o[r] = 0.f;
@@ -625,23 +485,18 @@ __global__ void __launch_bounds__(256) mha_presplit_kernel(const float* __restri
   const int ntiles = Lkp / KT;
   const int t_begin = KSPLIT ? (int)((long long)wave * ntiles / NW) : 0;
   const int t_end = KSPLIT ? (int)((long long)(wave + 1) * ntiles / NW) : ntiles;
-  // fragments of one key tile: K (hi, lo) x 2 k-steps, V^T (hi, lo) x 2 k-steps x 2 runs of 4 keys
+  // fragments of one key tile: K (hi, lo) x 2 k-steps, V^T (hi, lo) x 2 k-steps
   struct Frag {
-    ah16x8 kh[2], kl[2];
-    au32x2 vh[2][2], vl[2][2];
+    h16x8 kh[2], kl[2], vh[2], vl[2];
   };
   auto load_tile = [&](Frag& f, const int t) {
     const long long krow = ((long long)t * KT + l31) * 64;
     const long long vrow = (long long)t * 2048 + l31 * 64;
+    load_k_frags(Kh + krow, Kl + krow, lhi, f.kh, f.kl);
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
-      f.kh[s] = *reinterpret_cast<const ah16x8*>(Kh + krow + (16 * s + 8 * lhi) * 2);
-      f.kl[s] = *reinterpret_cast<const ah16x8*>(Kl + krow + (16 * s + 8 * lhi) * 2);
-      const int kb = (16 * s + 4 * lhi) * 2;
-      f.vh[s][0] = *reinterpret_cast<const au32x2*>(Vh + vrow + kb);
-      f.vh[s][1] = *reinterpret_cast<const au32x2*>(Vh + vrow + kb + 16);
-      f.vl[s][0] = *reinterpret_cast<const au32x2*>(Vl + vrow + kb);
-      f.vl[s][1] = *reinterpret_cast<const au32x2*>(Vl + vrow + kb + 16);
+      f.vh[s] = load_vt_frag(Vh + vrow, s, lhi);
+      f.vl[s] = load_vt_frag(Vl + vrow, s, lhi);
     }
   };
   Frag cur, nxt;
@@ -650,96 +505,29 @@ __global__ void __launch_bounds__(256) mha_presplit_kernel(const float* __restri
     if (t + 1 < t_end) load_tile(nxt, t + 1);
     const int k0 = t * KT;
     f32x16 st;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) st[r] = 0.f;
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      if (!single) {
-        st = __builtin_amdgcn_mfma_f32_32x32x16_f16(cur.kh[s], ql[s], st, 0, 0, 0);
-        st = __builtin_amdgcn_mfma_f32_32x32x16_f16(cur.kl[s], qh[s], st, 0, 0, 0);
-      }
-      st = __builtin_amdgcn_mfma_f32_32x32x16_f16(cur.kh[s], qh[s], st, 0, 0, 0);
-    }
-    float tmax = -3.0e38f;
+    scores_split<SINGLE>(cur.kh, cur.kl, qh, ql, st);
     const bool edge = k0 + KT > Lk || kmask != nullptr;  // uniform
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      float v = fminf(st[r], 3.0e38f);
+    online_update(st, m, l, o, [&](const int r, const float s) {
+      float v = fminf(s, 3.0e38f);
       if (edge) {
         const int key = k0 + crow(r, lhi);
         if (key >= Lk || (kmask && kmask[(long long)b * Lk + key])) v = -3.0e38f;
       }
-      st[r] = v;
-      tmax = fmaxf(tmax, v);
-    }
-    tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-    const float mnew = fmaxf(m, tmax);
-    const float corr = __expf(m - mnew);
-    l *= corr;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      o[r] *= corr;
-      const float pj = (st[r] > -1.0e38f) ? __expf(st[r] - mnew) : 0.f;
-      st[r] = pj;
-      l += pj;
-    }
+      return v;
+    });
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
-      unsigned ph[4], pl[4];
-#pragma unroll
-      for (int q2 = 0; q2 < 4; ++q2) attn_split2(st[8 * s + 2 * q2], st[8 * s + 2 * q2 + 1], ph[q2], pl[q2], single);
-      const ah16x8 bh_ = __builtin_bit_cast(ah16x8, au32x4{ph[0], ph[1], ph[2], ph[3]});
-      const ah16x8 bl_ = __builtin_bit_cast(ah16x8, au32x4{pl[0], pl[1], pl[2], pl[3]});
-      const ah16x8 vh_ = __builtin_bit_cast(ah16x8, au32x4{cur.vh[s][0][0], cur.vh[s][0][1], cur.vh[s][1][0], cur.vh[s][1][1]});
-      const ah16x8 vl_ = __builtin_bit_cast(ah16x8, au32x4{cur.vl[s][0][0], cur.vl[s][0][1], cur.vl[s][1][0], cur.vl[s][1][1]});
-      if (!single) {
-        o = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh_, bl_, o, 0, 0, 0);
-        o = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl_, bh_, o, 0, 0, 0);
-      }
-      o = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh_, bh_, o, 0, 0, 0);
+      h16x8 ph, pl;
+      p_frag<SINGLE>(st, s, ph, pl);
+      mma3(o, cur.vh[s], cur.vl[s], ph, pl, SINGLE);
     }
-    m = mnew;
     cur = nxt;
   }
   l += __shfl_xor(l, 32, 64);
-  if (KSPLIT) {
-    __shared__ float sO[NW][HD][33];
-    __shared__ float sML[NW][2][32];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) sO[wave][crow(r, lhi)][l31] = o[r];
-    if (lhi == 0) {
-      sML[wave][0][l31] = m;
-      sML[wave][1][l31] = l;
-    }
-    __syncthreads();
-    if (wave != 0) return;
-    float mstar = -3.0e38f;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) mstar = fmaxf(mstar, sML[w][0][l31]);
-    float f[NW];
-    l = 0.f;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) {
-      f[w] = __expf(sML[w][0][l31] - mstar);
-      l += sML[w][1][l31] * f[w];
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      float acc = 0.f;
-#pragma unroll
-      for (int w = 0; w < NW; ++w) acc = fmaf(sO[w][crow(r, lhi)][l31], f[w], acc);
-      o[r] = acc;
-    }
+  if constexpr (KSPLIT) {
+    if (!ksplit_merge<NW>(o, m, l, wave, l31, lhi)) return;
   }
-  if (qok) {
-    const float inv = l > 0.f ? 1.0f / l : 0.f;
-    float* po = O + b * sO + (long long)qi * ldo + h * HD;
-#pragma unroll
-    for (int g4 = 0; g4 < 4; ++g4) {
-      f32x4 v = {o[4 * g4] * inv, o[4 * g4 + 1] * inv, o[4 * g4 + 2] * inv, o[4 * g4 + 3] * inv};
-      *reinterpret_cast<f32x4*>(po + 8 * g4 + 4 * lhi) = v;
-    }
-  }
+  if (qok) store_o(O + b * sO + (long long)qi * ldo + h * HD, o, l > 0.f ? 1.0f / l : 0.f, lhi);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -765,7 +553,6 @@ __global__ void __launch_bounds__(256) window_attn_mfma_kernel(const float* __re
   const int l31 = lane & 31, lhi = lane >> 5;
   const long long item = (long long)blockIdx.x * 2 + it;  // ((t*nWy + wy)*nWx + wx)*nH + h
   const bool active = item < total;
-  const int Hp = nWy * WS, Wp = nWx * WS;
   int h = 0, wx = 0, wy = 0, t = 0;
   if (active) {
     long long r = item;
@@ -774,16 +561,8 @@ __global__ void __launch_bounds__(256) window_attn_mfma_kernel(const float* __re
     wy = (int)(r % nWy); r /= nWy;
     t = (int)r;
   }
+  const Win2D g{wy, wx, shift, nWy * WS, nWx * WS, H, W};
   const int C3 = 3 * C;
-  // token j of the window -> source pixel (un-shifted, padded coordinates); false = padded token (qkv = bias)
-  auto src_of = [&](int j, int& ys, int& xs) {
-    const int yy = wy * WS + j / WS, xx = wx * WS + j % WS;
-    ys = yy + shift;
-    xs = xx + shift;
-    if (ys >= Hp) ys -= Hp;
-    if (xs >= Wp) xs -= Wp;
-    return ys < H && xs < W;
-  };
   if (active) {
     // the item's two waves (128 threads) stage K and V: 64 rows x 8 float4, rows >= 49 are zero
     const int t2 = tid & 127;
@@ -792,14 +571,8 @@ __global__ void __launch_bounds__(256) window_attn_mfma_kernel(const float* __re
       f32x4 kv = {0.f, 0.f, 0.f, 0.f}, vv = kv;
       if (j < NT) {
         int ys, xs;
-        if (src_of(j, ys, xs)) {
-          const float* p = qkv + (((long long)t * H + ys) * W + xs) * C3 + h * HD + d4 * 4;
-          kv = *reinterpret_cast<const f32x4*>(p + C);
-          vv = *reinterpret_cast<const f32x4*>(p + 2 * C);
-        } else {
-          kv = *reinterpret_cast<const f32x4*>(qkv_bias + C + h * HD + d4 * 4);
-          vv = *reinterpret_cast<const f32x4*>(qkv_bias + 2 * C + h * HD + d4 * 4);
-        }
+        const bool real = g.src(j, ys, xs);
+        load_kv(qkv, qkv_bias, real, ((long long)t * H + ys) * W + xs, C, h * HD + d4 * 4, kv, vv);
       }
 #pragma unroll
       for (int c = 0; c < 4; ++c) sK[it][j * KP + d4 * 4 + c] = kv[c];
@@ -813,41 +586,25 @@ __global__ void __launch_bounds__(256) window_attn_mfma_kernel(const float* __re
   const int qi = qt * 32 + l31;          // query index inside the window (>= 49: padding lane, never stored)
   const int qc = min(qi, NT - 1);
   int qys, qxs;
-  const bool real = src_of(qc, qys, qxs) && qi < NT;
+  const bool qreal = g.src(qc, qys, qxs);
+  const bool real = qreal && qi < NT;
   const int iy = qc / WS, ix = qc % WS;
   const float scale = 0.17677669529663687f;  // 32^-0.5
   // B operand of S^T = K Q^T: lane holds q[d = 2s + lhi] * scale
   float qreg[16];
   {
-    int ys, xs;
-    const bool qreal = src_of(qc, ys, xs);
-    const float* p = qreal ? qkv + (((long long)t * H + ys) * W + xs) * C3 + h * HD : qkv_bias + h * HD;
     float qrow[HD];
-#pragma unroll
-    for (int d4 = 0; d4 < 8; ++d4) {
-      const f32x4 v = *reinterpret_cast<const f32x4*>(p + d4 * 4);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) qrow[d4 * 4 + j] = v[j] * scale;
-    }
+    load_q_row(qreal ? qkv + (((long long)t * H + qys) * W + qxs) * C3 + h * HD : qkv_bias + h * HD, scale, qrow);
 #pragma unroll
     for (int s2 = 0; s2 < 16; ++s2) qreg[s2] = lhi ? qrow[2 * s2 + 1] : qrow[2 * s2];
   }
   int rid = 0;  // region id of the -100 shift mask (built on the padded, shifted grid)
-  if (shift > 0) {
-    const int yy = wy * WS + iy, xx = wx * WS + ix;
-    const int ry = yy < Hp - WS ? 0 : (yy < Hp - shift ? 1 : 2);
-    const int rx = xx < Wp - WS ? 0 : (xx < Wp - shift ? 1 : 2);
-    rid = ry * 3 + rx;
-  }
+  if (shift > 0) rid = g.region(iy, ix);
   f32x16 st[2];
   float mx = -3.0e38f;
 #pragma unroll
   for (int kt = 0; kt < 2; ++kt) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) st[kt][r] = 0.f;
-#pragma unroll
-    for (int s2 = 0; s2 < 16; ++s2)
-      st[kt] = __builtin_amdgcn_mfma_f32_32x32x2f32(sK[it][(kt * 32 + l31) * KP + 2 * s2 + lhi], qreg[s2], st[kt], 0, 0, 0);
+    scores_f32(&sK[it][(kt * 32 + l31) * KP + lhi], qreg, st[kt]);
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int j = kt * 32 + crow(r, lhi);  // key index inside the window
@@ -855,17 +612,13 @@ __global__ void __launch_bounds__(256) window_attn_mfma_kernel(const float* __re
       if (j < NT) {
         const int jy = j / WS, jx = j % WS;
         a = st[kt][r] + sB[it][(iy - jy + WS - 1) * (2 * WS - 1) + (ix - jx + WS - 1)];
-        if (shift > 0) {
-          const int y2 = wy * WS + jy, x2 = wx * WS + jx;
-          const int ry = y2 < Hp - WS ? 0 : (y2 < Hp - shift ? 1 : 2);
-          const int rx = x2 < Wp - WS ? 0 : (x2 < Wp - shift ? 1 : 2);
-          if (ry * 3 + rx != rid) a += -100.0f;
-        }
+        if (shift > 0 && g.region(jy, jx) != rid) a += -100.0f;
       }
       st[kt][r] = a;
       mx = fmaxf(mx, a);
     }
   }
+  // all 49 keys are in registers: a plain two-pass softmax, no running maximum
   mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
   float l = 0.f;
 #pragma unroll
@@ -880,41 +633,21 @@ __global__ void __launch_bounds__(256) window_attn_mfma_kernel(const float* __re
   f32x16 o;
 #pragma unroll
   for (int r = 0; r < 16; ++r) o[r] = 0.f;
-  // O^T[d][q] += V^T[d][key] P^T[key][q] : k-step r pairs keys crow(r,0), crow(r,1)
 #pragma unroll
-  for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-    for (int r = 0; r < 16; ++r)
-      o = __builtin_amdgcn_mfma_f32_32x32x2f32(sV[it][(kt * 32 + crow(r, lhi)) * HD + l31], st[kt][r], o, 0, 0, 0);
-  if (real) {
-    const float inv = 1.0f / l;
-    float* po = out + (((long long)t * H + qys) * W + qxs) * C + h * HD;
-#pragma unroll
-    for (int g4 = 0; g4 < 4; ++g4) {  // registers 4g..4g+3 are 4 consecutive d: d = 8g + 4*lhi + (0..3)
-      f32x4 v = {o[4 * g4] * inv, o[4 * g4 + 1] * inv, o[4 * g4 + 2] * inv, o[4 * g4 + 3] * inv};
-      *reinterpret_cast<f32x4*>(po + 8 * g4 + 4 * lhi) = v;
-    }
-  }
+  for (int kt = 0; kt < 2; ++kt) pv_f32(&sV[it][kt * 32 * HD + l31], lhi, st[kt], o);
+  if (real) store_o(out + (((long long)t * H + qys) * W + qxs) * C + h * HD, o, 1.0f / l, lhi);
 }
 
 // ---------------------------------------------------------------------------------------------------
 // Video-Swin 3-D window attention (video_swin_transformer.py:71-84,138-169,215-249,316-329).
 // One workgroup per (window, head); the window's K/V (<= 8*7*7 = 392 tokens x 32) and this head's column of
-// the relative-position table live in LDS for the whole workgroup.  Reference quirks reproduced:
+// the relative-position table live in LDS for the whole workgroup.  Reference quirks reproduced (geometry: Win3D):
 //   * windows SHRINK to the feature size when it is <= the nominal window (no padding in that dim, no shift);
 //   * the bias index is relative_position_index[:N,:N] of the FULL (8,7,7) window, i.e. token n of a shrunken
 //     window is re-read in full-window coordinates (n/49, (n%49)/7, n%7);
 //   * padded tokens (temporal padding when T is not a multiple of the depth) carry qkv = bias and are not masked;
 //   * the -100 shift mask uses region ids on the padded, shifted grid; a dim with shift 0 has one region.
 // ---------------------------------------------------------------------------------------------------
-struct Win3D {
-  int D, H, W;        // token grid (frames, rows, cols)
-  int wd, wh, ww;     // effective window
-  int sd, sh, sw;     // effective shift (0 if the block is not shifted)
-  int Dp, Hp, Wp;     // padded grid
-  int fd, fh, fw;     // nominal (full) window: 8,7,7
-};
-
 __global__ void __launch_bounds__(256) window_attn3d_kernel(const float* __restrict__ qkv,
                                                             const float* __restrict__ qkv_bias,
                                                             const float* __restrict__ table, float* __restrict__ out,
@@ -936,17 +669,10 @@ __global__ void __launch_bounds__(256) window_attn3d_kernel(const float* __restr
   const int bd = widx / nwy;
   const int C3 = 3 * C;
   for (int n = tid; n < N; n += 256) {
-    const int x = n % g.ww, y = (n / g.ww) % g.wh, d = n / (g.ww * g.wh);
-    const int dd = bd * g.wd + d, yy = by * g.wh + y, xx = bx * g.ww + x;  // shifted-grid coordinates
-    int ds = dd + g.sd, ys = yy + g.sh, xs = xx + g.sw;
-    if (ds >= g.Dp) ds -= g.Dp;
-    if (ys >= g.Hp) ys -= g.Hp;
-    if (xs >= g.Wp) xs -= g.Wp;
-    sSrc[n] = (ds < g.D && ys < g.H && xs < g.W) ? (ds * g.H + ys) * g.W + xs : -1;
-    const int rd = g.sd > 0 ? (dd < g.Dp - g.wd ? 0 : (dd < g.Dp - g.sd ? 1 : 2)) : 0;
-    const int ry = g.sh > 0 ? (yy < g.Hp - g.wh ? 0 : (yy < g.Hp - g.sh ? 1 : 2)) : 0;
-    const int rx = g.sw > 0 ? (xx < g.Wp - g.ww ? 0 : (xx < g.Wp - g.sw ? 1 : 2)) : 0;
-    sRid[n] = (rd * 3 + ry) * 3 + rx;
+    int src, rid;
+    g.token(n, bd, by, bx, src, rid);
+    sSrc[n] = src;
+    sRid[n] = rid;
   }
   for (int i = tid; i < table_rows; i += 256) sB[i] = table[(long long)i * nH + h];
   __syncthreads();
@@ -954,14 +680,7 @@ __global__ void __launch_bounds__(256) window_attn3d_kernel(const float* __restr
     const int n = i >> 3, d4 = i & 7;
     const int srow = sSrc[n];
     f32x4 kv, vv;
-    if (srow >= 0) {
-      const float* p = qkv + (long long)srow * C3 + h * HD + d4 * 4;
-      kv = *reinterpret_cast<const f32x4*>(p + C);
-      vv = *reinterpret_cast<const f32x4*>(p + 2 * C);
-    } else {
-      kv = *reinterpret_cast<const f32x4*>(qkv_bias + C + h * HD + d4 * 4);
-      vv = *reinterpret_cast<const f32x4*>(qkv_bias + 2 * C + h * HD + d4 * 4);
-    }
+    load_kv(qkv, qkv_bias, srow >= 0, srow, C, h * HD + d4 * 4, kv, vv);
     *reinterpret_cast<f32x4*>(&sK[n * HD + d4 * 4]) = kv;
     *reinterpret_cast<f32x4*>(&sV[n * HD + d4 * 4]) = vv;
   }
@@ -973,20 +692,15 @@ __global__ void __launch_bounds__(256) window_attn3d_kernel(const float* __restr
     const int i = q0 + tid;
     if (i >= N) break;
     const int srow = sSrc[i];
-    const float* qp = srow >= 0 ? qkv + (long long)srow * C3 + h * HD : qkv_bias + h * HD;
     float q[HD], o[HD];
-#pragma unroll
-    for (int d4 = 0; d4 < 8; ++d4) {
-      const f32x4 v = *reinterpret_cast<const f32x4*>(qp + d4 * 4);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) q[d4 * 4 + j] = v[j] * scale;
-    }
+    load_q_row(srow >= 0 ? qkv + (long long)srow * C3 + h * HD : qkv_bias + h * HD, scale, q);
 #pragma unroll
     for (int d = 0; d < HD; ++d) o[d] = 0.f;
     // full-window coordinates of flat index i (the [:N,:N] slicing quirk)
     const int id_ = i / fhw, iy_ = (i % fhw) / g.fw, ix_ = i % g.fw;
     const int rid = sRid[i];
     float m = -3.0e38f, l = 0.f;
+    // the online softmax of a VALU row (32 scores of one query per lane, the PV product inside the probability loop): not online_update's shape
     for (int k0 = 0; k0 < N; k0 += 32) {
       float s[32];
       float tmax = -3.0e38f;
@@ -1069,9 +783,6 @@ __global__ void __launch_bounds__(64 * NW) window_attn3d_mfma_kernel(const float
                                                                      const float* __restrict__ table,
                                                                      float* __restrict__ out, Win3D g, int C, int nH,
                                                                      int table_rows, int NKP) {
-  constexpr int single = SINGLE;
-  typedef unsigned au32x4 __attribute__((ext_vector_type(4)));
-  typedef unsigned au32x2 __attribute__((ext_vector_type(2)));
   constexpr int KPITCH = 80, VPITCH = NKMAX * 2 + 8;
   __shared__ __attribute__((aligned(16))) unsigned char sKh[NKMAX * KPITCH], sKl[NKMAX * KPITCH], sVh[HD * VPITCH], sVl[HD * VPITCH];
   __shared__ float sB[TROWS + 1];
@@ -1095,19 +806,11 @@ __global__ void __launch_bounds__(64 * NW) window_attn3d_mfma_kernel(const float
   for (int n = tid; n < NKP; n += nthr) {
     int src = -2, cr = 0;
     if (n < N) {
-      const int x = n % g.ww, y = (n / g.ww) % g.wh, d = n / (g.ww * g.wh);
-      const int dd = bd * g.wd + d, yy = by * g.wh + y, xx = bx * g.ww + x;  // shifted-grid coordinates
-      int ds = dd + g.sd, ys = yy + g.sh, xs = xx + g.sw;
-      if (ds >= g.Dp) ds -= g.Dp;
-      if (ys >= g.Hp) ys -= g.Hp;
-      if (xs >= g.Wp) xs -= g.Wp;
-      src = (ds < g.D && ys < g.H && xs < g.W) ? (ds * g.H + ys) * g.W + xs : -1;
-      const int rd = g.sd > 0 ? (dd < g.Dp - g.wd ? 0 : (dd < g.Dp - g.sd ? 1 : 2)) : 0;
-      const int ry = g.sh > 0 ? (yy < g.Hp - g.wh ? 0 : (yy < g.Hp - g.sh ? 1 : 2)) : 0;
-      const int rx = g.sw > 0 ? (xx < g.Wp - g.ww ? 0 : (xx < g.Wp - g.sw ? 1 : 2)) : 0;
+      int rid;
+      g.token(n, bd, by, bx, src, rid);
       // full-window coordinates of flat index n (relative_position_index[:N,:N] of the nominal window)
       const int code = ((n / fhw) * (2 * g.fh - 1) + (n % fhw) / g.fw) * (2 * g.fw - 1) + n % g.fw;
-      cr = code | (((rd * 3 + ry) * 3 + rx) << 16);
+      cr = code | (rid << 16);
     }
     sSrc[n] = src;
     sCR[n] = cr;
@@ -1123,32 +826,15 @@ __global__ void __launch_bounds__(64 * NW) window_attn3d_mfma_kernel(const float
     const int n = i >> 3, d4 = i & 7;
     const int srow = sSrc[n];
     f32x4 kv = {0.f, 0.f, 0.f, 0.f}, vv = kv;
-    if (srow >= 0) {
-      const float* p = qkv + (long long)srow * C3 + h * HD + d4 * 4;
-      kv = *reinterpret_cast<const f32x4*>(p + C);
-      vv = *reinterpret_cast<const f32x4*>(p + 2 * C);
-    } else if (srow == -1) {
-      kv = *reinterpret_cast<const f32x4*>(qkv_bias + C + h * HD + d4 * 4);
-      vv = *reinterpret_cast<const f32x4*>(qkv_bias + 2 * C + h * HD + d4 * 4);
-    }
+    if (srow >= -1) load_kv(qkv, qkv_bias, srow >= 0, srow, C, h * HD + d4 * 4, kv, vv);
     unsigned h0, l0, h1, l1;
-    attn_split2(kv[0], kv[1], h0, l0, single);
-    attn_split2(kv[2], kv[3], h1, l1, single);
-    *reinterpret_cast<au32x2*>(sKh + n * KPITCH + d4 * 8) = au32x2{h0, h1};
-    *reinterpret_cast<au32x2*>(sKl + n * KPITCH + d4 * 8) = au32x2{l0, l1};
-    attn_split2(vv[0], vv[1], h0, l0, single);
-    attn_split2(vv[2], vv[3], h1, l1, single);
-    unsigned short* const vh = reinterpret_cast<unsigned short*>(sVh + (d4 * 4) * VPITCH) + n;
-    unsigned short* const vl = reinterpret_cast<unsigned short*>(sVl + (d4 * 4) * VPITCH) + n;
-    const int vp = VPITCH / 2;
-    vh[0] = (unsigned short)(h0 & 0xffffu);
-    vh[vp] = (unsigned short)(h0 >> 16);
-    vh[2 * vp] = (unsigned short)(h1 & 0xffffu);
-    vh[3 * vp] = (unsigned short)(h1 >> 16);
-    vl[0] = (unsigned short)(l0 & 0xffffu);
-    vl[vp] = (unsigned short)(l0 >> 16);
-    vl[2 * vp] = (unsigned short)(l1 & 0xffffu);
-    vl[3 * vp] = (unsigned short)(l1 >> 16);
+    split2(kv[0], kv[1], h0, l0, SINGLE);
+    split2(kv[2], kv[3], h1, l1, SINGLE);
+    *reinterpret_cast<u32x2*>(sKh + n * KPITCH + d4 * 8) = u32x2{h0, h1};
+    *reinterpret_cast<u32x2*>(sKl + n * KPITCH + d4 * 8) = u32x2{l0, l1};
+    split2(vv[0], vv[1], h0, l0, SINGLE);
+    split2(vv[2], vv[3], h1, l1, SINGLE);
+    scatter_vt(sVh, sVl, VPITCH / 2, n, d4, h0, h1, l0, l1);
   }
   __syncthreads();
   // the -100 mask separates the regions of the shifted grid's LAST window along each shifted dimension; every other window
@@ -1164,22 +850,8 @@ __global__ void __launch_bounds__(64 * NW) window_attn3d_mfma_kernel(const float
     const int crq = sCR[qc];
     // table index = code_q + koff - code_k (never negative); the -100 mask applies where the region ids differ
     const int cq = (crq & 0xffff) + koff, rq = crq >> 16;
-    ah16x8 qh[2], ql[2];
-    {
-      const float* p = srow >= 0 ? qkv + (long long)srow * C3 + h * HD : qkv_bias + h * HD;
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        const f32x4 a = *reinterpret_cast<const f32x4*>(p + 16 * s + 8 * lhi);
-        const f32x4 c = *reinterpret_cast<const f32x4*>(p + 16 * s + 8 * lhi + 4);
-        unsigned hw[4], lw[4];
-        attn_split2(a[0] * scale, a[1] * scale, hw[0], lw[0], single);
-        attn_split2(a[2] * scale, a[3] * scale, hw[1], lw[1], single);
-        attn_split2(c[0] * scale, c[1] * scale, hw[2], lw[2], single);
-        attn_split2(c[2] * scale, c[3] * scale, hw[3], lw[3], single);
-        qh[s] = __builtin_bit_cast(ah16x8, au32x4{hw[0], hw[1], hw[2], hw[3]});
-        ql[s] = __builtin_bit_cast(ah16x8, au32x4{lw[0], lw[1], lw[2], lw[3]});
-      }
-    }
+    h16x8 qh[2], ql[2];
+    load_q_split<SINGLE>(srow >= 0 ? qkv + (long long)srow * C3 + h * HD : qkv_bias + h * HD, scale, lhi, qh, ql);
     f32x16 o;
 #pragma unroll
     for (int r = 0; r < 16; ++r) o[r] = 0.f;
@@ -1189,26 +861,16 @@ __global__ void __launch_bounds__(64 * NW) window_attn3d_mfma_kernel(const float
     auto key_tile = [&](const int kt, auto masked_c, auto ragged_c) {
       constexpr bool MASKED = decltype(masked_c)::value, RAGGED = decltype(ragged_c)::value;
       const int k0 = kt * 32;
+      h16x8 kh[2], kl[2];
+      load_k_frags(sKh + (k0 + l31) * KPITCH, sKl + (k0 + l31) * KPITCH, lhi, kh, kl);
       f32x16 st;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) st[r] = 0.f;
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        const ah16x8 ah = *reinterpret_cast<const ah16x8*>(sKh + (k0 + l31) * KPITCH + (16 * s + 8 * lhi) * 2);
-        const ah16x8 al = *reinterpret_cast<const ah16x8*>(sKl + (k0 + l31) * KPITCH + (16 * s + 8 * lhi) * 2);
-        if (!single) {
-          st = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, ql[s], st, 0, 0, 0);
-          st = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, qh[s], st, 0, 0, 0);
-        }
-        st = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, qh[s], st, 0, 0, 0);
-      }
-      float tmax = -3.0e38f;
+      scores_split<SINGLE>(kh, kl, qh, ql, st);
       int kc[16];
       {
-        const au32x4* cp = reinterpret_cast<const au32x4*>(sCodeF + k0 + 16 * lhi);
+        const u32x4* cp = reinterpret_cast<const u32x4*>(sCodeF + k0 + 16 * lhi);
 #pragma unroll
         for (int q4 = 0; q4 < 4; ++q4) {
-          const au32x4 c4 = cp[q4];
+          const u32x4 c4 = cp[q4];
 #pragma unroll
           for (int c = 0; c < 4; ++c) kc[4 * q4 + c] = (int)c4[c];
         }
@@ -1216,10 +878,10 @@ __global__ void __launch_bounds__(64 * NW) window_attn3d_mfma_kernel(const float
 #pragma unroll
       for (int r = 0; r < 16; ++r) st[r] += sB[cq - kc[r]];
       if (MASKED) {
-        const au32x4* rp = reinterpret_cast<const au32x4*>(sRidF + k0 + 16 * lhi);
+        const u32x4* rp = reinterpret_cast<const u32x4*>(sRidF + k0 + 16 * lhi);
 #pragma unroll
         for (int q4 = 0; q4 < 4; ++q4) {
-          const au32x4 r4 = rp[q4];
+          const u32x4 r4 = rp[q4];
 #pragma unroll
           for (int c = 0; c < 4; ++c) st[4 * q4 + c] += (int)r4[c] != rq ? -144.26950408889634f : 0.f;  // -100 * log2(e)
         }
@@ -1229,43 +891,13 @@ __global__ void __launch_bounds__(64 * NW) window_attn3d_mfma_kernel(const float
         for (int r = 0; r < 16; ++r)
           if (k0 + crow(r, lhi) >= N) st[r] = -3.0e38f;
       }
-#pragma unroll
-      for (int r = 0; r < 16; ++r) tmax = fmaxf(tmax, st[r]);
-      tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-      const float mnew = fmaxf(m, tmax);
-      if (__builtin_amdgcn_ballot_w64(mnew > m) != 0) {  // the running maximum of some query moved: rescale (else corr = 1 for all)
-        const float corr = __builtin_amdgcn_exp2f(m - mnew);
-        l *= corr;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[r] *= corr;
-      }
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        float pj = __builtin_amdgcn_exp2f(st[r] - mnew);  // exp2(-3e38 - m) = 0 for the keys that do not exist
-        st[r] = pj;
-        l += pj;
-      }
+      online_update_exp2(st, m, l, o);
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
-        unsigned ph[4], pl[4];
-#pragma unroll
-        for (int q2 = 0; q2 < 4; ++q2) attn_split2(st[8 * s + 2 * q2], st[8 * s + 2 * q2 + 1], ph[q2], pl[q2], single);
-        const ah16x8 bh_ = __builtin_bit_cast(ah16x8, au32x4{ph[0], ph[1], ph[2], ph[3]});
-        const ah16x8 bl_ = __builtin_bit_cast(ah16x8, au32x4{pl[0], pl[1], pl[2], pl[3]});
-        const int kb = (k0 + 16 * s + 4 * lhi) * 2;
-        const au32x2 h0 = *reinterpret_cast<const au32x2*>(sVh + l31 * VPITCH + kb);
-        const au32x2 h1 = *reinterpret_cast<const au32x2*>(sVh + l31 * VPITCH + kb + 16);
-        const au32x2 l0 = *reinterpret_cast<const au32x2*>(sVl + l31 * VPITCH + kb);
-        const au32x2 l1 = *reinterpret_cast<const au32x2*>(sVl + l31 * VPITCH + kb + 16);
-        const ah16x8 vh_ = __builtin_bit_cast(ah16x8, au32x4{h0[0], h0[1], h1[0], h1[1]});
-        const ah16x8 vl_ = __builtin_bit_cast(ah16x8, au32x4{l0[0], l0[1], l1[0], l1[1]});
-        if (!single) {
-          o = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh_, bl_, o, 0, 0, 0);
-          o = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl_, bh_, o, 0, 0, 0);
-        }
-        o = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh_, bh_, o, 0, 0, 0);
+        h16x8 ph, pl;
+        p_frag<SINGLE>(st, s, ph, pl);
+        mma3(o, load_vt_frag(sVh + l31 * VPITCH + k0 * 2, s, lhi), load_vt_frag(sVl + l31 * VPITCH + k0 * 2, s, lhi), ph, pl, SINGLE);
       }
-      m = mnew;
     };
     using T_ = std::true_type;
     using F_ = std::false_type;
@@ -1280,19 +912,33 @@ __global__ void __launch_bounds__(64 * NW) window_attn3d_mfma_kernel(const float
       else key_tile(nkt - 1, F_{}, F_{});
     }
     l += __shfl_xor(l, 32, 64);
-    if (qi < N && srow >= 0) {
-      const float inv = 1.0f / l;
-      float* po = out + (long long)srow * C + h * HD;
-#pragma unroll
-      for (int g4 = 0; g4 < 4; ++g4) {
-        f32x4 v = {o[4 * g4] * inv, o[4 * g4 + 1] * inv, o[4 * g4 + 2] * inv, o[4 * g4 + 3] * inv};
-        *reinterpret_cast<f32x4*>(po + 8 * g4 + 4 * lhi) = v;
-      }
-    }
+    if (qi < N && srow >= 0) store_o(out + (long long)srow * C + h * HD, o, 1.0f / l, lhi);
   }
 }
 
+// what tce_mha_f32 and tce_mha_ws_f32 are called with, in the order their kernels take it
+struct MhaArgs {
+  const float *Q, *K, *V;
+  float* O;
+  int batch, nheads, Lq, Lk, ldq, ldk, ldv, ldo;
+  long long sQ, sK, sV, sO;
+  const uint8_t* kmask;
+  float scale;
+};
+
 }  // namespace
+
+// the checks both entry points make; ws: tce_mha_ws_f32's workspace (nullptr when the entry has none)
+static int mha_check_args(const char* name, const MhaArgs& a, const void* ws, const bool has_ws) {
+  TCE_CHECK_ARG(a.Q && a.K && a.V && a.O && (ws || !has_ws), "%s: null pointer", name);
+  TCE_CHECK_ARG(a.batch > 0 && a.nheads > 0 && a.Lq > 0 && a.Lk > 0, "%s: bad sizes", name);
+  TCE_CHECK_ARG(a.ldq % 4 == 0 && a.ldk % 4 == 0 && a.ldv % 4 == 0 && a.ldo % 4 == 0 && a.sQ % 4 == 0 && a.sK % 4 == 0 &&
+                    a.sV % 4 == 0 && a.sO % 4 == 0,
+                "%s: leading dims / strides must be multiples of 4", name);
+  TCE_CHECK_ARG(tce_aligned16(a.Q) && tce_aligned16(a.K) && tce_aligned16(a.V) && tce_aligned16(a.O) && tce_aligned16(ws),
+                "%s: pointers must be 16-byte aligned", name);
+  return TCE_OK;
+}
 
 static int g_window_attn_mfma = 1;  // tuning aid (tce_debug_window_attn_set_mfma): 0 = the VALU kernel
 static int g_window_attn_2d_split = 1;  // tuning aid (tce_debug_window_attn_set_mfma(2 / 3)): 0 = 2-D windows on the exact-fp32 MFMA kernel
@@ -1318,12 +964,7 @@ extern "C" int tce_window_attn_f32(const float* qkv, const float* qkv_bias, cons
     // carries qkv = bias --, same region mask; relative-position index (dy+6)*13 + (dx+6) = the kernel's code difference with the
     // nominal window (1,7,7)): 49 keys in two tiles, two waves per (window, head), 20 KB of LDS -- five times fewer MFMA cycles than
     // the exact-fp32 kernel below and no per-score index arithmetic (profiles/r04_window_attn2d.txt)
-    Win3D g;
-    g.D = T; g.H = H; g.W = W;
-    g.wd = 1; g.wh = 7; g.ww = 7;
-    g.sd = 0; g.sh = shift; g.sw = shift;
-    g.Dp = T; g.Hp = nWy * 7; g.Wp = nWx * 7;
-    g.fd = 1; g.fh = 7; g.fw = 7;
+    const Win3D g = Win3D::make(T, H, W, 1, shift, false);
     TCE_CHECK_ARG(total < (1ll << 31), "tce_window_attn_f32: too many (window, head) items");
     TCE_BY_SINGLE(tce_gemm_single_pass(), (window_attn3d_mfma_kernel<2, 64, 13 * 13, true>), (window_attn3d_mfma_kernel<2, 64, 13 * 13, false>),
                   dim3((unsigned)total), dim3(128), 0, (hipStream_t)stream, qkv, qkv_bias, bias_table, out, g, C, nH, 13 * 13, 64);
@@ -1350,13 +991,13 @@ extern "C" int tce_debug_mha_set_split(int32_t on) {
 extern "C" int tce_mha_f32(const float* Q, const float* K, const float* V, float* O, int32_t batch, int32_t nheads,
                            int32_t Lq, int32_t Lk, int32_t ldq, int32_t ldk, int32_t ldv, int32_t ldo, int64_t sQ,
                            int64_t sK, int64_t sV, int64_t sO, const uint8_t* kmask, float scale, tceStream stream) {
-  TCE_CHECK_ARG(Q && K && V && O, "tce_mha_f32: null pointer");
-  TCE_CHECK_ARG(batch > 0 && nheads > 0 && Lq > 0 && Lk > 0, "tce_mha_f32: bad sizes");
-  TCE_CHECK_ARG(ldq % 4 == 0 && ldk % 4 == 0 && ldv % 4 == 0 && ldo % 4 == 0 && sQ % 4 == 0 && sK % 4 == 0 &&
-                    sV % 4 == 0 && sO % 4 == 0,
-                "tce_mha_f32: leading dims / strides must be multiples of 4");
-  TCE_CHECK_ARG(tce_aligned16(Q) && tce_aligned16(K) && tce_aligned16(V) && tce_aligned16(O),
-                "tce_mha_f32: pointers must be 16-byte aligned");
+  const MhaArgs a{Q, K, V, O, batch, nheads, Lq, Lk, ldq, ldk, ldv, ldo, sQ, sK, sV, sO, kmask, scale};
+  if (const int e = mha_check_args("tce_mha_f32", a, nullptr, false)) return e;
+  // every kernel of this entry takes the same arguments
+  auto launch = [&](auto kernel, dim3 grid, int nthr) {
+    hipLaunchKernelGGL(kernel, grid, dim3(nthr), 0, (hipStream_t)stream, a.Q, a.K, a.V, a.O, a.nheads, a.Lq, a.Lk, a.ldq, a.ldk,
+                       a.ldv, a.ldo, a.sQ, a.sK, a.sV, a.sO, a.kmask, a.scale);
+  };
   // 32 queries per wavefront; 4 waves share the K/V tiles when there are enough query tiles to fill the chip
   const long long tiles = (long long)tce_cdiv(Lq, 32) * batch * nheads;
   const int nw = (tiles >= 4096) ? 4 : 1;
@@ -1364,29 +1005,20 @@ extern "C" int tce_mha_f32(const float* Q, const float* K, const float* V, float
   // split-fp16 / fp16 modes: long key sequences on the fp16 matrix cores (5x fewer MFMA cycles per key tile); short ones
   // (text keys, frame tokens) are launch-bound either way and stay on the exact kernel, as does mode 0
   if (g_mha_split && tce_get_gemm_mode() != 0 && Lk >= 256) {
-    const int single = tce_gemm_single_pass();
+    const bool single = tce_gemm_single_pass();
     // few query tiles against many keys: split the keys over the 4 waves of a workgroup (4x shorter serial chains)
     const bool ksplit = tiles < 4096 && Lk >= 1024;
-    if (ksplit) {
-      dim3 gk(tce_cdiv(Lq, 32), batch * nheads);
-      TCE_BY_SINGLE(single, (mha_f16x3_kernel<4, true, true>), (mha_f16x3_kernel<4, true, false>), gk, dim3(256), 0, (hipStream_t)stream, Q,
-                    K, V, O, nheads, Lq, Lk, ldq, ldk, ldv, ldo, (long long)sQ, (long long)sK, (long long)sV, (long long)sO, kmask, scale);
-    } else if (nw == 4) {
-      TCE_BY_SINGLE(single, (mha_f16x3_kernel<4, false, true>), (mha_f16x3_kernel<4, false, false>), grid, dim3(256), 0, (hipStream_t)stream,
-                    Q, K, V, O, nheads, Lq, Lk, ldq, ldk, ldv, ldo, (long long)sQ, (long long)sK, (long long)sV, (long long)sO, kmask, scale);
-    } else {
-      TCE_BY_SINGLE(single, (mha_f16x3_kernel<1, false, true>), (mha_f16x3_kernel<1, false, false>), grid, dim3(64), 0, (hipStream_t)stream,
-                    Q, K, V, O, nheads, Lq, Lk, ldq, ldk, ldv, ldo, (long long)sQ, (long long)sK, (long long)sV, (long long)sO, kmask, scale);
-    }
-    TCE_CHECK_LAUNCH("tce_mha_f32");
-    return TCE_OK;
+    if (ksplit)
+      launch(single ? mha_f16x3_kernel<4, true, true> : mha_f16x3_kernel<4, true, false>, dim3(tce_cdiv(Lq, 32), batch * nheads), 256);
+    else if (nw == 4)
+      launch(single ? mha_f16x3_kernel<4, false, true> : mha_f16x3_kernel<4, false, false>, grid, 256);
+    else
+      launch(single ? mha_f16x3_kernel<1, false, true> : mha_f16x3_kernel<1, false, false>, grid, 64);
+  } else if (nw == 4) {
+    launch(mha_mfma_kernel<4>, grid, 256);
+  } else {
+    launch(mha_mfma_kernel<1>, grid, 64);
   }
-  if (nw == 4)
-    hipLaunchKernelGGL(mha_mfma_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, Q, K, V, O, nheads, Lq, Lk, ldq, ldk,
-                       ldv, ldo, (long long)sQ, (long long)sK, (long long)sV, (long long)sO, kmask, scale);
-  else
-    hipLaunchKernelGGL(mha_mfma_kernel<1>, grid, dim3(64), 0, (hipStream_t)stream, Q, K, V, O, nheads, Lq, Lk, ldq, ldk,
-                       ldv, ldo, (long long)sQ, (long long)sK, (long long)sV, (long long)sO, kmask, scale);
   TCE_CHECK_LAUNCH("tce_mha_f32");
   return TCE_OK;
 }
@@ -1400,30 +1032,24 @@ extern "C" int tce_mha_ws_f32(const float* Q, const float* K, const float* V, fl
                               int32_t nheads, int32_t Lq, int32_t Lk, int32_t ldq, int32_t ldk, int32_t ldv, int32_t ldo,
                               int64_t sQ, int64_t sK, int64_t sV, int64_t sO, const uint8_t* kmask, float scale,
                               tceStream stream) {
-  TCE_CHECK_ARG(Q && K && V && O && ws, "tce_mha_ws_f32: null pointer");
-  TCE_CHECK_ARG(batch > 0 && nheads > 0 && Lq > 0 && Lk > 0, "tce_mha_ws_f32: bad sizes");
-  TCE_CHECK_ARG(ldq % 4 == 0 && ldk % 4 == 0 && ldv % 4 == 0 && ldo % 4 == 0 && sQ % 4 == 0 && sK % 4 == 0 &&
-                    sV % 4 == 0 && sO % 4 == 0,
-                "tce_mha_ws_f32: leading dims / strides must be multiples of 4");
-  TCE_CHECK_ARG(tce_aligned16(Q) && tce_aligned16(K) && tce_aligned16(V) && tce_aligned16(O) && tce_aligned16(ws),
-                "tce_mha_ws_f32: pointers must be 16-byte aligned");
+  const MhaArgs a{Q, K, V, O, batch, nheads, Lq, Lk, ldq, ldk, ldv, ldo, sQ, sK, sV, sO, kmask, scale};
+  if (const int e = mha_check_args("tce_mha_ws_f32", a, ws, true)) return e;
   TCE_CHECK_ARG(tce_get_gemm_mode() != 0, "tce_mha_ws_f32: split-fp16 arithmetic; in exact-fp32 mode use tce_mha_f32");
   const int Lkp = (Lk + 31) / 32 * 32;
   const long long plane = (long long)batch * nheads * Lkp * 64;
   const int single = tce_gemm_single_pass();
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(mha_planes_kernel, dim3(Lkp / 32, batch * nheads), dim3(256), 0, s, K, V, (unsigned char*)ws, nheads, Lk,
-                     Lkp, ldk, ldv, (long long)sK, (long long)sV, plane, single);
+                     Lkp, ldk, ldv, a.sK, a.sV, plane, single);
+  auto launch = [&](auto kernel, int qtiles_per_wg) {
+    hipLaunchKernelGGL(kernel, dim3(tce_cdiv(Lq, 32 * qtiles_per_wg), batch * nheads), dim3(256), 0, s, a.Q, (const unsigned char*)ws,
+                       a.O, a.nheads, a.Lq, a.Lk, Lkp, a.ldq, a.ldo, a.sQ, a.sO, plane, a.kmask, a.scale);
+  };
   const long long tiles = (long long)tce_cdiv(Lq, 32) * batch * nheads;
-  if (tiles < 4096) {  // too few query tiles to fill the chip: the 4 waves of a workgroup split the keys
-    TCE_BY_SINGLE(single, (mha_presplit_kernel<true, true>), (mha_presplit_kernel<true, false>), dim3(tce_cdiv(Lq, 32), batch * nheads),
-                  dim3(256), 0, s, Q, (const unsigned char*)ws, O, nheads, Lq, Lk, Lkp, ldq, ldo, (long long)sQ, (long long)sO, plane, kmask,
-                  scale);
-  } else {
-    TCE_BY_SINGLE(single, (mha_presplit_kernel<false, true>), (mha_presplit_kernel<false, false>), dim3(tce_cdiv(Lq, 128), batch * nheads),
-                  dim3(256), 0, s, Q, (const unsigned char*)ws, O, nheads, Lq, Lk, Lkp, ldq, ldo, (long long)sQ, (long long)sO, plane, kmask,
-                  scale);
-  }
+  if (tiles < 4096)  // too few query tiles to fill the chip: the 4 waves of a workgroup split the keys
+    launch(single ? mha_presplit_kernel<true, true> : mha_presplit_kernel<true, false>, 1);
+  else
+    launch(single ? mha_presplit_kernel<false, true> : mha_presplit_kernel<false, false>, 4);
   TCE_CHECK_LAUNCH("tce_mha_ws_f32");
   return TCE_OK;
 }
@@ -1435,20 +1061,7 @@ extern "C" int tce_window_attn3d_f32(const float* qkv, const float* qkv_bias, co
   TCE_CHECK_ARG(T > 0 && H > 0 && W > 0 && nH > 0 && C == nH * 32, "tce_window_attn3d_f32: need C == nH*32");
   TCE_CHECK_ARG(tce_aligned16(qkv) && tce_aligned16(qkv_bias) && tce_aligned16(out),
                 "tce_window_attn3d_f32: pointers must be 16-byte aligned");
-  Win3D g;
-  g.D = T; g.H = H; g.W = W;
-  g.fd = 8; g.fh = 7; g.fw = 7;
-  const int size[3] = {T, H, W}, full[3] = {8, 7, 7};
-  int win[3], sh[3], pad[3];
-  for (int i = 0; i < 3; ++i) {  // get_window_size: shrink (and never shift) a dim that fits in one window
-    const bool fits = size[i] <= full[i];
-    win[i] = fits ? size[i] : full[i];
-    sh[i] = (fits || !shifted) ? 0 : full[i] / 2;
-    pad[i] = (size[i] + win[i] - 1) / win[i] * win[i];
-  }
-  g.wd = win[0]; g.wh = win[1]; g.ww = win[2];
-  g.sd = sh[0]; g.sh = sh[1]; g.sw = sh[2];
-  g.Dp = pad[0]; g.Hp = pad[1]; g.Wp = pad[2];
+  const Win3D g = Win3D::make(T, H, W, 8, shifted ? 3 : 0, true);
   const int N = g.wd * g.wh * g.ww;
   const int table_rows = (2 * 8 - 1) * 13 * 13;
   const int nwin = (g.Dp / g.wd) * (g.Hp / g.wh) * (g.Wp / g.ww);

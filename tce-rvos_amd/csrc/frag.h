@@ -1,4 +1,5 @@
-// Fragment-level helpers shared by the token-stationary kernels (tiles.h and its users, swinattn.hip): fp16 hi/lo operand splitting,
+// Fragment-level helpers shared by the token-stationary kernels (tiles.h and its users, swinattn.hip), the attention kernels
+// (attn_tile.h) and thin.hip: the accumulator row map, fp16 hi/lo operand splitting, the three-MFMA product,
 // the 1 KiB "piece" = one wave-wide 16-byte-per-lane LDS-DMA / ds_read_b128, and the per-wave LDS staging tile.
 #pragma once
 #include "common.h"
@@ -8,6 +9,10 @@ namespace {
 typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
 typedef __fp16 fp16x2_t __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+
+// Row of a 32x32 MFMA result held in accumulator register r (0..15) of lane half hi (lane >> 5); its column is lane & 31
+__host__ __device__ __forceinline__ int crow(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
 
 constexpr int PIECE = 1024;  // one wave-wide 16-byte-per-lane DMA / ds_read_b128
 
@@ -17,6 +22,27 @@ constexpr int PIECE = 1024;  // one wave-wide 16-byte-per-lane DMA / ds_read_b12
 __device__ __forceinline__ void glds16(const unsigned char* sbase, unsigned voff, unsigned lds_dst) {
   asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %0" ::"s"(sbase), "v"(voff), "s"(lds_dst)
                : "memory");
+}
+
+// Two fp32 -> one packed fp16 pair of the hi plane and one of the lo plane: one q step of split8 below
+__device__ __forceinline__ void split2(const float a, const float b, unsigned& hi, unsigned& lo, const int single) {
+  if (single) {
+    hi = __builtin_bit_cast(unsigned, fp16x2_t{(__fp16)a, (__fp16)b});
+    lo = 0u;
+    return;
+  }
+  const fp16x2_t h = __builtin_amdgcn_cvt_pkrtz(a, b);
+  hi = __builtin_bit_cast(unsigned, h);
+  lo = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(a - (float)h[0], b - (float)h[1]));
+}
+
+// D += A B in the library's arithmetic: three MFMAs on the hi/lo split (cross terms first), one in single mode
+__device__ __forceinline__ void mma3(f32x16& d, const h16x8 ah, const h16x8 al, const h16x8 bh, const h16x8 bl, const int single) {
+  if (!single) {
+    d = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, d, 0, 0, 0);
+    d = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, d, 0, 0, 0);
+  }
+  d = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, d, 0, 0, 0);
 }
 
 struct HL {

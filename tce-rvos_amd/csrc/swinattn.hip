@@ -60,19 +60,8 @@ struct SwinArgs {
   unsigned colhi[2];    // the same for columns
 };
 
-__device__ __forceinline__ int crow_(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
-
 // The head's steps run under static_for (tiles.h): a `#pragma unroll` over the head's 24..64 steps is not honoured by the
 // optimiser, and every per-step decision below must be a compile-time one: register arrays, ring offsets.
-
-// D += A B in the library's arithmetic: three MFMAs on the hi/lo split (cross terms first), one in single mode
-__device__ __forceinline__ void mma3(f32x16& d, const h16x8 ah, const h16x8 al, const h16x8 bh, const h16x8 bl, const int single) {
-  if (!single) {
-    d = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, d, 0, 0, 0);
-    d = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, d, 0, 0, 0);
-  }
-  d = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, d, 0, 0, 0);
-}
 
 // accumulator registers 8s..8s+7 -> fp16 hi/lo fragment of k-step s (s = 0, 1)
 __device__ __forceinline__ HL acc_frag(const f32x16& a, const int s, const int single) {
@@ -481,7 +470,7 @@ extern "C" int tce_swin_attn_fused_f32(const float* x, int64_t ldx, const void* 
     for (int i = 0; i < 8; ++i) a.cj[hf][i] = 0u;
     for (int slot = 0; slot < 32; ++slot) {
       const int kt = slot >> 4, r = slot & 15;
-      const int j = kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * hf, jc = j < NTOK ? j : NTOK - 1;
+      const int j = kt * 32 + crow(r, hf), jc = j < NTOK ? j : NTOK - 1;
       const int jy = jc / WS, jx = jc % WS;
       a.cj[hf][slot >> 2] |= (unsigned)(jy * (2 * WS - 1) + jx) << (8 * (slot & 3));
       if (j < NTOK) a.kvalid[hf] |= 1u << slot;

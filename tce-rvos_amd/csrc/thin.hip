@@ -30,8 +30,6 @@ struct ThinArgs {
   int* range_flag;      // tce_set_range_flag: PRO reports on the finished x (it is split here and never stored)
 };
 
-__device__ __forceinline__ int crow_t(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
-
 template <bool PRO, bool SINGLE>  // SINGLE: the arithmetic mode as a compile-time parameter (see ffn_fused_kernel, ffn.hip)
 __global__ void __launch_bounds__(256) thin_partials_kernel(const ThinArgs p) {
   // per wave: one staging tile for W and one for x (32 rows x 32 floats, 144-byte pitch: conflict-free for the row-of-8-lanes
@@ -129,7 +127,7 @@ __global__ void __launch_bounds__(256) thin_partials_kernel(const ThinArgs p) {
   for (int q = 0; q < 4; ++q) {
     const int i = 4 * wave + q;
     const float v = (sRed[0][i][lane] + sRed[1][i][lane]) + (sRed[2][i][lane] + sRed[3][i][lane]);
-    const int row = m0 + crow_t(i, hf);
+    const int row = m0 + crow(i, hf);
     if (row < p.M) plane_out[(long long)row * p.N + n0 + l31] = v;
   }
 }

@@ -24,8 +24,8 @@ def mha_form(batch, nh, Lq, Lk, mode, ws):
 
     A RESTATEMENT of the dispatch, not a query: the library has no entry that reports which kernel ran.  It mirrors
     ops.mha_core (ops.py: the workspace form needs an allocator, Lk >= ops.MHA_WS_MIN_KEYS and a split mode), tce_mha_f32
-    (attn.hip:1361-1389: tiles, nw, the Lk >= 256 split-mode branch, ksplit = tiles < 4096 && Lk >= 1024) and tce_mha_ws_f32
-    (attn.hip:1417-1426: tiles < 4096 picks the KSPLIT instantiation).  If the dispatcher changes, this changes with it.
+    (attn.hip, the body of tce_mha_f32: tiles, nw, the Lk >= 256 split-mode branch, ksplit = tiles < 4096 && Lk >= 1024) and
+    tce_mha_ws_f32 (attn.hip: tiles < 4096 picks the KSPLIT instantiation).  If the dispatcher changes, this changes with it.
         F1 mha_mfma_kernel<1>   F2 mha_mfma_kernel<4>   F3 mha_f16x3_kernel<1,false>   F4 mha_f16x3_kernel<4,false>
         F5 mha_f16x3_kernel<4,KSPLIT>   F6 mha_presplit_kernel<KSPLIT>   F7 mha_presplit_kernel<false>"""
     from tce_rvos_amd import ops
@@ -69,7 +69,7 @@ def case(name):
 # Key masks: uint8 [batch, Lk], non-zero = ignore the key
 # ---------------------------------------------------------------------------------------------------------------
 def wave_tiles(Lk, w):
-    """[t_begin, t_end) of KSPLIT wave w, the kernels' own formula (attn.hip:382-383, :626-627)."""
+    """[t_begin, t_end) of KSPLIT wave w, the kernels' own formula (attn.hip: t_begin / t_end of mha_f16x3_kernel and mha_presplit_kernel)."""
     nt = cdiv(Lk, KT)
     return w * nt // NW, (w + 1) * nt // NW
 
