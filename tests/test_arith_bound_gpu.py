@@ -16,6 +16,7 @@ import torch.nn.functional as F
 
 import _arith as A
 from _attn import attention_ref_and_bound
+from _window import bias_3d, to_windows2d, to_windows3d, windows_ref_and_bound
 
 pytestmark = pytest.mark.gpu
 
@@ -541,40 +542,6 @@ def test_patch_embed(ops, T, H, W, C):
 # ---------------------------------------------------------------------------------------------------------------
 # Attention cores (unit scale, composed softmax bound)
 # ---------------------------------------------------------------------------------------------------------------
-def windows_ref_and_bound(qkv_w, nh, bias, mask, Bqkv=None):
-    """qkv_w [nW, N, 3C] (windows of q | k | v rows), bias [nh, N, N], mask [nWm, N, N] or None -> ([nW, N, C] ref, bound, S)."""
-    nW, N, C3 = qkv_w.shape
-    C = C3 // 3
-    ref, B, S = (torch.zeros(nW, N, C, dtype=torch.float64) for _ in range(3))
-    for w in range(nW):
-        for h in range(nh):
-            sl = [slice(j * C + 32 * h, j * C + 32 * h + 32) for j in range(3)]
-            add = bias[h].double() + (mask[w % mask.shape[0]].double() if mask is not None else 0.0)
-            eb = [Bqkv[w][:, s_] for s_ in sl] if Bqkv is not None else [None] * 3
-            r, b, s_ = attention_ref_and_bound(qkv_w[w][:, sl[0]], qkv_w[w][:, sl[1]], qkv_w[w][:, sl[2]], 32 ** -0.5, add, *eb)
-            ref[w][:, 32 * h:32 * h + 32], B[w][:, 32 * h:32 * h + 32], S[w][:, 32 * h:32 * h + 32] = r, b, s_
-    return ref, B, S
-
-
-def to_windows2d(g, T, H, W, shift, fill):
-    """[T*H*W, Cx] -> ([nW, 49, Cx] windows of the padded, shifted grid; pad positions hold `fill`), and the inverse map."""
-    Cx = g.shape[-1]
-    Hp, Wp = (H + 6) // 7 * 7, (W + 6) // 7 * 7
-    grid = fill.to(g.dtype).expand(T, Hp, Wp, Cx).clone()
-    grid[:, :H, :W] = g.view(T, H, W, Cx)
-    if shift:
-        grid = torch.roll(grid, shifts=(-shift, -shift), dims=(1, 2))
-    win = grid.view(T, Hp // 7, 7, Wp // 7, 7, Cx).permute(0, 1, 3, 2, 4, 5).reshape(-1, 49, Cx)
-
-    def back(y):
-        C = y.shape[-1]
-        y = y.view(T, Hp // 7, Wp // 7, 7, 7, C).permute(0, 1, 3, 2, 4, 5).reshape(T, Hp, Wp, C)
-        if shift:
-            y = torch.roll(y, shifts=(shift, shift), dims=(1, 2))
-        return y[:, :H, :W].reshape(T * H * W, C)
-    return win, back, (Hp, Wp)
-
-
 @pytest.mark.parametrize("T,H,W,nH,shift", [(2, 18, 25, 3, 0), (2, 18, 25, 3, 3), (1, 9, 13, 6, 3), (1, 7, 7, 1, 3), (1, 14, 21, 2, 0)])
 def test_window_attn(ops, T, H, W, nH, shift):
     """2-D window attention core on a given qkv tensor (padding rows hold the qkv bias), relative-position bias, -100 shift mask."""
@@ -595,30 +562,12 @@ def test_window_attn(ops, T, H, W, nH, shift):
                                                (8, 16, 23, 2, True), (16, 14, 7, 1, True)])
 def test_window_attn3d(ops, T, H, W, nH, shifted):
     """3-D (8, 7, 7) window attention core on a given qkv tensor."""
-    from oracle import tce_oracle as O
     g = torch.Generator().manual_seed(T * H + W)
     C = nH * 32
     qkv, qb = torch.randn(T * H * W, 3 * C, generator=g), torch.randn(3 * C, generator=g) * 0.3
     table = torch.randn(15 * 13 * 13, nH, generator=g)
-    full = (8, 7, 7)
-    ws, ss = O.get_window_size_3d((T, H, W), full, tuple(i // 2 for i in full) if shifted else (0, 0, 0))
-    Dp, Hp, Wp = (-(-n // w) * w for n, w in zip((T, H, W), ws))
-    grid = qb.expand(1, Dp, Hp, Wp, 3 * C).clone()
-    grid[0, :T, :H, :W] = qkv.view(T, H, W, 3 * C)
-    mask = None
-    if any(i > 0 for i in ss):
-        grid = torch.roll(grid, shifts=(-ss[0], -ss[1], -ss[2]), dims=(1, 2, 3))
-        mask = O.compute_mask_3d(Dp, Hp, Wp, ws, ss)
-    win = O.window_partition_3d(grid, ws)
-    N = win.shape[1]
-    bias = table[O.rel_pos_index_3d(*full)[:N, :N].reshape(-1)].reshape(N, N, nH).permute(2, 0, 1)
-    ref, B, S = windows_ref_and_bound(win, nH, bias, mask)
-
-    def back(y):
-        y = O.window_reverse_3d(y, ws, 1, Dp, Hp, Wp)
-        if any(i > 0 for i in ss):
-            y = torch.roll(y, shifts=(ss[0], ss[1], ss[2]), dims=(1, 2, 3))
-        return y[0, :T, :H, :W].reshape(T * H * W, C)
+    win, back, mask, N = to_windows3d(qkv, T, H, W, shifted, qb)
+    ref, B, S = windows_ref_and_bound(win, nH, bias_3d(table, nH, N), mask)
     out = ops.window_attn3d(dev(qkv), dev(qb), dev(table), T, H, W, C, nH, shifted)
     check("window_attn3d", f"{T}x{H}x{W} C={C} shifted={shifted}", tag(1, 1), out, back(ref), back(B), back(S))
 
